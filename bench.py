@@ -12,6 +12,7 @@ token ids) are resident in HBM before the timed region.  Prints ONE JSON line (r
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -245,6 +246,29 @@ def box_calibration(H, dev, warm_seconds=2.0, launches=20):
     return out
 
 
+def dump_outputs(out_dir, loss, arena, max_elems=1 << 22):
+    """--dump-outputs: what the last timed step handed back, as float32 .npy files for output-by-output comparison of two
+    builds: `loss.npy` (its loss), `params.npy` (the trainable parameters after its update) and `grads.npy` (the gradients it
+    computed), ~32 MB in all.  The flat arena holds ~131 M trainable values, so both arrays are the same fixed sample of
+    `max_elems` of them, drawn with a seeded generator over the true (unpadded) elements in arena order: the sample is the
+    same whatever the arena's alignment padding.  Every element when there are no more than `max_elems`."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = torch.tensor([math.prod(arena.shapes[n]) for n in arena.names], dtype=torch.int64)
+    offs = torch.tensor([arena.offsets[n] for n in arena.names], dtype=torch.int64)
+    end = sizes.cumsum(0)
+    n = int(end[-1])
+    if n <= max_elems:
+        r = torch.arange(n)
+    else:
+        r = torch.randint(0, n, (max_elems,), generator=torch.Generator().manual_seed(0)).sort().values
+    t = torch.searchsorted(end, r, right=True)                            # tensor that true element r belongs to
+    pos = (offs[t] + r - (end[t] - sizes[t])).to(arena.params.device)
+    arrays = {"loss": loss.detach().float().reshape(1), "params": arena.params[pos], "grads": arena.grads[pos]}
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -293,7 +317,12 @@ def main():
     ap.add_argument("--no-gemm-tail-skip", action="store_true", help="A/B: the 256x256 GEMM re-loads dead LDS slots past its last K-tile (rounds 1-3) instead of stopping the half-tile stream there")
     ap.add_argument("--no-swiglu-fusion", action="store_true", help="A/B: silu(gate) * up and its backward as their own HBM passes instead of inside the gate|up / d(act) GEMM epilogues")
     ap.add_argument("--full-lm-head", action="store_true", help="A/B: lm_head / CE over the whole token grid, not only the target rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's loss and a fixed sample of the updated parameters and of its "
+                         "gradients to DIR/*.npy (float32; rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.cpu_full_step:                                  # host-only leg, no device involved
         sys.path.insert(0, os.path.join(ROOT, "desta2.5-audio_amd"))
@@ -486,6 +515,8 @@ def main():
     prof_timed = H.gemm_profile_stop(by_kernel=True) if a.timed_gemm_events else None
     comm, trainer.comm_profile = trainer.comm_profile, None
     per_step = [x.elapsed_time(y) for x, y in zip(step_events[:-1], step_events[1:])]
+    if a.dump_outputs and rank == 0:                     # before the kernel pass below steps the model on
+        dump_outputs(a.dump_outputs, loss, model.arena)
     # UNTIMED, UN-OVERLAPPED pass (the `roofline` leg): the same steps with EVERY side stream off — optimizer tail, connector backward,
     # encoder prefetch, K | V projections and weight gradients all in line on the main stream — and HIP events around every GEMM
     # launch and every tagged HBM-bound / attention launch.  Beside another stream two kernels time-share the chip and each one's

@@ -44,12 +44,64 @@ def test_world_size_mismatch_exits_nonzero():
     assert p.returncode == 2 and "does not match WORLD_SIZE" in p.stderr and not p.stdout.strip()
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _padded_arena(shapes, align):
+    """Stand-in for desta.optim.ParamArena: true element k holds k (params) / -k (grads), the alignment padding holds NaN."""
+    import math
+    import types
+    import torch
+    a = types.SimpleNamespace(names=[], shapes={}, offsets={})
+    off = 0
+    for i, s in enumerate(shapes):
+        a.names.append(f"t{i}")
+        a.shapes[f"t{i}"], a.offsets[f"t{i}"] = tuple(s), off
+        off += -(-math.prod(s) // align) * align
+    a.params, a.grads = torch.full((off,), float("nan")), torch.full((off,), float("nan"))
+    k = 0
+    for n in a.names:
+        m, o = math.prod(a.shapes[n]), a.offsets[n]
+        a.params[o:o + m] = torch.arange(k, k + m, dtype=torch.float32)
+        a.grads[o:o + m] = -a.params[o:o + m]
+        k += m
+    return a
+
+
+def test_dump_outputs_samples_true_elements_only(tmp_path):
+    """--dump-outputs: float32 files, every true element when the arena is small, otherwise a fixed seeded sample that never
+    lands on alignment padding and does not depend on the padding."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    shapes = [(3, 5), (7,), (100, 33), (1,), (50, 50)]
+    n_true = 15 + 7 + 3300 + 1 + 2500
+    for max_elems in (1 << 22, 500):
+        got = []
+        for align in (64, 256):
+            d = tmp_path / f"{max_elems}_{align}"
+            bench.dump_outputs(str(d), torch.tensor(1.25), _padded_arena(shapes, align), max_elems=max_elems)
+            f = {k: np.load(d / f"{k}.npy") for k in ("loss", "params", "grads")}
+            assert all(v.dtype == np.float32 for v in f.values()) and f["loss"].tolist() == [1.25]
+            assert f["params"].size == min(n_true, max_elems) and np.isfinite(f["params"]).all()
+            assert (f["grads"] == -f["params"]).all()
+            got.append(f["params"])
+        assert (got[0] == got[1]).all()
+        if max_elems > n_true:
+            assert (got[0] == np.arange(n_true)).all()
+
+
 @pytest.mark.gpu
-def test_two_rank_bench_on_one_card_reports_the_exchange():
+def test_two_rank_bench_on_one_card_reports_the_exchange(tmp_path):
     """The real bench through its own launcher at N = 2 (two ranks share cuda:0 over gloo: the box has one GPU): n_gpus == 2,
     the all-reduce / wait_update fields are present, value = steps / time (optimizer steps of the node), gpu_batch_steps_per_s = 2 x that."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--single-device",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-pass", "--no-calibration"],
+                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-kernel-pass", "--no-calibration", "--dump-outputs", str(tmp_path)],
                        env=dict(ENV, HSA_ENABLE_IPC_MODE_LEGACY="0"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     line = _json_line(p.stdout)
@@ -60,3 +112,9 @@ def test_two_rank_bench_on_one_card_reports_the_exchange():
     per_s = 1.0 / (line["ms_per_step"] * 1e-3)
     assert abs(line["value"] - per_s) < 1e-6 and abs(line["gpu_batch_steps_per_s"] - 2 * per_s) < 1e-6
     assert abs(line["samples_per_s"] - 16 * per_s) < 1e-5
+    assert line["steps"] == 2 and len(line["ms_per_step_each"]) == 2
+    import numpy as np
+    loss, params, grads = (np.load(tmp_path / f"{k}.npy") for k in ("loss", "params", "grads"))
+    assert abs(float(loss[0]) - line["final_loss"]) < 1e-6 * max(1.0, abs(line["final_loss"]))
+    assert params.shape == grads.shape == (1 << 22,) and np.isfinite(params).all() and np.isfinite(grads).all()
+    assert np.count_nonzero(grads) > 0.9 * grads.size
