@@ -246,6 +246,24 @@ def clip_adafactor_step(plan: OptPlan, params, grads, state, workspace, lr, beta
                      clip_threshold, max_grad_norm, stream()), "desta_clip_adafactor_step")
 
 
+class AdamWPlan(C.Structure):
+    _fields_ = [("items", vp), ("item_wd", vp), ("n_items", i32), ("numel", i64)]
+
+
+ADAMW_ITEM_FLOATS = 4096                                   # DESTA_ADAMW_ITEM_FLOATS
+lib.desta_adamw_workspace_floats.restype = C.c_size_t
+lib.desta_adamw_workspace_floats.argtypes = [C.POINTER(AdamWPlan)]
+_adamw = _sig("desta_clip_adamw_step", C.POINTER(AdamWPlan), vp, vp, vp, vp, vp, f32, C.c_double, C.c_double, f32, f32, f32,
+              f32, vp)
+
+
+@_profiled("clip_adamw", lambda plan, params, *a, **k: 32 * params.numel())              # g twice; p, m, v read + written (fp32)
+def clip_adamw_step(plan: AdamWPlan, params, grads, exp_avg, exp_avg_sq, workspace, lr, beta1, beta2, eps, bc1, bc2,
+                    max_grad_norm):
+    check(_adamw(C.byref(plan), p(params), p(grads), p(exp_avg), p(exp_avg_sq), p(workspace), lr, beta1, beta2, eps, bc1, bc2,
+                 max_grad_norm, stream()), "desta_clip_adamw_step")
+
+
 # ----------------------------------------------------------------------------- norms / activations / layout
 c_size_t = C.c_size_t
 _ln_fwd = _sig("desta_layernorm_fwd", vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, vp)
@@ -647,7 +665,7 @@ def attention_set_concurrent_bwd(on: bool) -> None:
 def _check_struct_layouts() -> None:
     lib.desta_sizeof_desc.restype = C.c_size_t
     lib.desta_sizeof_desc.argtypes = [i32]
-    for which, cls in ((0, GemmDesc), (1, AttnDesc), (2, OptPlan)):
+    for which, cls in ((0, GemmDesc), (1, AttnDesc), (2, OptPlan), (3, AdamWPlan)):
         if lib.desta_sizeof_desc(which) != C.sizeof(cls):
             raise ImportError(f"struct layout mismatch for {cls.__name__}: library {lib.desta_sizeof_desc(which)} B, binding {C.sizeof(cls)} B")
 

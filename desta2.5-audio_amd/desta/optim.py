@@ -1,4 +1,4 @@
-"""Flat fp32 parameter arena + fused clip/Adafactor (host side of csrc/adafactor.hip).
+"""Flat fp32 parameter arena + fused clip/Adafactor and clip/AdamW (host side of csrc/adafactor.hip, csrc/adamw.hip).
 
 Mirrors what the reference gets from HF Trainer: `clip_grad_norm_(1.0)` then
 `transformers.optimization.Adafactor(lr, scale_parameter=False, relative_step=False)` with the
@@ -220,6 +220,7 @@ class FusedAdafactor:
         return {"state": state if self.step_count > 0 else {}, "param_groups": groups}
 
     def load_hf_state_dict(self, sd: dict, ref_names: Sequence[str]) -> None:
+        _require_saved_optimizer(sd, "adafactor")
         dm = dict(zip(ref_names, decay_mask(ref_names)))
         order = [n for n in ref_names if dm[n]] + [n for n in ref_names if not dm[n]]
         self.step_count = 0
@@ -246,6 +247,7 @@ class FusedAdafactor:
         return {"state": st, "names": list(self.arena.names), "step": self.step_count}
 
     def load_state_dict(self, sd: dict) -> None:
+        _require_saved_optimizer(sd, "adafactor")
         self.step_count = int(sd.get("step", 0))
         for i, name in enumerate(self.arena.names):
             ent = sd["state"][i]
@@ -254,3 +256,126 @@ class FusedAdafactor:
                 if key in sl:
                     off, shape = sl[key]
                     self.state[off:off + int(math.prod(shape))].copy_(ent[hf].reshape(-1))
+
+
+def _hf_order(ref_names: Sequence[str]) -> Tuple[List[str], int]:
+    """HF Trainer's two param groups (TF:trainer.py:1181-1195): decay first, each in named_parameters() order."""
+    dm = dict(zip(ref_names, decay_mask(ref_names)))
+    order = [n for n in ref_names if dm[n]] + [n for n in ref_names if not dm[n]]
+    return order, sum(dm.values())
+
+
+def _saved_optimizer(sd: dict) -> str:
+    """Which optimizer wrote a state dict (HF `optimizer.pt` or this module's local form): 'adamw', 'adafactor' or '?'."""
+    if sd.get("optimizer") in ("adamw", "adafactor"):
+        return sd["optimizer"]
+    groups = sd.get("param_groups") or []
+    if groups and "betas" in groups[0]:
+        return "adamw"
+    if groups and ("clip_threshold" in groups[0] or "decay_rate" in groups[0]):
+        return "adafactor"
+    for ent in (sd.get("state") or {}).values():
+        if "exp_avg" in ent:
+            return "adamw"
+        if "exp_avg_sq_row" in ent or "RMS" in ent:
+            return "adafactor"
+    return "?"
+
+
+def _require_saved_optimizer(sd: dict, expected: str) -> None:
+    names = {"adamw": "AdamW", "adafactor": "Adafactor"}
+    got = _saved_optimizer(sd)
+    if got != "?" and got != expected:
+        raise ValueError(f"optimizer state was written by {names[got]}, but this trainer runs {names[expected]}: "
+                         f"a {names[got]} checkpoint cannot resume an {names[expected]} run (set `optim` to match the checkpoint)")
+
+
+class FusedAdamW:
+    """clip_grad_norm_(max_grad_norm) + torch.optim.AdamW over the arena in two launches (csrc/adamw.hip): HF Trainer with
+    optim="adamw_torch" / "adamw_torch_fused" (TF:trainer_optimizer.py:201-208).  State: exp_avg / exp_avg_sq, two fp32
+    buffers the size of the arena; the step count lives on the host (bias corrections in double, as torch forms them)."""
+
+    def __init__(self, arena: ParamArena, weight_decay: float = 0.0, betas: Tuple[float, float] = (0.9, 0.999),
+                 eps: float = 1e-8, max_grad_norm: float = 1.0, decay: Sequence[bool] = None, torch_fused: bool = False):
+        self.arena = arena
+        self.beta1, self.beta2 = float(betas[0]), float(betas[1])
+        self.eps, self.max_grad_norm = float(eps), float(max_grad_norm)
+        self.torch_fused = bool(torch_fused)                   # only recorded in the HF wire format (`fused` of the param groups)
+        self.step_count = 0
+        dev = arena.params.device
+        decay = decay_mask(arena.names) if decay is None else list(decay)
+        items, wd = [], []
+        for name, dk in zip(arena.names, decay):
+            off, n = arena.offsets[name], _al(int(math.prod(arena.shapes[name])), 4)   # inside the tensor's 64-float slot
+            for e0 in range(0, n, _hip.ADAMW_ITEM_FLOATS):
+                items.append([off + e0, min(_hip.ADAMW_ITEM_FLOATS, n - e0)])
+                wd.append(weight_decay if dk else 0.0)
+        if not items:
+            raise ValueError("FusedAdamW: the arena holds no trainable values")
+        self._items = torch.tensor(items, dtype=torch.int64, device=dev)
+        self._wd = torch.tensor(wd, dtype=torch.float32, device=dev)
+        pl = _hip.AdamWPlan()
+        pl.items, pl.item_wd, pl.n_items, pl.numel = self._items.data_ptr(), self._wd.data_ptr(), len(items), arena.numel
+        self.plan = pl
+        self.exp_avg = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
+        self.workspace = torch.zeros(_hip.lib.desta_adamw_workspace_floats(ctypes.byref(pl)), dtype=torch.float32, device=dev)
+
+    def step(self, lr: float) -> None:
+        """clip_grad_norm_(max_grad_norm) + AdamW update, in place on the arena (grads are not modified)."""
+        self.step_count += 1
+        bc1 = 1.0 - self.beta1 ** self.step_count
+        bc2 = 1.0 - self.beta2 ** self.step_count
+        _hip.clip_adamw_step(self.plan, self.arena.params, self.arena.grads, self.exp_avg, self.exp_avg_sq, self.workspace,
+                             lr, self.beta1, self.beta2, self.eps, bc1, bc2, self.max_grad_norm)
+
+    def grad_norm(self) -> torch.Tensor:
+        """Pre-clip global gradient norm of the last step (device scalar, no sync)."""
+        return self.workspace[0]
+
+    def _moment(self, buf: torch.Tensor, name: str) -> torch.Tensor:
+        return self.arena._view(buf, name)
+
+    # -- wire format of `torch.optim.AdamW.state_dict()` (torch 2.10) as HF Trainer writes it to checkpoint-<step>/optimizer.pt
+    def hf_state_dict(self, ref_names: Sequence[str], lr: float, weight_decay: float = 0.01) -> dict:
+        order, n_decay = _hf_order(ref_names)
+        state = {}
+        if self.step_count > 0:
+            for idx, name in enumerate(order):
+                state[idx] = {"step": torch.tensor(float(self.step_count), dtype=torch.float32),
+                              "exp_avg": self._moment(self.exp_avg, name).detach().cpu().clone(),
+                              "exp_avg_sq": self._moment(self.exp_avg_sq, name).detach().cpu().clone()}
+        common = {"lr": lr, "betas": (self.beta1, self.beta2), "eps": self.eps, "amsgrad": False, "maximize": False,
+                  "foreach": None, "capturable": False, "differentiable": False, "fused": True if self.torch_fused else None,
+                  "decoupled_weight_decay": True}
+        groups = [dict(weight_decay=weight_decay, **common, params=list(range(n_decay))),
+                  dict(weight_decay=0.0, **common, params=list(range(n_decay, len(order))))]
+        return {"state": state, "param_groups": groups}
+
+    def load_hf_state_dict(self, sd: dict, ref_names: Sequence[str]) -> None:
+        _require_saved_optimizer(sd, "adamw")
+        order, _ = _hf_order(ref_names)
+        self.step_count = 0
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        for idx, name in enumerate(order):
+            ent = sd["state"].get(idx)
+            if ent is None:
+                continue
+            self.step_count = int(float(ent["step"]))
+            self._moment(self.exp_avg, name).copy_(ent["exp_avg"].reshape(self.arena.shapes[name]))
+            self._moment(self.exp_avg_sq, name).copy_(ent["exp_avg_sq"].reshape(self.arena.shapes[name]))
+
+    # -- local form: per arena tensor, in arena order
+    def state_dict(self) -> dict:
+        st = {i: {"step": self.step_count, "exp_avg": self._moment(self.exp_avg, name).clone(),
+                  "exp_avg_sq": self._moment(self.exp_avg_sq, name).clone()} for i, name in enumerate(self.arena.names)}
+        return {"optimizer": "adamw", "state": st, "names": list(self.arena.names), "step": self.step_count}
+
+    def load_state_dict(self, sd: dict) -> None:
+        _require_saved_optimizer(sd, "adamw")
+        self.step_count = int(sd.get("step", 0))
+        for i, name in enumerate(self.arena.names):
+            ent = sd["state"][i]
+            self._moment(self.exp_avg, name).copy_(ent["exp_avg"].reshape(self.arena.shapes[name]))
+            self._moment(self.exp_avg_sq, name).copy_(ent["exp_avg_sq"].reshape(self.arena.shapes[name]))

@@ -23,7 +23,7 @@ import torch
 import torch.distributed as dist
 
 from ..models.modeling_desta25 import DeSTA25AudioModel
-from ..optim import FusedAdafactor, linear_warmup_lr
+from ..optim import FusedAdafactor, FusedAdamW, linear_warmup_lr
 
 
 @dataclass
@@ -40,7 +40,10 @@ class TrainingArguments:
     gradient_accumulation_steps: int = 1
     max_grad_norm: float = 1.0
     logging_steps: int = 10
-    optim: str = "adafactor"
+    optim: str = "adafactor"                       # | "adamw_torch" | "adamw_torch_fused" (HF: both torch.optim.AdamW, TF:trainer_optimizer.py:201-208)
+    adam_beta1: float = 0.9                        # HF TrainingArguments defaults; used by the AdamW optimizers only
+    adam_beta2: float = 0.999
+    adam_epsilon: float = 1e-8
     bf16: bool = True
     overlap_comm: bool = True
     overlap_connector_backward: bool = False       # with overlap_comm: the connector's backward ALSO runs on the side stream (bit-identical results; round 3: -0.4 ms WITHOUT the encoder stream; round 4, beside `overlap_encoder`: +0.5 ms and 4x the step-time spread, same-box A/B -> off)
@@ -56,6 +59,8 @@ class TrainingArguments:
     seed: int = 42                                 # map-style datasets: the epoch's sample order is randperm(seed + epoch)
     shuffle: bool = True                           # (HF: RandomSampler unless group_by_length); False = manifest order
 
+
+OPTIMIZERS = ("adafactor", "adamw_torch", "adamw_torch_fused")        # values of `TrainingArguments.optim` this trainer runs
 
 ALLREDUCE_CALLS: Dict[str, int] = {}              # "<backend>:<op>" -> collectives issued by this process (tests assert which branch ran)
 
@@ -117,12 +122,17 @@ class DeSTA25Trainer:
         self.processing_class = processing_class
         from ..utils.metrics import ConsecutiveWordsAccuracyMetric
         self.metrics = ConsecutiveWordsAccuracyMetric()                       # desta_trainer.py:36
-        if self.args.optim != "adafactor":
-            raise NotImplementedError("only optim='adafactor' (train_desta.py:149) is implemented")
+        if self.args.optim not in OPTIMIZERS:
+            raise NotImplementedError(f"optim={self.args.optim!r} is not implemented (choose one of {', '.join(OPTIMIZERS)})")
         if self.args.gradient_accumulation_steps < 1:
             raise ValueError("gradient_accumulation_steps must be >= 1")
         self._micro, self._acc = 0, None                                      # micro-batches seen in the current accumulation window / their gradient sum
-        self.optimizer = FusedAdafactor(model.arena, weight_decay=self.args.weight_decay, max_grad_norm=self.args.max_grad_norm)
+        if self.args.optim == "adafactor":
+            self.optimizer = FusedAdafactor(model.arena, weight_decay=self.args.weight_decay, max_grad_norm=self.args.max_grad_norm)
+        else:
+            self.optimizer = FusedAdamW(model.arena, weight_decay=self.args.weight_decay,
+                                        betas=(self.args.adam_beta1, self.args.adam_beta2), eps=self.args.adam_epsilon,
+                                        max_grad_norm=self.args.max_grad_norm, torch_fused=self.args.optim == "adamw_torch_fused")
         self.global_step = 0
         self._total_steps: Optional[int] = None
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -238,7 +248,8 @@ class DeSTA25Trainer:
         empty = self._is_empty_batch(inputs)
         if empty and self.world == 1:
             # HF loop on one device: zero loss, backward leaves every .grad None, Adafactor skips every parameter
-            # (TF:optimization.py:1220), the scheduler and global_step still advance
+            # (TF:optimization.py:1220) and so does torch AdamW (parameters, moments and its step count unchanged); the
+            # scheduler and global_step still advance
             self.global_step += 1
             return self.compute_loss(model, inputs)
         prefetch = next_inputs is not None and not self._is_empty_batch(next_inputs)
@@ -618,7 +629,7 @@ class DeSTA25Trainer:
         return ids
 
     # -- HF `checkpoint-<step>/` layout (TF:trainer.py `_save_checkpoint` / `_save_optimizer_and_scheduler` / `_save_rng_state`):
-    #    model.safetensors (trainable-only) + config.json, optimizer.pt (Adafactor state_dict wire format), scheduler.pt (LambdaLR
+    #    model.safetensors (trainable-only) + config.json, optimizer.pt (Adafactor / AdamW state_dict wire format), scheduler.pt (LambdaLR
     #    state), trainer_state.json (TrainerState fields ONLY: `TrainerState.load_from_json` does cls(**json)), rng_state.pth
     #    (rng_state_<rank>.pth under data parallel), training_args.bin; this library's own resume data (forward counter and seed
     #    of the stateless dropout stream) lives in the sidecar desta_hip_state.json, which HF never opens.

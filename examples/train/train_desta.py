@@ -11,7 +11,7 @@ Hydra/OmegaConf are not installed here, so the few features the reference uses a
 the `???` mandatory marker.  `create_model` / `create_training_args` read exactly the keys the reference
 reads (train_desta.py:96-162).  Checkpoints are HF `checkpoint-<step>/` directories written at every epoch end
 (save_strategy="epoch", :146) and `resume_from_checkpoint` is handed to `trainer.train` (:231), which restores the
-parameters, Adafactor moments, schedule position and step.  Datasets: `synthetic: true` streams (benchmarks, tests), or
+parameters, optimizer moments (Adafactor, or AdamW with `optim.name=adamw_torch`), schedule position and step.  Datasets: `synthetic: true` streams (benchmarks, tests), or
 the reference's JSONL manifests through `desta.trainer.data.simple_dataset` (`BaseAudioTextDataset` + `BaseCollateFn`, WAV
 decode + device log-mel) — that path needs the LLM's tokenizer, which is loaded by NAME from the local HF cache
 (`create_tokenizer`; there is no hub access here, tests inject one).
@@ -130,14 +130,23 @@ def create_model(cfg: Cfg, device="cuda:0"):
 
 def create_training_args(cfg: Cfg):
     """Reference train_desta.py:133-162, restricted to what the hot path consumes."""
-    from desta.trainer.desta_trainer import TrainingArguments
+    from desta.trainer.desta_trainer import OPTIMIZERS, TrainingArguments
+    # optim.name (this port's key; absent = the reference's hard-coded "adafactor", :149): an AdamW name takes optim.betas and
+    # the optional optim.eps as HF's adam_beta1 / adam_beta2 / adam_epsilon
+    optim = str(cfg.optim.get("name", "adafactor"))
+    if optim not in OPTIMIZERS:
+        raise ValueError(f"optim.name={optim!r} is not supported (choose one of {', '.join(OPTIMIZERS)})")
+    adam = {}
+    if optim != "adafactor":
+        betas = cfg.optim.get("betas", (0.9, 0.999))
+        adam = dict(adam_beta1=float(betas[0]), adam_beta2=float(betas[1]), adam_epsilon=float(cfg.optim.get("eps", 1e-8)))
     return TrainingArguments(
         output_dir=cfg.exp_dir, num_train_epochs=cfg.trainer.max_epochs,
         per_device_train_batch_size=cfg.dataset.train_ds.batch_size,
         gradient_accumulation_steps=cfg.trainer.accumulate_grad_batches,
         learning_rate=float(cfg.optim.lr), weight_decay=float(cfg.optim.weight_decay),
         warmup_steps=cfg.optim.sched.warmup_steps, logging_steps=cfg.trainer.log_every_n_steps,
-        max_steps=cfg.trainer.get("max_steps", -1), bf16="bf16" in cfg.trainer.precision, optim="adafactor",
+        max_steps=cfg.trainer.get("max_steps", -1), bf16="bf16" in cfg.trainer.precision, optim=optim, **adam,
         save_strategy="epoch" if cfg.trainer.get("enable_checkpointing", False) else "no",
         eval_strategy="steps" if isinstance(cfg.trainer.get("val_check_interval"), int) else "epoch",      # reference :147-148
         eval_steps=cfg.trainer.get("val_check_interval") if isinstance(cfg.trainer.get("val_check_interval"), int) else None,

@@ -37,7 +37,7 @@ extern "C" {
 
 int desta_abi_version(void);
 /* sizeof of the descriptor structs as this library was compiled (0 = desta_gemm_desc, 1 = desta_attn_desc,
- * 2 = desta_opt_plan): a binding checks its own struct layouts against these before the first call. */
+ * 2 = desta_opt_plan, 3 = desta_adamw_plan): a binding checks its own struct layouts against these before the first call. */
 size_t desta_sizeof_desc(int which);
 const char* desta_last_error(void);
 
@@ -177,6 +177,34 @@ size_t desta_adafactor_workspace_floats_v3(const desta_opt_plan* plan, int64_t c
 int desta_clip_adafactor_step(const desta_opt_plan* plan, float* params, const float* grads, float* state,
                               float* workspace, float lr, float beta2t, float eps1, float clip_threshold,
                               float max_grad_norm, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Global-norm clip + AdamW over the same flat fp32 arena (optim="adamw_torch" / "adamw_torch_fused").
+ * Replaces `clip_grad_norm_(params, max_grad_norm)` (TF:trainer.py:1780-1782) followed by
+ * `torch.optim.AdamW(lr, betas=(adam_beta1, adam_beta2), eps=adam_epsilon).step` over the two weight-decay groups
+ * (TF:trainer_optimizer.py:201-208), per element in torch's order:
+ *   g = grad * coef;  p *= 1 - lr wd;  m += (1 - beta1) (g - m);  v = beta2 v + (1 - beta2) g^2;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * with coef = min(1, max_grad_norm / (||grads|| + 1e-6)) (1 when max_grad_norm <= 0) and bc1 = 1 - beta1^t,
+ * bc2 = 1 - beta2^t computed by the caller from its own step count t.  beta1 / beta2 are doubles: 1 - beta is formed in
+ * double before the fp32 arithmetic, as torch forms it from its Python-float arguments.
+ *   items   DEVICE int64 [n_items][2] : arena offset, count (both multiples of 4; count <= DESTA_ADAMW_ITEM_FLOATS), every
+ *                                       item inside one tensor, ascending arena order (the update pass walks the table
+ *                                       BACKWARDS, from the end the norm pass has just streamed through the Infinity Cache)
+ *   item_wd DEVICE float [n_items]    : the item's tensor's weight decay (0 for the no-decay group)
+ *   numel   floats in the arena (multiple of 4); padding between tensors must hold zeros in every buffer and stays zero.
+ * `grads` is read only; exp_avg / exp_avg_sq are two arena-sized fp32 buffers.  Two launches, no float atomics (bitwise
+ * deterministic).  workspace (desta_adamw_workspace_floats floats): [0] = pre-clip global grad norm, [1] = clip coefficient
+ * after the call. */
+#define DESTA_ADAMW_ITEM_FLOATS 4096
+typedef struct desta_adamw_plan {
+    const int64_t* items; const float* item_wd; int n_items;
+    int64_t numel;
+} desta_adamw_plan;
+size_t desta_adamw_workspace_floats(const desta_adamw_plan* plan);
+int desta_clip_adamw_step(const desta_adamw_plan* plan, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                          float* workspace, float lr, double beta1, double beta2, float eps, float bc1, float bc2,
+                          float max_grad_norm, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Whisper log-mel front end: wave [batch, n_samples] f32 (row stride wave_stride) ->
@@ -442,7 +470,7 @@ int desta_rope_kv_append(void* qkv, int64_t ld, int rows, int seq, int n_q_heads
  * For hosts without torch.distributed (the Python host layer issues the same collective through torch's RCCL binding):
  *   rank 0: desta_comm_get_unique_id(&id); hand the 128 bytes to every rank (any channel);
  *   every rank (its device current): desta_comm_create(&comm, world, rank, &id);
- *   every step: desta_allreduce_grads(comm, arena_grads, n, stream) between backward and desta_clip_adafactor_step;
+ *   every step: desta_allreduce_grads(comm, arena_grads, n, stream) between backward and desta_clip_adafactor_step (or desta_clip_adamw_step);
  *   desta_comm_destroy(comm).
  * RCCL is loaded on first use (dlopen): the other entry points need no RCCL on the box.  One process per GPU. */
 typedef struct { char internal[128]; } desta_comm_unique_id;        /* = ncclUniqueId */
