@@ -54,7 +54,8 @@ struct Tab {
     int NC;
 };
 
-// workspace carve (floats): scalars[8] | unit_sumsq[U] | vec_sumsq[V] | chunk_usq[NC] | rowsum[SR] | rfac[SR] | cfac[SC] | colpart[...]
+// workspace carve (floats): scalars[8] | unit_sumsq[U] | vec_sumsq[V] | chunk_usq[max(NC, U)] | rowsum[S] | rfac[S] | cfac[S] | colpart[...]
+// (S = state_floats: rowsum / rfac / cfac are indexed by state offsets)
 // scalars: [0] global grad norm  [1] clip coefficient  [2..7] unused
 struct Ws {
     float* scalars; float* unit_sumsq; float* vec_sumsq; float* chunk_usq;
@@ -375,20 +376,9 @@ __global__ __launch_bounds__(256, 3) void af_apply(Tab tb, Ws ws, const float* _
     }
 }
 
-// sum u^2 of a whole tensor from its unit sums, in place: unit_usq[first unit] <- total (fixed order: thread-strided partials, then
-// the block tree).  One block per tensor (`t0 + blockIdx.x`).  [Rounds 1-3 summed the units serially in EVERY block of the apply
-// kernel: quadratic in the unit count, 2.3 s for a [4096, 4096, 5] Conv1d weight = 262 144 units.]
-__global__ __launch_bounds__(256) void k34_totals(Tab tb, int t0, float* __restrict__ unit_usq) {
-    __shared__ float red[4];
-    const long* tt = tb.ten + (long)(t0 + blockIdx.x) * 8;
-    const int unit0 = (int)tt[6], nun = (int)tt[7];
-    float s = 0.f;
-    for (int k = threadIdx.x; k < nun; k += 256) s += unit_usq[unit0 + k];
-    s = block_sum<256>(s, red);
-    __syncthreads();
-    if (threadIdx.x == 0) unit_usq[unit0] = s;
-}
-
+// sum u^2 of a whole ragged tensor from its unit sums, in place: unit_usq[unit0] <- total (fixed order: thread-strided partials,
+// then the block tree).  One block.  [Rounds 1-3 summed the units serially in EVERY block of the apply kernel: quadratic in the
+// unit count, 2.3 s for a [4096, 4096, 5] Conv1d weight = 262 144 units.]
 __global__ __launch_bounds__(256) void k34_totals_range(int unit0, int nun, float* __restrict__ unit_usq) {
     __shared__ float red[4];
     float s = 0.f;
@@ -415,7 +405,7 @@ __global__ __launch_bounds__(256) void k34_update(Tab tb, Ws ws, const float* __
     const bool vec4 = (Cn % 4 == 0);
     float scale = 0.f, decay = 1.f;
     if (APPLY) {
-        const float s = unit_usq[(int)tt[6]];                             // the tensor's total (k34_totals)
+        const float s = unit_usq[(int)tt[6]];                             // the tensor's total (k34_totals_range)
         const float rms = sqrtf(s / ((float)nb * (float)R * (float)Cn));
         scale = lr / fmaxf(1.0f, rms / clip_thr);
         decay = 1.0f - tb.ten_wd[t] * lr;
@@ -489,15 +479,11 @@ __global__ __launch_bounds__(256) void v2_update(Tab tb, Ws ws, const float* __r
 
 }  // namespace
 
-// floats: scalars | unit_sumsq[U] | vec_sumsq[V] | chunk_usq[NC] (>= U: the two-launch path keeps unit sums there) | rowsum | rfac | cfac |
-// colpart
-extern "C" size_t desta_adafactor_workspace_floats(int U, int V, int64_t sum_rows, int64_t sum_cols, int64_t colpart_floats) {
-    return (size_t)(8 + 2 * (size_t)U + (size_t)V + 2 * (size_t)sum_rows + (size_t)sum_cols + (size_t)colpart_floats + 64);
-}
-extern "C" size_t desta_adafactor_workspace_floats_v3(const desta_opt_plan* pl, int64_t colpart_floats) {
+// floats: the carve above (chunk_usq >= U: the ragged tensors keep their unit sums there), each of rowsum / cfac / colpart
+// 16-B aligned, + 64 floats of slack
+extern "C" size_t desta_adafactor_workspace_floats(const desta_opt_plan* pl) {
     const size_t nc = (size_t)(pl->n_chunks > pl->n_units ? pl->n_chunks : pl->n_units);
-    return 8 + (size_t)pl->n_units + (size_t)pl->n_vec + nc + 2 * (size_t)pl->sum_rows + (size_t)pl->sum_cols +
-           (size_t)colpart_floats + 64;
+    return 8 + (size_t)pl->n_units + (size_t)pl->n_vec + nc + 3 * (size_t)pl->state_floats + (size_t)pl->colpart_floats + 64;
 }
 
 extern "C" int desta_clip_adafactor_step(const desta_opt_plan* pl, float* params, const float* grads, float* state,
@@ -523,10 +509,10 @@ extern "C" int desta_clip_adafactor_step(const desta_opt_plan* pl, float* params
     ws.vec_sumsq = w; w += tb.V;
     ws.chunk_usq = w; w += nc;
     w += (4 - ((w - workspace) & 3)) & 3;
-    ws.rowsum = w; w += pl->sum_rows;
-    ws.rfac = w; w += pl->sum_rows;
+    ws.rowsum = w; w += pl->state_floats;
+    ws.rfac = w; w += pl->state_floats;
     w += (4 - ((w - workspace) & 3)) & 3;
-    ws.cfac = w; w += pl->sum_cols;
+    ws.cfac = w; w += pl->state_floats;
     w += (4 - ((w - workspace) & 3)) & 3;
     ws.colpart = w;
     hipStream_t st = (hipStream_t)stream;
@@ -542,9 +528,7 @@ extern "C" int desta_clip_adafactor_step(const desta_opt_plan* pl, float* params
         hipLaunchKernelGGL(k34_totals_range, dim3(1), dim3(256), 0, st, u0, n, ws.chunk_usq);
         hipLaunchKernelGGL(k34_update<true>, dim3(n), dim3(256), 0, st, tb, ws, grads, params, lr, clip_threshold, ws.chunk_usq, u0);
     }
-    if (pl->n_ragged > 0 && tb.NC == 0) {
-        if (tb.V > 0) hipLaunchKernelGGL(v2_update, dim3(tb.V), dim3(256), 0, st, tb, ws, grads, params, state, beta2t, eps1, lr, clip_threshold);
-    } else if (pl->cols_multiple_of_4) {
+    if (tb.NC > 0) {
         DESTA_CHECK_ARG(pl->group_bounds && pl->n_groups > 0 && pl->group_bounds[0] == 0 && pl->group_bounds[pl->n_groups] == tb.NC,
                         "adafactor: bad group table");
         for (int gi = 0; gi < pl->n_groups; ++gi) {
@@ -558,12 +542,8 @@ extern "C" int desta_clip_adafactor_step(const desta_opt_plan* pl, float* params
             hipLaunchKernelGGL(af_apply, dim3(n + n1 + nv), dim3(256), 0, st, tb, ws, grads, params, state, beta2t, eps1, lr, clip_threshold,
                                c0, n, c1, n1);
         }
-    } else {
-        DESTA_CHECK_ARG(pl->n_ragged == 0, "adafactor: a ragged-tensor table needs cols_multiple_of_4 = 1 for the tensors with chunks");
-        hipLaunchKernelGGL(k34_update<false>, dim3(tb.U), dim3(256), 0, st, tb, ws, grads, params, lr, clip_threshold, ws.chunk_usq, 0);
-        hipLaunchKernelGGL(k34_totals, dim3(tb.T), dim3(256), 0, st, tb, 0, ws.chunk_usq);
-        hipLaunchKernelGGL(k34_update<true>, dim3(tb.U), dim3(256), 0, st, tb, ws, grads, params, lr, clip_threshold, ws.chunk_usq, 0);
-        if (tb.V > 0) hipLaunchKernelGGL(v2_update, dim3(tb.V), dim3(256), 0, st, tb, ws, grads, params, state, beta2t, eps1, lr, clip_threshold);
+    } else if (tb.V > 0) {                          // every factored tensor is ragged: the 1-D tensors on their own launch
+        hipLaunchKernelGGL(v2_update, dim3(tb.V), dim3(256), 0, st, tb, ws, grads, params, state, beta2t, eps1, lr, clip_threshold);
     }
     DESTA_CHECK_LAUNCH("clip_adafactor_step");
     return DESTA_OK;

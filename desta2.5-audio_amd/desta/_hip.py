@@ -40,7 +40,7 @@ class GemmDesc(C.Structure):
 
 lib.desta_abi_version.restype = i32
 lib.desta_last_error.restype = C.c_char_p
-ABI_VERSION = 7
+ABI_VERSION = 8
 if lib.desta_abi_version() != ABI_VERSION:
     raise ImportError(f"libdesta_hip.so has ABI version {lib.desta_abi_version()}, this binding needs {ABI_VERSION}: "
                       "rebuild with `python desta2.5-audio_amd/build.py`")
@@ -226,16 +226,14 @@ class OptPlan(C.Structure):
     _fields_ = [("tensors", vp), ("tensor_wd", vp), ("n_tensors", i32),
                 ("units", vp), ("unit_col_off", vp), ("n_units", i32),
                 ("vecs", vp), ("vec_wd", vp), ("n_vec", i32),
-                ("sum_rows", i64), ("sum_cols", i64), ("max_batch", i32), ("max_cols", i32),
-                ("chunks", vp), ("ten_chunks", vp), ("n_chunks", i32), ("max_chunks_per_tensor", i32),
-                ("fin", vp), ("n_fin", i32), ("colpart_floats", i64), ("cols_multiple_of_4", i32),
+                ("state_floats", i64), ("max_cols", i32),
+                ("chunks", vp), ("ten_chunks", vp), ("n_chunks", i32),
+                ("fin", vp), ("n_fin", i32), ("colpart_floats", i64),
                 ("group_bounds", vp), ("n_groups", i32), ("ragged_units", vp), ("n_ragged", i32)]
 
 
 lib.desta_adafactor_workspace_floats.restype = C.c_size_t
-lib.desta_adafactor_workspace_floats.argtypes = [i32, i32, i64, i64, i64]
-lib.desta_adafactor_workspace_floats_v3.restype = C.c_size_t
-lib.desta_adafactor_workspace_floats_v3.argtypes = [C.POINTER(OptPlan), i64]
+lib.desta_adafactor_workspace_floats.argtypes = [C.POINTER(OptPlan)]
 _adafactor = _sig("desta_clip_adafactor_step", C.POINTER(OptPlan), vp, vp, vp, vp, f32, f32, f32, f32, f32, vp)
 
 

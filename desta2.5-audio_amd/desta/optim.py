@@ -9,7 +9,6 @@ from __future__ import annotations
 
 import ctypes
 import math
-from collections import OrderedDict
 from typing import Dict, List, Sequence, Tuple
 
 import torch
@@ -78,186 +77,6 @@ def linear_warmup_lr(step: int, base_lr: float, warmup: int, total: int) -> floa
     return base_lr * max(0.0, (total - step) / max(1, total - warmup))
 
 
-class FusedAdafactor:
-    def __init__(self, arena: ParamArena, weight_decay: float = 0.01, eps1: float = 1e-30,
-                 clip_threshold: float = 1.0, decay_rate: float = -0.8, max_grad_norm: float = 1.0,
-                 decay: Sequence[bool] = None):
-        self.arena = arena
-        self.eps1, self.clip_threshold, self.decay_rate = eps1, clip_threshold, decay_rate
-        self.max_grad_norm = max_grad_norm
-        self.step_count = 0
-        dev = arena.params.device
-        decay = decay_mask(arena.names) if decay is None else list(decay)
-        tensors, twd, units, ucol, vecs, vwd = [], [], [], [], [], []
-        self.state_slices: "OrderedDict[str, dict]" = OrderedDict()
-        st_off, col_ws_off, sum_rows, sum_cols, max_batch, max_cols = 0, 0, 0, 0, 1, 1
-        for name, dk in zip(arena.names, decay):
-            shape = arena.shapes[name]
-            wd = weight_decay if dk else 0.0
-            if len(shape) >= 2:
-                R, Cn = shape[-2], shape[-1]
-                nb = int(math.prod(shape[:-2]))
-                row_off = st_off
-                st_off += _al(nb * R, 4)
-                col_off = st_off
-                st_off += _al(nb * Cn, 4)
-                # rows per statistics unit: 64; a tensor with ragged rows (cols % 4 != 0, in practice a Conv1d weight [out, in, k]: `in` rows of
-                # k columns per batch item) takes up to 32 K elements per unit instead — 64 x 5 elements per block would mean 262 144 blocks
-                # for ORCA's [4096, 4096, 5] local_conv.weight
-                ur = UNIT_ROWS if Cn % 4 == 0 else max(UNIT_ROWS, min(R, 32768 // Cn))
-                upb = (R + ur - 1) // ur
-                unit0 = len(units)
-                for b in range(nb):
-                    for k in range(upb):
-                        r0 = k * ur
-                        units.append([len(tensors), b, r0, min(ur, R - r0)])
-                        ucol.append(col_ws_off)
-                        col_ws_off += _al(Cn, 4)
-                tensors.append([arena.offsets[name], nb, R, Cn, row_off, col_off, unit0, nb * upb])
-                twd.append(wd)
-                self.state_slices[name] = {"row": (row_off, shape[:-1]), "col": (col_off, shape[:-2] + shape[-1:])}
-                sum_rows = max(sum_rows, row_off + nb * R)
-                sum_cols = max(sum_cols, col_off + nb * Cn)
-                max_batch, max_cols = max(max_batch, nb), max(max_cols, Cn)
-            else:
-                n = int(math.prod(shape))
-                vecs.append([arena.offsets[name], n, st_off])
-                vwd.append(wd)
-                self.state_slices[name] = {"sq": (st_off, shape)}
-                st_off += _al(n, 4)
-        # the kernels index rowsum/rfac/cfac workspaces with the STATE offsets, so size them by st_off
-        self.state = torch.zeros(max(st_off, 4), dtype=torch.float32, device=dev)
-        i64, i32, f32 = torch.int64, torch.int32, torch.float32
-        self._tensors = torch.tensor(tensors or [[0] * 8], dtype=i64, device=dev)
-        self._twd = torch.tensor(twd or [0.0], dtype=f32, device=dev)
-        self._units = torch.tensor(units or [[0] * 4], dtype=i32, device=dev)
-        self._ucol = torch.tensor(ucol or [0], dtype=i64, device=dev)
-        self._vecs = torch.tensor(vecs or [[0] * 3], dtype=i64, device=dev)
-        self._vwd = torch.tensor(vwd or [0.0], dtype=f32, device=dev)
-        pl = _hip.OptPlan()
-        pl.tensors, pl.tensor_wd, pl.n_tensors = self._tensors.data_ptr(), self._twd.data_ptr(), len(tensors)
-        pl.units, pl.unit_col_off, pl.n_units = self._units.data_ptr(), self._ucol.data_ptr(), len(units)
-        pl.vecs, pl.vec_wd, pl.n_vec = self._vecs.data_ptr(), self._vwd.data_ptr(), len(vecs)
-        pl.sum_rows, pl.sum_cols = st_off, st_off
-        pl.max_batch, pl.max_cols = max_batch, max_cols
-        # work items of the update kernels: <= CHUNK contiguous elements of one [rows, cols] matrix; tensors in DESCENDING
-        # arena order (the update pass starts where the statistics pass ended: that tail is still in the Infinity Cache),
-        # the chunks of one tensor contiguous
-        # Tensors with ragged rows (cols % 4 != 0: the ORCA Conv1d weight [h, h, 5]) get no chunks: the unit-based kernels update them
-        # over their own unit range (`ragged_units`, ABI 7)
-        chunks, ten_chunks, fin = [], [[0, 0] for _ in tensors], []
-        ragged = [ti for ti, t in enumerate(tensors) if t[3] % 4 != 0]
-        for ti in reversed(range(len(tensors))):
-            _, nb, R, Cn = tensors[ti][:4]
-            if ti in ragged:
-                continue
-            ten_chunks[ti][0] = len(chunks)
-            for b in range(nb):
-                for e0 in range(0, R * Cn, CHUNK):
-                    chunks.append([ti, b, e0, min(CHUNK, R * Cn - e0)])
-            ten_chunks[ti][1] = len(chunks) - ten_chunks[ti][0]
-        for ti, (_, nb, R, Cn, *_rest) in enumerate(tensors):
-            for b in range(nb):
-                fin += [[ti, b, part] for part in range(1 + (Cn + 255) // 256)]
-        self._chunks = torch.tensor(chunks or [[0] * 4], dtype=i32, device=dev)
-        self._ten_chunks = torch.tensor(ten_chunks or [[0, 0]], dtype=i32, device=dev)
-        self._fin = torch.tensor(fin or [[0] * 3], dtype=i32, device=dev)
-        pl.chunks, pl.ten_chunks, pl.n_chunks = self._chunks.data_ptr(), self._ten_chunks.data_ptr(), len(chunks)
-        pl.max_chunks_per_tensor = max([c[1] for c in ten_chunks] or [0])
-        pl.fin, pl.n_fin, pl.colpart_floats = self._fin.data_ptr(), len(fin), col_ws_off
-        pl.cols_multiple_of_4 = 1
-        rag = [v for ti in ragged for v in (tensors[ti][6], tensors[ti][7])]
-        self._ragged = (ctypes.c_int32 * max(len(rag), 1))(*rag)                # HOST array, kept alive with the plan
-        pl.ragged_units, pl.n_ragged = ctypes.cast(self._ragged, ctypes.c_void_p), len(ragged)
-        # launch groups: cut the chunk list at tensor boundaries (a tensor's rms needs all of its chunk sums before its apply)
-        bounds, acc = [0], 0
-        for ti in reversed(range(len(tensors))):
-            if ti in ragged:
-                continue
-            n = tensors[ti][1] * tensors[ti][2] * tensors[ti][3]
-            if acc and acc + n > GROUP_FLOATS:
-                bounds.append(ten_chunks[ti][0])
-                acc = 0
-            acc += n
-        bounds.append(len(chunks))
-        self._group_bounds = (ctypes.c_int32 * len(bounds))(*bounds)            # HOST array, kept alive with the plan
-        pl.group_bounds, pl.n_groups = ctypes.cast(self._group_bounds, ctypes.c_void_p), len(bounds) - 1
-        self.plan = pl
-        nws = _hip.lib.desta_adafactor_workspace_floats_v3(ctypes.byref(pl), col_ws_off)
-        self.workspace = torch.zeros(nws, dtype=torch.float32, device=dev)
-
-    def step(self, lr: float) -> None:
-        """clip_grad_norm_(max_grad_norm) + Adafactor update, in place on the arena."""
-        self.step_count += 1
-        beta2t = 1.0 - math.pow(self.step_count, self.decay_rate)
-        _hip.clip_adafactor_step(self.plan, self.arena.params, self.arena.grads, self.state, self.workspace,
-                                 lr, beta2t, self.eps1, self.clip_threshold, self.max_grad_norm)
-
-    def grad_norm(self) -> torch.Tensor:
-        """Pre-clip global gradient norm of the last step (device scalar, no sync)."""
-        return self.workspace[0]
-
-    # -- wire format of `transformers.optimization.Adafactor.state_dict()` as HF Trainer writes it to
-    #    checkpoint-<step>/optimizer.pt: two param groups (decay first, TF:trainer.py:1181-1195), parameters
-    #    numbered in the reference's named_parameters() order inside each group
-    def hf_state_dict(self, ref_names: Sequence[str], lr: float, weight_decay: float = 0.01) -> dict:
-        dm = dict(zip(ref_names, decay_mask(ref_names)))
-        order = [n for n in ref_names if dm[n]] + [n for n in ref_names if not dm[n]]
-        n_decay = sum(dm.values())
-        state = {}
-        for idx, name in enumerate(order):
-            sl, p = self.state_slices[name], self.arena.param(name)
-            ent = {"step": self.step_count, "RMS": (p.norm(2) / math.sqrt(p.numel())).cpu()}
-            for key, hf in (("row", "exp_avg_sq_row"), ("col", "exp_avg_sq_col"), ("sq", "exp_avg_sq")):
-                if key in sl:
-                    off, shape = sl[key]
-                    ent[hf] = self.state[off:off + int(math.prod(shape))].view(tuple(shape)).detach().cpu().clone()
-            state[idx] = ent
-        common = {"lr": lr, "eps": (self.eps1, 1e-3), "clip_threshold": self.clip_threshold, "decay_rate": self.decay_rate,
-                  "beta1": None, "scale_parameter": False, "relative_step": False, "warmup_init": False}
-        groups = [dict(common, weight_decay=weight_decay, params=list(range(n_decay))),
-                  dict(common, weight_decay=0.0, params=list(range(n_decay, len(order))))]
-        return {"state": state if self.step_count > 0 else {}, "param_groups": groups}
-
-    def load_hf_state_dict(self, sd: dict, ref_names: Sequence[str]) -> None:
-        _require_saved_optimizer(sd, "adafactor")
-        dm = dict(zip(ref_names, decay_mask(ref_names)))
-        order = [n for n in ref_names if dm[n]] + [n for n in ref_names if not dm[n]]
-        self.step_count = 0
-        for idx, name in enumerate(order):
-            ent = sd["state"].get(idx)
-            if ent is None:
-                continue
-            self.step_count = int(ent["step"])
-            for key, hf in (("row", "exp_avg_sq_row"), ("col", "exp_avg_sq_col"), ("sq", "exp_avg_sq")):
-                if key in self.state_slices[name]:
-                    off, shape = self.state_slices[name][key]
-                    self.state[off:off + int(math.prod(shape))].copy_(ent[hf].reshape(-1))
-
-    # -- HF `optimizer.pt`-shaped state (exp_avg_sq_row / exp_avg_sq_col / exp_avg_sq, step)
-    def state_dict(self) -> dict:
-        st = {}
-        for i, name in enumerate(self.arena.names):
-            sl, ent = self.state_slices[name], {"step": self.step_count, "RMS": 0}
-            for key, hf in (("row", "exp_avg_sq_row"), ("col", "exp_avg_sq_col"), ("sq", "exp_avg_sq")):
-                if key in sl:
-                    off, shape = sl[key]
-                    ent[hf] = self.state[off:off + int(math.prod(shape))].view(tuple(shape)).clone()
-            st[i] = ent
-        return {"state": st, "names": list(self.arena.names), "step": self.step_count}
-
-    def load_state_dict(self, sd: dict) -> None:
-        _require_saved_optimizer(sd, "adafactor")
-        self.step_count = int(sd.get("step", 0))
-        for i, name in enumerate(self.arena.names):
-            ent = sd["state"][i]
-            sl = self.state_slices[name]
-            for key, hf in (("row", "exp_avg_sq_row"), ("col", "exp_avg_sq_col"), ("sq", "exp_avg_sq")):
-                if key in sl:
-                    off, shape = sl[key]
-                    self.state[off:off + int(math.prod(shape))].copy_(ent[hf].reshape(-1))
-
-
 def _hf_order(ref_names: Sequence[str]) -> Tuple[List[str], int]:
     """HF Trainer's two param groups (TF:trainer.py:1181-1195): decay first, each in named_parameters() order."""
     dm = dict(zip(ref_names, decay_mask(ref_names)))
@@ -290,10 +109,189 @@ def _require_saved_optimizer(sd: dict, expected: str) -> None:
                          f"a {names[got]} checkpoint cannot resume an {names[expected]} run (set `optim` to match the checkpoint)")
 
 
-class FusedAdamW:
+class _FusedOptimizer:
+    """The state-dict codec both fused optimizers share.  Each names its per-tensor state as slots (`slots[name]`: HF state key ->
+    view into its buffers) and supplies what differs: `tag`, `_buffers` (zeroed before an HF load), `_head` (the step in its
+    wire form, Adafactor's RMS) and `_hf_common` (the keys both param groups share, in wire order)."""
+
+    def grad_norm(self) -> torch.Tensor:
+        """Pre-clip global gradient norm of the last step (device scalar, no sync)."""
+        return self.workspace[0]
+
+    def _entry(self, name: str, hf: bool) -> dict:
+        ent = self._head(name, hf)
+        for key, v in self.slots[name].items():
+            ent[key] = v.detach().cpu().clone() if hf else v.clone()
+        return ent
+
+    def _load_entry(self, name: str, ent: dict) -> None:
+        for key, v in self.slots[name].items():
+            v.copy_(ent[key].reshape(v.shape))
+
+    # -- wire format of the reference optimizer's `state_dict()` as HF Trainer writes it to checkpoint-<step>/optimizer.pt: two
+    #    param groups (decay first), parameters numbered in the reference's named_parameters() order inside each group
+    def hf_state_dict(self, ref_names: Sequence[str], lr: float, weight_decay: float = 0.01) -> dict:
+        order, n_decay = _hf_order(ref_names)
+        state = {idx: self._entry(name, hf=True) for idx, name in enumerate(order)} if self.step_count > 0 else {}
+        common = self._hf_common(lr)
+        groups = [dict(common, weight_decay=weight_decay, params=list(range(n_decay))),
+                  dict(common, weight_decay=0.0, params=list(range(n_decay, len(order))))]
+        return {"state": state, "param_groups": groups}
+
+    def load_hf_state_dict(self, sd: dict, ref_names: Sequence[str]) -> None:
+        """A parameter without an entry starts from zeros, as in HF."""
+        _require_saved_optimizer(sd, self.tag)
+        order, _ = _hf_order(ref_names)
+        self.step_count = 0
+        for b in self._buffers:
+            b.zero_()
+        for idx, name in enumerate(order):
+            ent = sd["state"].get(idx)
+            if ent is not None:
+                self.step_count = int(float(ent["step"]))
+                self._load_entry(name, ent)
+
+    # -- local form: per arena tensor, in arena order
+    def state_dict(self) -> dict:
+        st = {i: self._entry(name, hf=False) for i, name in enumerate(self.arena.names)}
+        return {"optimizer": self.tag, "state": st, "names": list(self.arena.names), "step": self.step_count}
+
+    def load_state_dict(self, sd: dict) -> None:
+        _require_saved_optimizer(sd, self.tag)
+        self.step_count = int(sd.get("step", 0))
+        for i, name in enumerate(self.arena.names):
+            self._load_entry(name, sd["state"][i])
+
+
+class FusedAdafactor(_FusedOptimizer):
+    tag = "adafactor"
+
+    def __init__(self, arena: ParamArena, weight_decay: float = 0.01, eps1: float = 1e-30,
+                 clip_threshold: float = 1.0, decay_rate: float = -0.8, max_grad_norm: float = 1.0,
+                 decay: Sequence[bool] = None):
+        self.arena = arena
+        self.eps1, self.clip_threshold, self.decay_rate = eps1, clip_threshold, decay_rate
+        self.max_grad_norm = max_grad_norm
+        self.step_count = 0
+        dev = arena.params.device
+        decay = decay_mask(arena.names) if decay is None else list(decay)
+        tensors, twd, units, ucol, vecs, vwd = [], [], [], [], [], []
+        slot_offs = {}                  # name -> {HF state key: (state offset, shape)}
+        st_off, col_ws_off, max_cols = 0, 0, 1
+        for name, dk in zip(arena.names, decay):
+            shape = arena.shapes[name]
+            wd = weight_decay if dk else 0.0
+            if len(shape) >= 2:
+                R, Cn = shape[-2], shape[-1]
+                nb = int(math.prod(shape[:-2]))
+                row_off = st_off
+                st_off += _al(nb * R, 4)
+                col_off = st_off
+                st_off += _al(nb * Cn, 4)
+                # rows per statistics unit: 64; a tensor with ragged rows (cols % 4 != 0, in practice a Conv1d weight [out, in, k]: `in` rows of
+                # k columns per batch item) takes up to 32 K elements per unit instead — 64 x 5 elements per block would mean 262 144 blocks
+                # for ORCA's [4096, 4096, 5] local_conv.weight
+                ur = UNIT_ROWS if Cn % 4 == 0 else max(UNIT_ROWS, min(R, 32768 // Cn))
+                upb = (R + ur - 1) // ur
+                unit0 = len(units)
+                for b in range(nb):
+                    for k in range(upb):
+                        r0 = k * ur
+                        units.append([len(tensors), b, r0, min(ur, R - r0)])
+                        ucol.append(col_ws_off)
+                        col_ws_off += _al(Cn, 4)
+                tensors.append([arena.offsets[name], nb, R, Cn, row_off, col_off, unit0, nb * upb])
+                twd.append(wd)
+                slot_offs[name] = {"exp_avg_sq_row": (row_off, shape[:-1]), "exp_avg_sq_col": (col_off, shape[:-2] + shape[-1:])}
+                max_cols = max(max_cols, Cn)
+            else:
+                n = int(math.prod(shape))
+                vecs.append([arena.offsets[name], n, st_off])
+                vwd.append(wd)
+                slot_offs[name] = {"exp_avg_sq": (st_off, shape)}
+                st_off += _al(n, 4)
+        # the kernels index rowsum/rfac/cfac workspaces with the STATE offsets, so size them by st_off
+        self.state = torch.zeros(max(st_off, 4), dtype=torch.float32, device=dev)
+        self.slots = {name: {k: self.state[o:o + math.prod(shp)].view(shp) for k, (o, shp) in sl.items()} for name, sl in slot_offs.items()}
+        self._buffers = (self.state,)
+        i64, i32, f32 = torch.int64, torch.int32, torch.float32
+        self._tensors = torch.tensor(tensors or [[0] * 8], dtype=i64, device=dev)
+        self._twd = torch.tensor(twd or [0.0], dtype=f32, device=dev)
+        self._units = torch.tensor(units or [[0] * 4], dtype=i32, device=dev)
+        self._ucol = torch.tensor(ucol or [0], dtype=i64, device=dev)
+        self._vecs = torch.tensor(vecs or [[0] * 3], dtype=i64, device=dev)
+        self._vwd = torch.tensor(vwd or [0.0], dtype=f32, device=dev)
+        pl = _hip.OptPlan()
+        pl.tensors, pl.tensor_wd, pl.n_tensors = self._tensors.data_ptr(), self._twd.data_ptr(), len(tensors)
+        pl.units, pl.unit_col_off, pl.n_units = self._units.data_ptr(), self._ucol.data_ptr(), len(units)
+        pl.vecs, pl.vec_wd, pl.n_vec = self._vecs.data_ptr(), self._vwd.data_ptr(), len(vecs)
+        pl.state_floats, pl.max_cols = st_off, max_cols
+        # work items of the update kernels: <= CHUNK contiguous elements of one [rows, cols] matrix; tensors in DESCENDING
+        # arena order (the update pass starts where the statistics pass ended: that tail is still in the Infinity Cache),
+        # the chunks of one tensor contiguous
+        # Tensors with ragged rows (cols % 4 != 0: the ORCA Conv1d weight [h, h, 5]) get no chunks: the unit-based kernels update them
+        # over their own unit range (`ragged_units`, ABI 7)
+        chunks, ten_chunks, fin = [], [[0, 0] for _ in tensors], []
+        ragged = [ti for ti, t in enumerate(tensors) if t[3] % 4 != 0]
+        for ti in reversed(range(len(tensors))):
+            _, nb, R, Cn = tensors[ti][:4]
+            if ti in ragged:
+                continue
+            ten_chunks[ti][0] = len(chunks)
+            for b in range(nb):
+                for e0 in range(0, R * Cn, CHUNK):
+                    chunks.append([ti, b, e0, min(CHUNK, R * Cn - e0)])
+            ten_chunks[ti][1] = len(chunks) - ten_chunks[ti][0]
+        for ti, (_, nb, R, Cn, *_rest) in enumerate(tensors):
+            for b in range(nb):
+                fin += [[ti, b, part] for part in range(1 + (Cn + 255) // 256)]
+        self._chunks = torch.tensor(chunks or [[0] * 4], dtype=i32, device=dev)
+        self._ten_chunks = torch.tensor(ten_chunks or [[0, 0]], dtype=i32, device=dev)
+        self._fin = torch.tensor(fin or [[0] * 3], dtype=i32, device=dev)
+        pl.chunks, pl.ten_chunks, pl.n_chunks = self._chunks.data_ptr(), self._ten_chunks.data_ptr(), len(chunks)
+        pl.max_chunks_per_tensor = max([c[1] for c in ten_chunks] or [0])      # host-side attribute, not a field of desta_opt_plan
+        pl.fin, pl.n_fin, pl.colpart_floats = self._fin.data_ptr(), len(fin), col_ws_off
+        rag = [v for ti in ragged for v in (tensors[ti][6], tensors[ti][7])]
+        self._ragged = (ctypes.c_int32 * max(len(rag), 1))(*rag)                # HOST array, kept alive with the plan
+        pl.ragged_units, pl.n_ragged = ctypes.cast(self._ragged, ctypes.c_void_p), len(ragged)
+        # launch groups: cut the chunk list at tensor boundaries (a tensor's rms needs all of its chunk sums before its apply)
+        bounds, acc = [0], 0
+        for ti in reversed(range(len(tensors))):
+            if ti in ragged:
+                continue
+            n = tensors[ti][1] * tensors[ti][2] * tensors[ti][3]
+            if acc and acc + n > GROUP_FLOATS:
+                bounds.append(ten_chunks[ti][0])
+                acc = 0
+            acc += n
+        bounds.append(len(chunks))
+        self._group_bounds = (ctypes.c_int32 * len(bounds))(*bounds)            # HOST array, kept alive with the plan
+        pl.group_bounds, pl.n_groups = ctypes.cast(self._group_bounds, ctypes.c_void_p), len(bounds) - 1
+        self.plan = pl
+        self.workspace = torch.zeros(_hip.lib.desta_adafactor_workspace_floats(ctypes.byref(pl)), dtype=torch.float32, device=dev)
+
+    def step(self, lr: float) -> None:
+        """clip_grad_norm_(max_grad_norm) + Adafactor update, in place on the arena."""
+        self.step_count += 1
+        beta2t = 1.0 - math.pow(self.step_count, self.decay_rate)
+        _hip.clip_adafactor_step(self.plan, self.arena.params, self.arena.grads, self.state, self.workspace,
+                                 lr, beta2t, self.eps1, self.clip_threshold, self.max_grad_norm)
+
+    # -- `transformers.optimization.Adafactor.state_dict()`: an int step, the parameter's RMS, exp_avg_sq_row / exp_avg_sq_col / exp_avg_sq
+    def _head(self, name: str, hf: bool) -> dict:
+        p = self.arena.param(name)
+        return {"step": self.step_count, "RMS": (p.norm(2) / math.sqrt(p.numel())).cpu() if hf else 0}
+
+    def _hf_common(self, lr: float) -> dict:
+        return {"lr": lr, "eps": (self.eps1, 1e-3), "clip_threshold": self.clip_threshold, "decay_rate": self.decay_rate,
+                "beta1": None, "scale_parameter": False, "relative_step": False, "warmup_init": False}
+
+
+class FusedAdamW(_FusedOptimizer):
     """clip_grad_norm_(max_grad_norm) + torch.optim.AdamW over the arena in two launches (csrc/adamw.hip): HF Trainer with
     optim="adamw_torch" / "adamw_torch_fused" (TF:trainer_optimizer.py:201-208).  State: exp_avg / exp_avg_sq, two fp32
     buffers the size of the arena; the step count lives on the host (bias corrections in double, as torch forms them)."""
+    tag = "adamw"
 
     def __init__(self, arena: ParamArena, weight_decay: float = 0.0, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-8, max_grad_norm: float = 1.0, decay: Sequence[bool] = None, torch_fused: bool = False):
@@ -319,6 +317,8 @@ class FusedAdamW:
         self.plan = pl
         self.exp_avg = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
+        self.slots = {n: {"exp_avg": arena._view(self.exp_avg, n), "exp_avg_sq": arena._view(self.exp_avg_sq, n)} for n in arena.names}
+        self._buffers = (self.exp_avg, self.exp_avg_sq)
         self.workspace = torch.zeros(_hip.lib.desta_adamw_workspace_floats(ctypes.byref(pl)), dtype=torch.float32, device=dev)
 
     def step(self, lr: float) -> None:
@@ -329,53 +329,12 @@ class FusedAdamW:
         _hip.clip_adamw_step(self.plan, self.arena.params, self.arena.grads, self.exp_avg, self.exp_avg_sq, self.workspace,
                              lr, self.beta1, self.beta2, self.eps, bc1, bc2, self.max_grad_norm)
 
-    def grad_norm(self) -> torch.Tensor:
-        """Pre-clip global gradient norm of the last step (device scalar, no sync)."""
-        return self.workspace[0]
+    # -- `torch.optim.AdamW.state_dict()` (torch 2.10): the step as a float32 scalar tensor, exp_avg / exp_avg_sq
+    def _head(self, name: str, hf: bool) -> dict:
+        return {"step": torch.tensor(float(self.step_count), dtype=torch.float32) if hf else self.step_count}
 
-    def _moment(self, buf: torch.Tensor, name: str) -> torch.Tensor:
-        return self.arena._view(buf, name)
-
-    # -- wire format of `torch.optim.AdamW.state_dict()` (torch 2.10) as HF Trainer writes it to checkpoint-<step>/optimizer.pt
-    def hf_state_dict(self, ref_names: Sequence[str], lr: float, weight_decay: float = 0.01) -> dict:
-        order, n_decay = _hf_order(ref_names)
-        state = {}
-        if self.step_count > 0:
-            for idx, name in enumerate(order):
-                state[idx] = {"step": torch.tensor(float(self.step_count), dtype=torch.float32),
-                              "exp_avg": self._moment(self.exp_avg, name).detach().cpu().clone(),
-                              "exp_avg_sq": self._moment(self.exp_avg_sq, name).detach().cpu().clone()}
-        common = {"lr": lr, "betas": (self.beta1, self.beta2), "eps": self.eps, "amsgrad": False, "maximize": False,
-                  "foreach": None, "capturable": False, "differentiable": False, "fused": True if self.torch_fused else None,
-                  "decoupled_weight_decay": True}
-        groups = [dict(weight_decay=weight_decay, **common, params=list(range(n_decay))),
-                  dict(weight_decay=0.0, **common, params=list(range(n_decay, len(order))))]
-        return {"state": state, "param_groups": groups}
-
-    def load_hf_state_dict(self, sd: dict, ref_names: Sequence[str]) -> None:
-        _require_saved_optimizer(sd, "adamw")
-        order, _ = _hf_order(ref_names)
-        self.step_count = 0
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
-        for idx, name in enumerate(order):
-            ent = sd["state"].get(idx)
-            if ent is None:
-                continue
-            self.step_count = int(float(ent["step"]))
-            self._moment(self.exp_avg, name).copy_(ent["exp_avg"].reshape(self.arena.shapes[name]))
-            self._moment(self.exp_avg_sq, name).copy_(ent["exp_avg_sq"].reshape(self.arena.shapes[name]))
-
-    # -- local form: per arena tensor, in arena order
-    def state_dict(self) -> dict:
-        st = {i: {"step": self.step_count, "exp_avg": self._moment(self.exp_avg, name).clone(),
-                  "exp_avg_sq": self._moment(self.exp_avg_sq, name).clone()} for i, name in enumerate(self.arena.names)}
-        return {"optimizer": "adamw", "state": st, "names": list(self.arena.names), "step": self.step_count}
-
-    def load_state_dict(self, sd: dict) -> None:
-        _require_saved_optimizer(sd, "adamw")
-        self.step_count = int(sd.get("step", 0))
-        for i, name in enumerate(self.arena.names):
-            ent = sd["state"][i]
-            self._moment(self.exp_avg, name).copy_(ent["exp_avg"].reshape(self.arena.shapes[name]))
-            self._moment(self.exp_avg_sq, name).copy_(ent["exp_avg_sq"].reshape(self.arena.shapes[name]))
+    def _hf_common(self, lr: float) -> dict:
+        # weight_decay leads, as in torch's groups; each group sets its own value
+        return {"weight_decay": None, "lr": lr, "betas": (self.beta1, self.beta2), "eps": self.eps, "amsgrad": False,
+                "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                "fused": True if self.torch_fused else None, "decoupled_weight_decay": True}

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DESTA_ABI_VERSION 7
+#define DESTA_ABI_VERSION 8
 
 int desta_abi_version(void);
 /* sizeof of the descriptor structs as this library was compiled (0 = desta_gemm_desc, 1 = desta_attn_desc,
@@ -145,35 +145,33 @@ int desta_gemm_set_option(int option, int value);
  *                                   tensor with ragged rows, ABI 7)
  *   unit_col_off int64 [n_units]  : offset of the unit's column partial sums in the workspace
  *   vecs     int64 [n_vec][3]     : arena offset, length, state offset
- * `state` holds exp_avg_sq_row / exp_avg_sq_col / exp_avg_sq.  workspace[0] = pre-clip global
- * grad norm, workspace[1] = clip coefficient after the call. */
+ * `state` (state_floats floats) holds exp_avg_sq_row / exp_avg_sq_col / exp_avg_sq.  workspace
+ * (desta_adafactor_workspace_floats floats): [0] = pre-clip global grad norm, [1] = clip coefficient
+ * after the call. */
 typedef struct desta_opt_plan {
     const int64_t* tensors; const float* tensor_wd; int n_tensors;
     const int32_t* units; const int64_t* unit_col_off; int n_units;
     const int64_t* vecs; const float* vec_wd; int n_vec;
-    int64_t sum_rows, sum_cols;      /* total factored row / column state entries */
-    int max_batch, max_cols;
+    int64_t state_floats;            /* length of `state`: the row / column factors of the workspace are indexed by state offsets */
+    int max_cols;
     /* ABI 3: work items of the update kernels and of the factor kernel.
      * chunks [n_chunks][4] = (tensor, batch index, first element inside the [rows, cols] matrix, count <= 16384), the chunks of
      * one tensor contiguous, tensors in DESCENDING arena order (the update passes walk the arena backwards, from the end the
      * statistics pass has just streamed through the Infinity Cache); ten_chunks [n_tensors][2] = (first chunk, chunk count);
      * fin [n_fin][3] = (tensor, batch index, part): part 0 = the row factors, k >= 1 = columns [256 (k-1), 256 k);
      * group_bounds: HOST array [n_groups + 1] of chunk indices cutting the chunk list at tensor boundaries into groups of
-     * <= 64 MB of gradients (the re-read of a group's gradients is then served by the Infinity Cache). */
-    const int32_t* chunks; const int32_t* ten_chunks; int n_chunks, max_chunks_per_tensor;
+     * <= 64 MB of gradients (the re-read of a group's gradients is then served by the Infinity Cache).  Every tensor with
+     * chunks has cols % 4 == 0 (16-B row accesses in the chunk kernels). */
+    const int32_t* chunks; const int32_t* ten_chunks; int n_chunks;
     const int32_t* fin; int n_fin;
-    int64_t colpart_floats;
-    int cols_multiple_of_4;          /* every factored tensor WITH CHUNKS has cols % 4 == 0 (16-B row accesses in the chunk kernels) */
+    int64_t colpart_floats;          /* column partial sums of all units (unit_col_off indexes into them) */
     const int32_t* group_bounds; int n_groups;
     /* ABI 7: factored tensors with ragged rows (cols % 4 != 0, e.g. a Conv1d weight [out, in, 5]) carry NO chunks
      * (ten_chunks = (0, 0)) and are updated by the unit-based kernels: ragged_units = HOST array [n_ragged][2] of
-     * (first unit, unit count), one entry per such tensor.  n_ragged == 0 with cols_multiple_of_4 == 0 is the ABI <= 6
-     * behaviour (EVERY tensor on the unit-based kernels). */
+     * (first unit, unit count), one entry per such tensor. */
     const int32_t* ragged_units; int n_ragged;
 } desta_opt_plan;
-size_t desta_adafactor_workspace_floats(int n_units, int n_vec, int64_t sum_rows, int64_t sum_cols,
-                                        int64_t colpart_floats);      /* ABI <= 2 layout, kept for old callers */
-size_t desta_adafactor_workspace_floats_v3(const desta_opt_plan* plan, int64_t colpart_floats);
+size_t desta_adafactor_workspace_floats(const desta_opt_plan* plan);
 int desta_clip_adafactor_step(const desta_opt_plan* plan, float* params, const float* grads, float* state,
                               float* workspace, float lr, float beta2t, float eps1, float clip_threshold,
                               float max_grad_norm, void* stream);

@@ -12,7 +12,7 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(desta_[a-z0-9_]+)\s*\(", txt)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_the_header_abi_version():
     import torch  # noqa: F401  (same load order as the product path)
     path = os.path.join(ROOT, "desta2.5-audio_amd", "desta", "lib", "libdesta_hip.so")
     if not os.path.exists(path):
@@ -27,7 +27,9 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/desta_hip.h but not exported"
     lib.desta_abi_version.restype = ctypes.c_int
-    assert lib.desta_abi_version() == 7
+    header = re.search(r"#define DESTA_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "desta_hip.h")).read())
+    from desta import _hip
+    assert lib.desta_abi_version() == int(header.group(1)) == _hip.ABI_VERSION == 8
 
 
 def test_host_side_table_helper_runs_without_gpu():

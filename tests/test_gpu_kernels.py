@@ -470,27 +470,48 @@ def test_adafactor_connector_shapes(hip):
     assert opt.plan.n_groups >= 1 and opt.plan.max_chunks_per_tensor == 320
 
 
-def test_adafactor_ragged_rows_take_the_unit_kernels(hip):
+def _assert_chunk_table(opt):
+    """The plan's chunk table: a factored tensor with cols % 4 == 0 has chunks (16-B row accesses in the chunk kernels), each
+    ragged one has none and a unit range of its own; the chunks of one tensor are contiguous, tensors in descending arena order."""
+    pl = opt.plan
+    tens, ten_chunks = opt._tensors.tolist()[:pl.n_tensors], opt._ten_chunks.tolist()[:pl.n_tensors]
+    chunks = opt._chunks.tolist()[:pl.n_chunks]
+    rag = list(opt._ragged)[:2 * pl.n_ragged]
+    assert [[t[6], t[7]] for t in tens if t[3] % 4] == [rag[i:i + 2] for i in range(0, len(rag), 2)]
+    for ti, (t, (c0, n)) in enumerate(zip(tens, ten_chunks)):
+        if t[3] % 4:
+            assert n == 0, ti
+        else:
+            assert n > 0 and all(c[0] == ti for c in chunks[c0:c0 + n]), ti
+    assert [c[0] for c in chunks] == sorted((c[0] for c in chunks), reverse=True)
+
+
+def test_adafactor_ragged_rows_carry_no_chunks_and_take_the_unit_kernels(hip):
     """cols % 4 != 0 (no 16-B row accesses): such tensors carry no chunks and are updated by the unit-based kernels over their own
     unit range (ABI 7: `ragged_units`), the others stay on the chunk kernels; same numbers.  Cases: a mix, a plan whose factored
     tensors are ALL ragged (no chunk launch at all, 1-D tensors on their own launch), and a Conv1d-like [out, in, 5] weight
     (ORCA's local_conv: batch = out, 5 columns, hundreds of units whose sums `k34_totals_range` adds up once per tensor)."""
     _, opt = _run_adafactor_case(hip, [(33, 7), (5, 3, 9), (11,), (40, 64)], steps=3, gscale=[0.5, 4.0])
-    assert opt.plan.cols_multiple_of_4 == 1 and opt.plan.n_ragged == 2 and opt.plan.n_chunks == 1
+    assert opt.plan.n_ragged == 2 and opt.plan.n_chunks == 1
+    _assert_chunk_table(opt)
     _, opt = _run_adafactor_case(hip, [(33, 7), (9,), (5, 3, 9)], steps=3, gscale=[0.5, 4.0])
     assert opt.plan.n_ragged == 2 and opt.plan.n_chunks == 0
+    _assert_chunk_table(opt)
     _, opt = _run_adafactor_case(hip, [(64, 4), (192, 130, 5), (192,), (256, 192)], steps=2, gscale=[0.05, 3.0])
     assert opt.plan.n_ragged == 1 and opt.plan.n_units == 1 + 192 + 4          # one unit per [130, 5] batch item of the ragged tensor
+    _assert_chunk_table(opt)
     # ragged AND wider than the one-thread-per-row form (<= 16 columns): the wave-per-row scalar form
     _, opt = _run_adafactor_case(hip, [(20, 30), (3, 70, 259), (5,), (8, 12)], steps=2, gscale=[0.05, 3.0])
     assert opt.plan.n_ragged == 2
+    _assert_chunk_table(opt)
 
 
-def test_adafactor_many_chunk_tensor_and_full_arena_order(hip):
+def test_adafactor_many_chunk_tensor_and_descending_chunk_order(hip):
     """A tensor of 321 chunks between small ones, several launch groups in the reverse arena order; 2 steps against the
     exact-reduction oracle."""
     _, opt = _run_adafactor_case(hip, [(8, 64), (4100, 1280), (1280,), (2, 16, 1280), (257, 516)], steps=2, gscale=[0.03, 2.0])
-    assert opt.plan.cols_multiple_of_4 == 1 and opt.plan.max_chunks_per_tensor == 321
+    assert opt.plan.max_chunks_per_tensor == 321
+    _assert_chunk_table(opt)
 
 
 def test_adafactor_is_deterministic(hip):
