@@ -60,7 +60,7 @@ __device__ __forceinline__ void rope4(const GemmArgs& p, int m, int n0, float (&
     }
 }
 
-// bias + GELU of 4 adjacent outputs destined for a bf16 store: packed polynomial form (common.h), or the A&S form (option 9 = 0)
+// GELU(erf) of 4 adjacent outputs destined for a bf16 store (A&S 7.1.26 form, common.h)
 __device__ __forceinline__ void gelu4_bf16(float (&v)[4]) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = gelu_erf_fast(v[e]);
@@ -683,6 +683,221 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_nt_ring_kernel(GemmArgs p) {
 //   slots so the count stays constant.
 constexpr int HT = 128 * BK * 2;                         // half-tile bytes (128 rows x 128 B)
 
+// The half-tile stream of ONE 256x256 tile (or K-slice): the staging sources of this thread and the issue / counted-wait helpers.
+// Shared by the one-tile-per-block kernel and the persistent kernel, which re-initialises it per work item.
+struct K256Stream {
+    const bf16_t* src[4][2];                              // [A0, A1, B0, B1][i]: this thread's two 16-B chunks of each half-tile kind
+    char* lds;
+    int kt0, nk, n_ht, wave;
+    bool tskip;
+    __device__ __forceinline__ void init(const GemmArgs& p, char* lds_, int tid, int wave_, const bf16_t* A, const bf16_t* B,
+                                         int brow, int bcol, int kt0_, int nk_, bool tskip_) {
+        lds = lds_; wave = wave_; kt0 = kt0_; nk = nk_; n_ht = 4 * nk_; tskip = tskip_;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int idx = i * 512 + tid;
+            const int r = idx >> 3, pc = idx & 7;
+            const int c = pc ^ (r & 7);
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2) {
+                const int arow = (r >> 6) * 128 + s2 * 64 + (r & 63);
+                const int bcolr = (r >> 5) * 64 + s2 * 32 + (r & 31);
+                src[s2][i] = A + (long)min(brow + arow, p.M - 1) * p.lda + c * 8;
+                src[2 + s2][i] = B + (long)min(bcol + bcolr, p.N - 1) * p.ldb + c * 8;
+            }
+        }
+    }
+    // issue half-tile number j of the stream
+    // tail_skip (2-phase schedule): half-tiles past the end of the stream are NOT issued — without it the stream re-loads the last K-tile
+    // into dead slots so that the counted vmcnt stays constant: 7 x 16 KiB of L2 -> LDS traffic per tile that nothing reads (2.7 % of
+    // a K = 4096 tile's operand traffic, 8.8 % at K = 1280) and a drain behind the last MFMA
+    __device__ __forceinline__ void stage(int j) {
+        if (tskip && j >= n_ht) return;                   // (wave-uniform)
+        const int t = j >> 2, q = j & 3;                  // q: 0 A0, 1 B0, 2 B1, 3 A1
+        const int kind = (q == 0) ? 0 : (q == 1) ? 2 : (q == 2) ? 3 : 1;
+        const long koff = (long)(kt0 + min(t, nk - 1)) * BK;
+        char* dst = lds + ((t & 1) * 4 + kind) * HT;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            glds16(src[kind][i] + koff, dst + (i * 512 + wave * 64) * 16);
+    }
+    __device__ __forceinline__ void stage_steady(int j) { // j < 4 nk: no end-of-stream test, no clamp
+        const int t = j >> 2, q = j & 3;
+        const int kind = (q == 0) ? 0 : (q == 1) ? 2 : (q == 2) ? 3 : 1;
+        const long koff = (long)(kt0 + t) * BK;
+        char* dst = lds + ((t & 1) * 4 + kind) * HT;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            glds16(src[kind][i] + koff, dst + (i * 512 + wave * 64) * 16);
+    }
+    // counted wait in front of a barrier: all but the 4 youngest half-tiles of the UNCAPPED stream must have landed; `issued` = stream
+    // position after this slot's stage() calls.  Steady state: 4 half-tiles x 2 ops = vmcnt(8); in the tail the stream is shorter by
+    // the overshoot, so fewer ops may stay outstanding (wave-uniform branch on a scalar)
+    __device__ __forceinline__ void wait_steady(int) { asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
+    __device__ __forceinline__ void tail_wait(int issued) {
+        const int ov = tskip ? issued - n_ht : 0;
+        if (ov <= 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (ov == 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else if (ov == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else if (ov == 3) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+};
+
+// The K loop of the staggered / lockstep TWO-phase schedule over a stream whose first 7 half-tiles were issued and waited for (the
+// caller's barrier).  STAGGER: waves 4-7 (the SIMD partners of waves 0-3) run half a phase behind, so on every SIMD one wave issues its
+// MFMAs while the other issues its LDS reads / LDS-DMA: group B enters the loop one barrier late and group A leaves it one barrier late;
+// both groups leave aligned.  Every slot ends with lgkmcnt(0) (its ds_reads have returned before any other wave may re-stage the slot)
+// and the counted vmcnt (the shares this wave issued have landed).  at_tail() runs once, in front of the last two K-tiles.
+template <bool STAGGER, class AtTail>
+__device__ __forceinline__ void k256_loop_2phase(K256Stream& st, const int (&offA)[4], const int (&offB)[2], f32x4 (&acc)[8][4],
+                                                 AtTail&& at_tail) {
+    const int nk = st.nk, wave = st.wave;
+    const char* lds = st.lds;
+    bf16x8 a[4][2], b0[2][2], b1[2][2];
+#define MFMA_SLOT(ACC_I0, ACC_J0, BF)                                                                        \
+    __builtin_amdgcn_sched_barrier(0);                                                                       \
+    __builtin_amdgcn_s_setprio(1);                                                                           \
+    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                         \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                        \
+            _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                    \
+                acc[ACC_I0 + i][ACC_J0 + j] =                                                                \
+                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF[j][kk], a[i][kk], acc[ACC_I0 + i][ACC_J0 + j], 0, 0, 0); \
+    __builtin_amdgcn_s_setprio(0);                                                                           \
+    __builtin_amdgcn_sched_barrier(0);
+    // One K-tile.  STAGE / WAIT are the half-tile issue and the counted wait in front of a barrier: the STEADY forms (no end-of-stream
+    // test, constant vmcnt(8)) for every K-tile whose slots stay inside the stream, the checked forms for the last two.  [Round 4 first
+    // shipped the checked forms for EVERY K-tile: the scalar compare / branch chains in front of the barriers cost the LLM shapes 4-5 %
+    // (gate_up 903 -> 955 us) — invisible to the same-binary A/B of the run-time switch.]
+#define KTILE_2PHASE(STAGE, WAIT)                                                                              \
+    {                                                                                                          \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                          \
+            _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                 \
+                b0[i][kk] = *(const bf16x8*)(B0 + (offB[i] ^ (kk << 6)));                                      \
+                b1[i][kk] = *(const bf16x8*)(B1 + (offB[i] ^ (kk << 6)));                                      \
+            }                                                                                                  \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                          \
+            _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A0 + (offA[i] ^ (kk << 6))); \
+        st.STAGE(g + 7);                                                                                       \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
+        if (STAGGER) { st.WAIT(g + 8); __builtin_amdgcn_s_barrier(); }                                         \
+        MFMA_SLOT(0, 0, b0)                                                                                    \
+        MFMA_SLOT(0, 2, b1)                                                                                    \
+        st.WAIT(g + 8); __builtin_amdgcn_s_barrier();                                                          \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                          \
+            _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A1 + (offA[i] ^ (kk << 6))); \
+        st.STAGE(g + 8);                                                                                       \
+        st.STAGE(g + 9);                                                                                       \
+        st.STAGE(g + 10);                                                                                      \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
+        if (STAGGER) { st.WAIT(g + 11); __builtin_amdgcn_s_barrier(); }                                       \
+        MFMA_SLOT(4, 2, b1)                                                                                    \
+        MFMA_SLOT(4, 0, b0)                                                                                    \
+        st.WAIT(g + 11); __builtin_amdgcn_s_barrier();                                                         \
+    }
+    if (STAGGER && wave >= 4) __builtin_amdgcn_s_barrier();
+    // K-tiles [0, nk - 2) in the steady form (every slot they stage, <= 4 t + 10, lies inside the stream), the last two in the checked
+    // form — two loops, one body each
+    const int nk_steady = max(nk - 2, 0);
+    for (int t = 0; t < nk_steady; ++t) {
+        const char* base = lds + (t & 1) * 4 * HT;
+        const char* A0 = base, *A1 = base + HT, *B0 = base + 2 * HT, *B1 = base + 3 * HT;
+        const int g = 4 * t;
+        KTILE_2PHASE(stage_steady, wait_steady)
+    }
+    at_tail();
+    for (int t = nk_steady; t < nk; ++t) {
+        const char* base = lds + (t & 1) * 4 * HT;
+        const char* A0 = base, *A1 = base + HT, *B0 = base + 2 * HT, *B1 = base + 3 * HT;
+        const int g = 4 * t;
+        KTILE_2PHASE(stage, tail_wait)
+    }
+    if (STAGGER && wave < 4) __builtin_amdgcn_s_barrier();
+#undef KTILE_2PHASE
+#undef MFMA_SLOT
+}
+
+// ---- the 256x256 tile's epilogue from registers (lane: rows brow + wm*128 + i*16 + fr, columns bcol + wn*64 + j*16 + fq*4 .. +3)
+// EPI >= 0 and < 32: the wide-store MODE bits of epilogue_pair_bf16 (1 bias, 2 GELU, 4 rotary, 8 residual, 16 preact), fixed at compile
+// time; E256_SWIGLU_FWD / _BWD: act 2 / act 3; E256_F32_STREAM: the Whisper fp32 residual stream; E256_DYN: anything else
+// (dropout, fp32 output, ...), with the feature tests per fragment (epilogue_pair_bf16<-1> or epilogue4).  The host has
+// checked that the fixed instances' conditions hold (desta_gemm_bf16_nt).  (The one-tile-per-block kernel keeps its own run-time
+// dispatch over the wide-store instances: moving it into this function made hipcc keep the GemmArgs fields in spilled SGPRs, +15 000
+// instructions per kernel.)
+constexpr int E256_DYN = -2, E256_SWIGLU_FWD = 32, E256_SWIGLU_BWD = 33, E256_F32_STREAM = 64;
+template <int EPI>
+__device__ __forceinline__ void k256_epilogue(const GemmArgs& p, int z, int brow, int bcol, int wm, int wn, int fr, int fq,
+                                              const f32x4 (&acc)[8][4]) {
+    if constexpr (EPI == E256_SWIGLU_FWD || EPI == E256_SWIGLU_BWD) {
+        const int ncol0 = bcol + wn * 64;
+        if (ncol0 < p.N) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int m = brow + wm * 128 + i * 16 + fr;
+                if (EPI == E256_SWIGLU_FWD) epilogue_swiglu_fwd(p, z, min(m, p.M - 1), m < p.M, ncol0, fq, acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+                else epilogue_swiglu_bwd(p, z, min(m, p.M - 1), m < p.M, ncol0, fq, acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+            }
+        }
+        return;
+    }
+    // whole 32-column pairs inside N, bf16 output, no side outputs: wide-store epilogue (block-uniform choice;
+    // the permlane swap needs all 64 lanes, so row guards only predicate the store)
+#define DESTA_WIDE_TILE(MODE)                                                                                          \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                                \
+            const int m = brow + wm * 128 + i * 16 + fr;                                                               \
+            const int mc = min(m, p.M - 1);                                                                            \
+            _Pragma("unroll") for (int j = 0; j < 4; j += 2) {                                                         \
+                const int ncol0 = bcol + wn * 64 + j * 16;                                                             \
+                if (ncol0 >= p.N) continue;                                   /* wave-uniform */                       \
+                epilogue_pair_bf16<MODE>(p, z, mc, m < p.M, ncol0, fq, acc[i][j], acc[i][j + 1]);   /* all lanes swap; rows >= M only skip the store */ \
+            }                                                                                                          \
+        }
+#define DESTA_F32_STREAM_TILE()                                                                                        \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                                \
+            const int m = brow + wm * 128 + i * 16 + fr;                                                               \
+            if (m >= p.M) continue;                                                                                    \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                            \
+                const int n0 = bcol + wn * 64 + j * 16 + fq * 4;                                                       \
+                if (n0 >= p.N) continue;                                                                               \
+                epilogue4_f32_stream(p, z, m, n0, acc[i][j]);                                                          \
+            }                                                                                                          \
+        }
+    if constexpr (EPI == E256_F32_STREAM) {
+        DESTA_F32_STREAM_TILE()
+    } else if constexpr (EPI >= 0) {
+        DESTA_WIDE_TILE(EPI)
+    } else {                                             // anything else (dropout, fp32 output, ...): feature tests per fragment
+        const bool pre_ok = !p.preact || (p.act == 0 && !p.res && (p.ldp & 7) == 0 && (p.sP & 7) == 0);
+        const bool wide = !p.out_f32 && pre_ok && p.act <= 1 && !p.drop_thresh && (p.N % 32 == 0) && (p.ldc % 8 == 0);
+        if (wide) {
+            DESTA_WIDE_TILE(-1)
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int m = brow + wm * 128 + i * 16 + fr;
+            if (m >= p.M) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int n0 = bcol + wn * 64 + j * 16 + fq * 4;
+                if (n0 >= p.N) continue;
+                epilogue4(p, z, m, n0, acc[i][j]);               // (no rotary epilogue here: see epilogue4)
+            }
+        }
+    }
+#undef DESTA_F32_STREAM_TILE
+#undef DESTA_WIDE_TILE
+}
+
+// raw fp32 accumulators -> the K-slice's slab of the split-K workspace
+__device__ __forceinline__ void k256_store_slab(float* slab, int wm, int wn, int fr, int fq, const f32x4 (&acc)[8][4]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            *(f32x4*)(slab + (wm * 128 + i * 16 + fr) * 256 + wn * 64 + j * 16 + fq * 4) = acc[i][j];
+}
+
 // PHASES = 4: the schedule described above.  PHASES = 2: the same half-tile stream and slots, but a K-tile is multiplied
 // in TWO phases of 32 MFMAs per wave (P1 reads A0,B0,B1 -> Q00,Q01; P2 reads A1 -> Q11,Q10 with B in registers): half the
 // workgroup barriers per K-tile (rocprofv3 PMC: the waves of the 4-phase kernel are parked at s_waitcnt / s_barrier 37 %
@@ -718,63 +933,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256_kernel(GemmArgs p) {
     const bf16_t* A = p.A + (long)z * p.sA;
     const bf16_t* B = p.B + (long)z * p.sB;
 
-    // staging sources: this thread's two 16-B chunks of each of the four half-tile kinds
-    const bf16_t* src[4][2];                              // [A0, A1, B0, B1][i]
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int idx = i * 512 + tid;
-        const int r = idx >> 3, pc = idx & 7;
-        const int c = pc ^ (r & 7);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const int arow = (r >> 6) * 128 + s2 * 64 + (r & 63);
-            const int bcolr = (r >> 5) * 64 + s2 * 32 + (r & 31);
-            src[s2][i] = A + (long)min(brow + arow, p.M - 1) * p.lda + c * 8;
-            src[2 + s2][i] = B + (long)min(bcol + bcolr, p.N - 1) * p.ldb + c * 8;
-        }
-    }
     const int nk_all = p.K / BK;
     const bool partial = (int)blockIdx.x >= p.full_tiles && p.split > 1;
     const int kt0 = partial ? (int)((long)nk_all * slice / p.split) : 0;
     const int kt1 = partial ? (int)((long)nk_all * (slice + 1) / p.split) : nk_all;
     const int nk = kt1 - kt0;
-    // issue half-tile number j of the stream
-    // tail_skip (2-phase schedule): half-tiles past the end of the stream are NOT issued — without it the stream re-loads the last K-tile
-    // into dead slots so that the counted vmcnt stays constant: 7 x 16 KiB of L2 -> LDS traffic per tile that nothing reads (2.7 % of
-    // a K = 4096 tile's operand traffic, 8.8 % at K = 1280) and a drain behind the last MFMA
-    const bool tskip = PHASES == 2 && p.tail_skip != 0;
-    const int n_ht = 4 * nk;
-    auto stage = [&](int j) {
-        if (tskip && j >= n_ht) return;                   // (wave-uniform)
-        const int t = j >> 2, q = j & 3;                  // q: 0 A0, 1 B0, 2 B1, 3 A1
-        const int kind = (q == 0) ? 0 : (q == 1) ? 2 : (q == 2) ? 3 : 1;
-        const long koff = (long)(kt0 + min(t, nk - 1)) * BK;
-        char* dst = lds + ((t & 1) * 4 + kind) * HT;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            glds16(src[kind][i] + koff, dst + (i * 512 + wave * 64) * 16);
-    };
-    // counted wait in front of a barrier: all but the 4 youngest half-tiles of the UNCAPPED stream must have landed; `issued` = stream
-    // position after this slot's stage() calls.  Steady state: 4 half-tiles x 2 ops = vmcnt(8); in the tail the stream is shorter by
-    // the overshoot, so fewer ops may stay outstanding (wave-uniform branch on a scalar)
-    auto stage_steady = [&](int j) __attribute__((always_inline)) {       // j < 4 nk: no end-of-stream test, no clamp
-        const int t = j >> 2, q = j & 3;
-        const int kind = (q == 0) ? 0 : (q == 1) ? 2 : (q == 2) ? 3 : 1;
-        const long koff = (long)(kt0 + t) * BK;
-        char* dst = lds + ((t & 1) * 4 + kind) * HT;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            glds16(src[kind][i] + koff, dst + (i * 512 + wave * 64) * 16);
-    };
-    auto wait_steady = [&](int) __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); };
-    auto tail_wait = [&](int issued) __attribute__((always_inline)) {
-        const int ov = tskip ? issued - n_ht : 0;
-        if (ov <= 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (ov == 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (ov == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (ov == 3) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
+    K256Stream st;
+    st.init(p, lds, tid, wave, A, B, brow, bcol, kt0, nk, PHASES == 2 && p.tail_skip != 0);
 
     f32x4 acc[8][4];
 #pragma unroll
@@ -796,19 +961,18 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256_kernel(GemmArgs p) {
     }
 
 #pragma unroll
-    for (int j = 0; j < 7; ++j) stage(j);
+    for (int j = 0; j < 7; ++j) st.stage(j);
     if (PHASES == 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else tail_wait(7);
+    else st.tail_wait(7);
     __builtin_amdgcn_s_barrier();
 
-    bf16x8 a[4][2], b0[2][2], b1[2][2];
-    // STAGGER: waves 4-7 (the SIMD partners of waves 0-3) run half a phase behind, so on every SIMD one wave
-    // issues its 16 MFMAs while the other issues its LDS reads / LDS-DMA: each phase is split into a LOAD
-    // slot and an MFMA slot with a barrier after each; group B enters the loop one barrier late and group A
-    // leaves it one barrier late.  Every slot ends with lgkmcnt(0) (its ds_reads have returned before any
-    // other wave may re-stage the slot) and the counted vmcnt (the shares this wave issued have landed).
+    if constexpr (PHASES == 2) {
+        k256_loop_2phase<STAGGER>(st, offA, offB, acc, [] {});
+    } else {
+        bf16x8 a[4][2], b0[2][2], b1[2][2];
+        // STAGGER: as in k256_loop_2phase, with a LOAD slot and an MFMA slot per phase and a barrier after each.
 #define SLOT_END()                                                                                                  \
-    if (PHASES == 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); \
+    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");                                                               \
     __builtin_amdgcn_s_barrier();
 #define MFMA_SLOT(ACC_I0, ACC_J0, BF)                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                                       \
@@ -820,113 +984,62 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256_kernel(GemmArgs p) {
                     __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF[j][kk], a[i][kk], acc[ACC_I0 + i][ACC_J0 + j], 0, 0, 0); \
     __builtin_amdgcn_s_setprio(0);                                                                           \
     __builtin_amdgcn_sched_barrier(0);
-    // One K-tile of the two-phase schedule.  STAGE / WAIT are the half-tile issue and the counted wait in front of a barrier: the
-    // STEADY forms (no end-of-stream test, constant vmcnt(8)) for every K-tile whose slots stay inside the stream, the checked forms
-    // for the last two.  [Round 4 first shipped the checked forms for EVERY K-tile: the scalar compare / branch chains in front of the
-    // barriers cost the LLM shapes 4-5 % (gate_up 903 -> 955 us) — invisible to the same-binary A/B of the run-time switch.]
-#define KTILE_2PHASE(STAGE, WAIT)                                                                              \
-    {                                                                                                          \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                          \
-            _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) {                                                 \
-                b0[i][kk] = *(const bf16x8*)(B0 + (offB[i] ^ (kk << 6)));                                      \
-                b1[i][kk] = *(const bf16x8*)(B1 + (offB[i] ^ (kk << 6)));                                      \
-            }                                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                          \
-            _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A0 + (offA[i] ^ (kk << 6))); \
-        STAGE(g + 7);                                                                                          \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
-        if (STAGGER) { WAIT(g + 8); __builtin_amdgcn_s_barrier(); }                                            \
-        MFMA_SLOT(0, 0, b0)                                                                                    \
-        MFMA_SLOT(0, 2, b1)                                                                                    \
-        WAIT(g + 8); __builtin_amdgcn_s_barrier();                                                             \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                          \
-            _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A1 + (offA[i] ^ (kk << 6))); \
-        STAGE(g + 8);                                                                                          \
-        STAGE(g + 9);                                                                                          \
-        STAGE(g + 10);                                                                                         \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
-        if (STAGGER) { WAIT(g + 11); __builtin_amdgcn_s_barrier(); }                                           \
-        MFMA_SLOT(4, 2, b1)                                                                                    \
-        MFMA_SLOT(4, 0, b0)                                                                                    \
-        WAIT(g + 11); __builtin_amdgcn_s_barrier();                                                            \
-    }
-    if (STAGGER && wave >= 4) __builtin_amdgcn_s_barrier();
-    // two-phase schedule: K-tiles [0, nk - 2) in the steady form (every slot they stage, <= 4 t + 10, lies inside the stream), the last
-    // two in the checked form — two loops, one body each
-    const int nk_steady = PHASES == 2 ? max(nk - 2, 0) : 0;
-    if constexpr (PHASES == 2) {
-        for (int t = 0; t < nk_steady; ++t) {
+        if (STAGGER && wave >= 4) __builtin_amdgcn_s_barrier();
+        for (int t = 0; t < nk; ++t) {
             const char* base = lds + (t & 1) * 4 * HT;
             const char* A0 = base, *A1 = base + HT, *B0 = base + 2 * HT, *B1 = base + 3 * HT;
             const int g = 4 * t;
-            KTILE_2PHASE(stage_steady, wait_steady)
+            // ---------------- P1: A0, B0 -> Q00
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) b0[i][kk] = *(const bf16x8*)(B0 + (offB[i] ^ (kk << 6)));
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A0 + (offA[i] ^ (kk << 6)));
+            st.stage(g + 7);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (STAGGER) { SLOT_END() }
+            MFMA_SLOT(0, 0, b0)
+            SLOT_END()
+            // ---------------- P2: B1 -> Q01
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) b1[i][kk] = *(const bf16x8*)(B1 + (offB[i] ^ (kk << 6)));
+            st.stage(g + 8);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (STAGGER) { SLOT_END() }
+            MFMA_SLOT(0, 2, b1)
+            SLOT_END()
+            // ---------------- P3: A1 -> Q11
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A1 + (offA[i] ^ (kk << 6)));
+            st.stage(g + 9);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (STAGGER) { SLOT_END() }
+            MFMA_SLOT(4, 2, b1)
+            SLOT_END()
+            // ---------------- P4: (B0 in registers) -> Q10
+            st.stage(g + 10);
+            if (STAGGER) { SLOT_END() }
+            MFMA_SLOT(4, 0, b0)
+            SLOT_END()
         }
-        for (int t = nk_steady; t < nk; ++t) {
-            const char* base = lds + (t & 1) * 4 * HT;
-            const char* A0 = base, *A1 = base + HT, *B0 = base + 2 * HT, *B1 = base + 3 * HT;
-            const int g = 4 * t;
-            KTILE_2PHASE(stage, tail_wait)
-        }
-    }
-    for (int t = (PHASES == 2 ? nk : 0); t < nk; ++t) {
-        const char* base = lds + (t & 1) * 4 * HT;
-        const char* A0 = base, *A1 = base + HT, *B0 = base + 2 * HT, *B1 = base + 3 * HT;
-        const int g = 4 * t;
-        // ---------------- P1: A0, B0 -> Q00
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) b0[i][kk] = *(const bf16x8*)(B0 + (offB[i] ^ (kk << 6)));
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A0 + (offA[i] ^ (kk << 6)));
-        stage(g + 7);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (STAGGER) { SLOT_END() }
-        MFMA_SLOT(0, 0, b0)
-        SLOT_END()
-        // ---------------- P2: B1 -> Q01
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) b1[i][kk] = *(const bf16x8*)(B1 + (offB[i] ^ (kk << 6)));
-        stage(g + 8);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (STAGGER) { SLOT_END() }
-        MFMA_SLOT(0, 2, b1)
-        SLOT_END()
-        // ---------------- P3: A1 -> Q11
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A1 + (offA[i] ^ (kk << 6)));
-        stage(g + 9);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (STAGGER) { SLOT_END() }
-        MFMA_SLOT(4, 2, b1)
-        SLOT_END()
-        // ---------------- P4: (B0 in registers) -> Q10
-        stage(g + 10);
-        if (STAGGER) { SLOT_END() }
-        MFMA_SLOT(4, 0, b0)
-        SLOT_END()
-    }
-    if (STAGGER && wave < 4) __builtin_amdgcn_s_barrier();
-#undef KTILE_2PHASE
+        if (STAGGER && wave < 4) __builtin_amdgcn_s_barrier();
 #undef MFMA_SLOT
 #undef SLOT_END
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the dummy tail loads before LDS is released
 
     if (partial) {
         // raw fp32 accumulators -> this item's slab
         float* slab = p.ws + ((long)z * (p.tilesM * p.tilesN - p.full_tiles) * p.split +
                               (long)(blockIdx.x - p.full_tiles)) * (256 * 256);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                *(f32x4*)(slab + (wm * 128 + i * 16 + fr) * 256 + wn * 64 + j * 16 + fq * 4) = acc[i][j];
+        k256_store_slab(slab, wm, wn, fr, fq, acc);
         if (!p.tickets) return;                            // a fix-up launch sums the slices in order
         // In-kernel reduction, scattered: once ALL `split` slices of the tile have arrived, slice s sums rows
         // [256 s / split, 256 (s+1) / split) of the tile over the slabs IN SLICE ORDER (deterministic) and runs the epilogue on
@@ -1046,37 +1159,52 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256_kernel(GemmArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// PERSISTENT form of the 256x256 kernel: gridDim.x = min(items, CUs) blocks, block b walks items b, b+G, ...
-// and the half-tile stream simply CONTINUES across item boundaries: while the last phases of item s run, the
-// LDS-DMA stream is already loading the first K-tiles of item s+1 (no per-tile prologue), and the epilogue
-// stores of item s drain behind the main loop of item s+1 (with one block per CU nothing else would hide
-// them).  With the staggered schedule the two wave groups run their epilogues half a phase apart, each
-// beside the other group's MFMA slot.  Same phase structure, LDS slot rule and counted vmcnt(10) as above.
-template <bool STAGGER, int PHASES>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, int n_items) {
-    __shared__ __attribute__((aligned(16))) char lds[2 * 4 * HT];
-
+// PERSISTENT form of the staggered two-phase 256x256 kernel: 256 blocks (one per CU) draw work items from eight per-XCD queues
+// until theirs is empty.  Same K loop (k256_loop_2phase), same item -> (tile, K-slice) map and slab layout as the one-tile-per-block
+// kernel, so every item is computed by one block in the same K order with the same epilogue arithmetic: bit-identical results.
+//   * Queues.  Queue x (x = blockIdx.x & 7: blocks dealt round-robin over the XCDs share one) holds the contiguous L range xcd_remap
+//     gives XCD x in the one-tile-per-block grid, in the same order, then the split-K items j = x, x + 8, ... of the tail (slab j).
+//     A ticket is a relaxed agent-scope fetch_add on the queue's counter.  No stealing from other queues.
+//   * Ticket ahead.  Thread 0 draws the NEXT item's ticket in front of the last two K-tiles of the current one (the atomic's latency
+//     hides behind them), and hands it to the block through LDS after the loop's final vmcnt(0).
+//   * Prologue under the epilogue.  The first 7 half-tiles of the next item are issued into the free LDS before the current item's
+//     epilogue runs from registers; the next item's first counted wait then also retires the epilogue's stores (conservative count:
+//     stores are younger than the DMA, so vmcnt(8) <= 8 outstanding still implies the oldest 6 DMA ops, in-order loads, have landed).
+//   * Counters.  queue[0..7] = tickets, queue[8] = departures; the last block to depart (every block has drawn its final, empty
+//     ticket) zeroes all nine for the next launch on the stream.  They sit in the last 64 bytes of the caller's workspace, which is
+//     handed over zeroed once (desta_hip.h).
+// EPI: the epilogue instance (k256_epilogue); every instance but act 2 / act 3 also writes raw K-slice slabs.
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, int* queue) {
+    __shared__ __attribute__((aligned(16))) char lds[2 * 4 * HT + 16];     // [buf][A0,A1,B0,B1] + the ticket hand-off (one array: see
+                                                                            // cdna_hip_programming.md on a second __shared__ object beside glds)
+    int* s_ticket = (int*)(lds + 2 * 4 * HT);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
-    const int G = gridDim.x, z = blockIdx.y;
-    const int n_my = (n_items - (int)blockIdx.x + G - 1) / G;
-    const bf16_t* A = p.A + (long)z * p.sA;
-    const bf16_t* B = p.B + (long)z * p.sB;
-    const int nk_all = p.K / BK;
+    const int fr = lane & 15, fq = lane >> 4;
     constexpr int GROUP_M = GEMM_GROUP_M;              // the fix-up / persistent kernels must map L -> tile like the main kernel
+    const int nk_all = p.K / BK;
 
-    // item id -> tile origin + K range
-    auto item_geom = [&](int s, int& brow, int& bcol, int& kt0, int& nk, bool& partial, int& slab) {
-        const int id = blockIdx.x + s * G;
+    // this block's queue: whole tiles [lo, lo + n_full) of the L order, then split items j = xq + 8 u
+    const int xq = blockIdx.x & 7;
+    const int F = p.full_tiles, q8 = F >> 3, r8 = F & 7;
+    const int lo = (xq < r8) ? xq * (q8 + 1) : r8 * (q8 + 1) + (xq - r8) * q8;
+    const int n_full = q8 + (xq < r8 ? 1 : 0);
+    const int n_split_items = p.split > 1 ? (p.tilesM * p.tilesN - F) * p.split : 0;
+    const int n_items = n_full + (n_split_items > xq ? (n_split_items - xq + 7) >> 3 : 0);
+    int* counter = queue + xq;
+
+    int brow, bcol, kt0, nk, slab;
+    bool partial;
+    auto geometry = [&](int tk) {                        // ticket -> tile origin, K range, slab
         int L, slice = 0;
-        partial = false;
-        if (id < p.full_tiles) {
-            L = xcd_remap(id, p.full_tiles);
+        partial = tk >= n_full;
+        if (!partial) {
+            L = lo + tk;
         } else {
-            const int j = id - p.full_tiles;
-            L = p.full_tiles + j / p.split;
-            slice = j % p.split;
-            partial = p.split > 1;
+            slab = xq + 8 * (tk - n_full);
+            L = F + slab / p.split;
+            slice = slab % p.split;
         }
         const int gspan = GROUP_M * p.tilesN;
         const int first_m = (L / gspan) * GROUP_M;
@@ -1086,45 +1214,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, i
         kt0 = partial ? (int)((long)nk_all * slice / p.split) : 0;
         const int kt1 = partial ? (int)((long)nk_all * (slice + 1) / p.split) : nk_all;
         nk = kt1 - kt0;
-        slab = id - p.full_tiles;
     };
+    auto draw = [&]() { return __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
 
-    // ---- issue side: stream state
-    const bf16_t* src[4][2];
-    int iss_s = 0, iss_t = 0, iss_nk = 1, iss_kt0 = 0, issT = 0;     // item, local K-tile, its count / first tile, global K-tile count
-    auto setup_issue = [&](int s) {
-        int brow, bcol, slab; bool partial;
-        item_geom(s, brow, bcol, iss_kt0, iss_nk, partial, slab);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = i * 512 + tid;
-            const int r = idx >> 3, pc = idx & 7;
-            const int c = pc ^ (r & 7);
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const int arow = (r >> 6) * 128 + s2 * 64 + (r & 63);
-                const int bcolr = (r >> 5) * 64 + s2 * 32 + (r & 31);
-                src[s2][i] = A + (long)min(brow + arow, p.M - 1) * p.lda + c * 8;
-                src[2 + s2][i] = B + (long)min(bcol + bcolr, p.N - 1) * p.ldb + c * 8;
-            }
-        }
-    };
-    // issue the next half-tile of the stream; Q = position within the (A0,B0,B1,A1) K-tile group (static per call site)
-#define STAGE_NEXT(Q)                                                                                   \
-    {                                                                                                   \
-        constexpr int kind_ = ((Q) == 0) ? 0 : ((Q) == 1) ? 2 : ((Q) == 2) ? 3 : 1;                      \
-        const long koff_ = (long)(iss_kt0 + min(iss_t, iss_nk - 1)) * BK;                               \
-        char* dst_ = lds + ((issT & 1) * 4 + kind_) * HT;                                               \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                \
-            glds16(src[kind_][i_] + koff_, dst_ + (i_ * 512 + wave * 64) * 16);                         \
-        if ((Q) == 3) {                                                                                 \
-            ++issT; ++iss_t;                                                                            \
-            if (iss_t == iss_nk && iss_s + 1 < n_my) { ++iss_s; iss_t = 0; setup_issue(iss_s); }        \
-        }                                                                                               \
-    }
-
-    f32x4 acc[8][4];
-    const int fr = lane & 15, fq = lane >> 4;
     int offA[4], offB[2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -1137,154 +1229,68 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, i
         offB[i] = r * 128 + ((fq ^ (r & 7)) << 4);
     }
 
-    setup_issue(0);
-    STAGE_NEXT(0) STAGE_NEXT(1) STAGE_NEXT(2) STAGE_NEXT(3) STAGE_NEXT(0) STAGE_NEXT(1) STAGE_NEXT(2)
-    if (PHASES == 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    bf16x8 a[4][2], b0[2][2], b1[2][2];
-#define SLOT_END()                                                                                                  \
-    if (PHASES == 4) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); \
-    __builtin_amdgcn_s_barrier();
-#define MFMA_SLOT(ACC_I0, ACC_J0, BF)                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                       \
-    __builtin_amdgcn_s_setprio(1);                                                                           \
-    _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                         \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                        \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                    \
-                acc[ACC_I0 + i][ACC_J0 + j] =                                                                \
-                    __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF[j][kk], a[i][kk], acc[ACC_I0 + i][ACC_J0 + j], 0, 0, 0); \
-    __builtin_amdgcn_s_setprio(0);                                                                           \
-    __builtin_amdgcn_sched_barrier(0);
-    if (STAGGER && wave >= 4) __builtin_amdgcn_s_barrier();
-    int Tc = 0;                                                       // global K-tile counter of the consumer
-    for (int s = 0; s < n_my; ++s) {
-        int brow, bcol, kt0, nk, slab; bool partial;
-        item_geom(s, brow, bcol, kt0, nk, partial, slab);
+    if (tid == 0) *s_ticket = draw();
+    __syncthreads();                                     // (no LDS-DMA in flight yet)
+    int tk = *s_ticket;
+    K256Stream st;
+    if (tk < n_items) {
+        geometry(tk);
+        st.init(p, lds, tid, wave, p.A, p.B, brow, bcol, kt0, nk, p.tail_skip != 0);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) st.stage(j);
+    }
+    f32x4 acc[8][4];
+    while (tk < n_items) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int t = 0; t < nk; ++t, ++Tc) {
-            const char* base = lds + (Tc & 1) * 4 * HT;
-            const char* A0 = base, *A1 = base + HT, *B0 = base + 2 * HT, *B1 = base + 3 * HT;
-            if constexpr (PHASES == 2) {
-                // P1: A0, B0, B1 -> Q00, Q01
+        st.tail_wait(7);
+        __builtin_amdgcn_s_barrier();
+        // the next ticket, drawn by lane 0 of wave 0 in front of the last two K-tiles.  As inline asm, because the compiler waits
+        // vmcnt(0) for the builtin's result at once (draining the K loop's LDS-DMA); here the result register is only read after
+        // the explicit vmcnt(0) below.  Every wave runs the instruction with EXEC = (wave 0 ? lane 0 : none): no branch, no copy
+        // of the pending register.  (Same encoding as the builtin's relaxed agent-scope fetch_add: returning, sc0.)
+        int nxt;
+        k256_loop_2phase<true>(st, offA, offB, acc, [&] {
+            const unsigned lane_mask = __builtin_amdgcn_readfirstlane(wave == 0 ? 1u : 0u);
+            unsigned long saved;
+            asm volatile("s_mov_b64 %1, exec\n\t"
+                         "s_mov_b32 exec_lo, %3\n\t"
+                         "s_mov_b32 exec_hi, 0\n\t"
+                         "global_atomic_add %0, %2, %4, off sc0\n\t"
+                         "s_mov_b64 exec, %1"
+                         : "=&v"(nxt), "=&s"(saved) : "v"(counter), "s"(lane_mask), "v"(1) : "memory");
+        });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the stream's tail and the ticket have landed; LDS is free
+        if (tid == 0) *s_ticket = nxt;
+        __syncthreads();                                 // (a bare s_barrier: nothing is in flight)
+        const int cur_brow = brow, cur_bcol = bcol, cur_slab = slab;
+        const bool cur_partial = partial;
+        tk = *s_ticket;
+        if (tk < n_items) {                              // next item's first 7 half-tiles, in flight under this item's epilogue
+            geometry(tk);
+            st.init(p, lds, tid, wave, p.A, p.B, brow, bcol, kt0, nk, p.tail_skip != 0);
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) {
-                        b0[i][kk] = *(const bf16x8*)(B0 + (offB[i] ^ (kk << 6)));
-                        b1[i][kk] = *(const bf16x8*)(B1 + (offB[i] ^ (kk << 6)));
-                    }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A0 + (offA[i] ^ (kk << 6)));
-                STAGE_NEXT(3)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (STAGGER) { SLOT_END() }
-                MFMA_SLOT(0, 0, b0)
-                MFMA_SLOT(0, 2, b1)
-                SLOT_END()
-                // P2: A1 (B in registers) -> Q11, Q10
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A1 + (offA[i] ^ (kk << 6)));
-                STAGE_NEXT(0)
-                STAGE_NEXT(1)
-                STAGE_NEXT(2)
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (STAGGER) { SLOT_END() }
-                MFMA_SLOT(4, 2, b1)
-                MFMA_SLOT(4, 0, b0)
-                SLOT_END()
+            for (int j = 0; j < 7; ++j) st.stage(j);
+        }
+        if constexpr (EPI != E256_SWIGLU_FWD && EPI != E256_SWIGLU_BWD) {
+            if (cur_partial) {
+                k256_store_slab(p.ws + (long)cur_slab * (256 * 256), wm, wn, fr, fq, acc);
                 continue;
             }
-            // P1: A0, B0 -> Q00            (stream position g+7 : A1 of the K-tile after next)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) b0[i][kk] = *(const bf16x8*)(B0 + (offB[i] ^ (kk << 6)));
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A0 + (offA[i] ^ (kk << 6)));
-            STAGE_NEXT(3)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (STAGGER) { SLOT_END() }
-            MFMA_SLOT(0, 0, b0)
-            SLOT_END()
-            // P2: B1 -> Q01
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) b1[i][kk] = *(const bf16x8*)(B1 + (offB[i] ^ (kk << 6)));
-            STAGE_NEXT(0)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (STAGGER) { SLOT_END() }
-            MFMA_SLOT(0, 2, b1)
-            SLOT_END()
-            // P3: A1 -> Q11
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) a[i][kk] = *(const bf16x8*)(A1 + (offA[i] ^ (kk << 6)));
-            STAGE_NEXT(1)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (STAGGER) { SLOT_END() }
-            MFMA_SLOT(4, 2, b1)
-            SLOT_END()
-            // P4: (B0 in registers) -> Q10
-            STAGE_NEXT(2)
-            if (STAGGER) { SLOT_END() }
-            MFMA_SLOT(4, 0, b0)
-            SLOT_END()
         }
-        // ---- epilogue of item s (no barrier inside: the other wave group keeps streaming)
-        if (partial) {
-            float* slabp = p.ws + ((long)z * (p.tilesM * p.tilesN - p.full_tiles) * p.split + (long)slab) * (256 * 256);
+        k256_epilogue<EPI>(p, 0, cur_brow, cur_bcol, wm, wn, fr, fq, acc);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                     // every thread is past its last draw's use
+    if (tid == 0) {
+        const int dpt = __hip_atomic_fetch_add(queue + 8, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (dpt == (int)gridDim.x - 1) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    *(f32x4*)(slabp + (wm * 128 + i * 16 + fr) * 256 + wn * 64 + j * 16 + fq * 4) = acc[i][j];
-            continue;
-        }
-        const bool wide = !p.out_f32 && !p.preact && p.act <= 1 && !p.drop_thresh && (p.N % 32 == 0) && (p.ldc % 8 == 0);
-        if (wide) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int m = brow + wm * 128 + i * 16 + fr;
-                const int mc = min(m, p.M - 1);
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {
-                    const int ncol0 = bcol + wn * 64 + j * 16;
-                    if (ncol0 >= p.N) continue;
-                    epilogue_pair_bf16(p, z, mc, m < p.M, ncol0, fq, acc[i][j], acc[i][j + 1]);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int m = brow + wm * 128 + i * 16 + fr;
-                if (m >= p.M) continue;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int n0 = bcol + wn * 64 + j * 16 + fq * 4;
-                    if (n0 >= p.N) continue;
-                    epilogue4(p, z, m, n0, acc[i][j]);
-                }
-            }
+            for (int k = 0; k < 9; ++k) __hip_atomic_store(queue + k, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (STAGGER && wave < 4) __builtin_amdgcn_s_barrier();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the tail of the stream before LDS is released
-#undef KTILE_2PHASE
-#undef MFMA_SLOT
-#undef SLOT_END
-#undef STAGE_NEXT
 }
 
 // sum the K-slice slabs of the split tiles (fixed order) and run the normal epilogue
@@ -1485,9 +1491,9 @@ __global__ __launch_bounds__(512, (COLS == 16 && U == 2) ? 2 : 1) void gemm_bf16
 
 static int g_last_kernel = 0;      // kernel family of the most recent launch: 1 = 128x128, 2 = 256x256 (+ split-K fix-up), 3 = skinny
 extern "C" int desta_gemm_last_kernel(void) { return g_last_kernel; }
-static int g_force_variant = 0;   // 0 auto, 1 = 128x128, 2 = 256x256 lockstep, 3 = staggered, 4 = staggered persistent (tuning / tests)
+static int g_force_variant = 0;   // 0 auto, 1 = 128x128, 2 = 256x256 lockstep, 3 = staggered, 4 / 8 = persistent tile queue (tuning / tests)
 extern "C" int desta_gemm_force_variant(int v) { g_force_variant = v; return DESTA_OK; }
-static int g_persistent = 0;      // automatic choice may use the persistent kernel (in-situ A/B: no gain)
+static int g_persistent = 1;      // option 0: 0 = never the persistent tile-queue kernel, 1 = for multi-round grids without a split-K tail (default), 2 = also with one
 static int g_stagger = 1;         // automatic choice uses the staggered schedule
 static int g_inkernel_splitk = 0; // option 5: K-slices of tail tiles reduced inside the GEMM launch instead of by the fix-up launch (measured: no gain)
 static int g_small_ring = 1;      // option 6: 0 never, 1 the four-slot ring form of the 128x128 kernel when its grid leaves one block per CU, 2 always (A/B runs)
@@ -1509,8 +1515,6 @@ extern "C" int desta_gemm_set_option(int option, int value) {
     else if (option == 4) g_phases2 = value;
     else if (option == 5) g_inkernel_splitk = value;
     else if (option == 6) g_small_ring = value;
-    else if (option == 7 || option == 8) { /* (round 3's de-synchronised start: measured no gain, removed) */ }
-    else if (option == 9) { /* (round 4's packed-polynomial GELU: measured equal in the step, and its code in every epilogue fragment cost the PLAIN path 17 % at K = 1280: removed) */ }
     else if (option == 10) g_tail_skip = value;
     else if (option == 3) {
         if (value < 1 || value > 65535) { desta_set_error("gemm_set_option: skinny grid %d out of range", value); return DESTA_EINVAL; }
@@ -1623,21 +1627,44 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
         a.tilesM = tM; a.tilesN = tN;
         a.full_tiles = full; a.split = split; a.ws = (float*)d->workspace;
         const int items = full + (int)(T - full) * split;
-        // tickets: the last 4 KiB of the workspace (<= 128 split tiles); zero at first use (the caller hands over a zeroed
-        // workspace once) and self-resetting afterwards.  Only the plain (non-persistent) kernels carry the in-kernel reduce.
-        const bool persistent_ = g_force_variant == 4 || g_force_variant == 8 || (g_force_variant == 0 && g_persistent && items > NCU);
-        const bool inkernel = split > 1 && g_inkernel_splitk && !persistent_;
+        // The persistent tile-queue kernel (staggered two-phase schedule; batch 1, a workspace to hold its queue counters): by default
+        // for grids of more than one round of whole tiles without a split-K tail (option 0 = 1; 2 = split-tail grids too, 0 = never).
+        const bool can_persist = d->batch == 1 && d->workspace && d->workspace_bytes >= 4096 && ((uintptr_t)d->workspace % 16) == 0;
+        const bool persistent = can_persist && (g_force_variant == 4 || g_force_variant == 8 ||
+                                                (g_force_variant == 0 && g_stagger && g_phases2 &&
+                                                 ((g_persistent == 1 && split == 1 && T > NCU) || (g_persistent == 2 && items > NCU))));
+        // tickets: the last 4 KiB of the workspace (<= 128 split tiles: its first 1 KiB); zero at first use (the caller hands over a
+        // zeroed workspace once) and self-resetting afterwards.  Only the one-tile-per-block kernels carry the in-kernel reduce.
+        // The persistent kernel's nine queue counters are the last 64 bytes, self-resetting the same way.
+        const bool inkernel = split > 1 && g_inkernel_splitk && !persistent;
         a.tickets = inkernel ? (int*)((char*)d->workspace + d->workspace_bytes - 4096) : nullptr;
-        // variants: 2 = lockstep, 3 = staggered (+4-7 %), 4 = staggered + persistent cross-tile streaming
-        //           (default when a block gets more than one item; +3-7 % on the LLM shapes)
-        const bool persistent = g_force_variant == 4 || (g_force_variant == 0 && g_persistent && items > NCU);
-        if (d->act == 2 || d->act == 3) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 2, 1>), dim3(items, d->batch), dim3(512), 0, (hipStream_t)stream, a);
-        else if (g_force_variant == 2 || (g_force_variant == 0 && !g_stagger)) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<false, 4>), dim3(items, d->batch), dim3(512), 0, (hipStream_t)stream, a);
-        else if (g_force_variant == 8) hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<true, 2>), dim3(items < NCU ? items : NCU, d->batch), dim3(512), 0, (hipStream_t)stream, a, items);
-        else if (persistent) hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<true, 4>), dim3(items < NCU ? items : NCU, d->batch), dim3(512), 0, (hipStream_t)stream, a, items);
-        else if (g_force_variant == 6 || (g_force_variant == 0 && g_phases2)) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 2>), dim3(items, d->batch), dim3(512), 0, (hipStream_t)stream, a);
-        else if (g_force_variant == 7) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<false, 2>), dim3(items, d->batch), dim3(512), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 4>), dim3(items, d->batch), dim3(512), 0, (hipStream_t)stream, a);
+        hipStream_t st = (hipStream_t)stream;
+        if (persistent) {
+            int* queue = (int*)((char*)d->workspace + ((d->workspace_bytes - 64) & ~(size_t)15));
+            const bool pre_ok = !d->preact || (d->act == 0 && !d->residual && (d->ldp & 7) == 0 && (d->stride_p & 7) == 0);
+            const bool wide = !d->out_f32 && pre_ok && d->act <= 1 && a.drop_thresh == 0 && d->N % 32 == 0 && d->ldc % 8 == 0;
+            const int mode = (d->bias ? 1 : 0) | (d->act == 1 ? 2 : 0) | (d->rope_cos_sin ? 4 : 0) | (d->residual ? 8 : 0) | (d->preact ? 16 : 0);
+            const bool f32_stream = d->out_f32 && d->bias && d->residual && d->residual_f32 && !d->preact && d->act == 0 && a.drop_thresh == 0;
+            const dim3 grid(NCU), blk(512);
+#define P256_LAUNCH(E_) hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<E_>), grid, blk, 0, st, a, queue)
+            if (d->act == 2) P256_LAUNCH(E256_SWIGLU_FWD);
+            else if (d->act == 3) P256_LAUNCH(E256_SWIGLU_BWD);
+            else if (wide && mode == 0) P256_LAUNCH(0);                // plain
+            else if (wide && mode == 8) P256_LAUNCH(8);                // residual
+            else if (wide && mode == 4) P256_LAUNCH(4);                // rotary
+            else if (wide && mode == 1) P256_LAUNCH(1);                // bias
+            else if (wide && mode == 3) P256_LAUNCH(3);                // bias + GELU
+            else if (wide && mode == 16) P256_LAUNCH(16);              // preact copy
+            else if (f32_stream) P256_LAUNCH(E256_F32_STREAM);         // Whisper fp32 residual stream
+            else P256_LAUNCH(E256_DYN);
+#undef P256_LAUNCH
+        }
+        // variants: 2 = lockstep, 3 = staggered (+4-7 %), 6 / 7 = staggered / lockstep two-phase schedule
+        else if (d->act == 2 || d->act == 3) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 2, 1>), dim3(items, d->batch), dim3(512), 0, st, a);
+        else if (g_force_variant == 2 || (g_force_variant == 0 && !g_stagger)) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<false, 4>), dim3(items, d->batch), dim3(512), 0, st, a);
+        else if (g_force_variant == 6 || g_force_variant == 4 || g_force_variant == 8 || (g_force_variant == 0 && g_phases2)) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 2>), dim3(items, d->batch), dim3(512), 0, st, a);
+        else if (g_force_variant == 7) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<false, 2>), dim3(items, d->batch), dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 4>), dim3(items, d->batch), dim3(512), 0, st, a);
         if (split > 1 && !inkernel)
             hipLaunchKernelGGL(gemm_splitk_fixup_kernel, dim3((unsigned)(T - full) * 64, d->batch), dim3(256), 0, (hipStream_t)stream, a);
     } else {

@@ -91,9 +91,12 @@ typedef struct desta_gemm_desc {
     uint64_t dropout_seed;             /*   = desta_dropout_mask(seed, m*N + n) (BertSelfOutput/BertOutput, p=0.1) */
     void* workspace;                   /* optional fp32 scratch for the split-K tail (NULL = never split);   */
     size_t workspace_bytes;            /* 64 MiB + 4 KiB covers every shape (<= 256 slabs of 256x256 fp32);   */
-                                       /* its LAST 4 KiB are the arrival tickets of the in-kernel K-slice     */
-                                       /* reduction: zero when first handed over, self-resetting afterwards;  */
-                                       /* one workspace per stream (two concurrent GEMMs must not share it)   */
+                                       /* its LAST 4 KiB hold the arrival tickets of the in-kernel K-slice    */
+                                       /* reduction (first 1 KiB) and the tile-queue counters of the          */
+                                       /* persistent 256x256 kernel (last 64 B): hand the workspace over      */
+                                       /* ZEROED once and then leave it alone (both reset themselves after    */
+                                       /* every launch); one workspace per stream (two concurrent GEMMs must  */
+                                       /* not share it)                                                        */
     int trans_a, trans_b;              /* != 0: the operand is stored transposed, A as [K,M] (lda = row stride), B as   */
                                        /*   [K,N]: autograd's dW = dY^T X (both) and dX = dY W (trans_b) without a        */
                                        /*   materialised transpose; M resp. N must be a multiple of 8                     */
@@ -113,22 +116,22 @@ typedef struct desta_gemm_desc {
     int rope_cols, rope_head_dim;
 } desta_gemm_desc;
 int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream);
-/* tuning / tests only: 0 = automatic tile choice, 1 = force 128x128, 2 / 3 / 4 = force the 256x256 kernel with the
- * lockstep / staggered / staggered-persistent four-phase schedule, 6 / 7 = staggered / lockstep two-phase schedule,
- * 8 = two-phase schedule in the persistent tile walk */
+/* tuning / tests only: 0 = automatic tile choice, 1 = force 128x128, 2 / 3 = force the 256x256 kernel with the lockstep /
+ * staggered four-phase schedule, 6 / 7 = staggered / lockstep two-phase schedule, 4 / 8 = the persistent tile-queue kernel
+ * (staggered two-phase; batch 1 with a workspace, else variant 6) */
 int desta_gemm_force_variant(int variant);
 /* kernel family the most recent desta_gemm_bf16_nt call launched: 1 = 128x128, 2 = 256x256 (+ split-K fix-up), 3 = skinny
  * (bench.py attributes its HIP-event timings to the dominant kernel with this) */
 int desta_gemm_last_kernel(void);
-int desta_gemm_set_persistent(int on);   /* 1: the automatic choice uses the persistent kernel when a block owns > 1 item */
-/* A/B switches of the automatic choice: option 0 = persistent, 1 = staggered, 2 = skinny (M <= 16) kernel variant
+int desta_gemm_set_persistent(int on);   /* = desta_gemm_set_option(0, on) */
+/* A/B switches of the automatic choice: option 0 = persistent tile-queue 256x256 kernel (0 never; 1, default: batch 1, a workspace,
+ * more than one round of 256 whole tiles and no split-K tail; 2: also grids with a split-K tail), 1 = staggered, 2 = skinny (M <= 16) kernel variant
  * (0 auto, else COLS*10 + U: 162 164 322 641), 3 = persistent grid size of the skinny kernel (default 512 = 2 blocks per CU),
  * 4 = two-phase schedule of the 256x256 kernel (default 1; 0 = the four-phase schedule), 5 = K-slices of tail tiles reduced inside
  * the GEMM launch instead of by the fix-up launch (default 0), 6 = four-slot software-pipelined ring form of the 128x128 kernel:
  * 0 never, 1 (default) when the grid leaves one block per CU (<= 256 tiles), 2 always; 10 = the two-phase 256x256 kernel stops its
  * half-tile stream at the last K-tile (default 1; 0 = re-load dead slots as rounds 1-3 did); bit-identical results in every setting.
- * Options 7, 8 (round 3's de-synchronised start) and 9 (round 4's polynomial GELU) are accepted and ignored: both measured equal and
- * their code slowed every tile of the kernel (profiles/r04_gemm_regression_bisect.log). */
+ * Options 7, 8 (round 3's de-synchronised start) and 9 (round 4's polynomial GELU) were removed and return DESTA_EINVAL. */
 int desta_gemm_set_option(int option, int value);
 
 /* ------------------------------------------------------------------------------------------
