@@ -1,0 +1,321 @@
+// One decode step of HF's logits chain on bf16 logits (gfx950): repetition penalty -> greedy argmax, or
+// temperature -> top-k -> top-p -> min-p -> one draw.  Reference call sites (TF: = transformers 5.15):
+//   llm_model.generate(...) ........ modeling_desta25.py:1419-1427 (inputs_embeds), :1703-1711 (input_ids)
+//   processor order ................ TF:generation/utils.py:1175 (penalty), :1296-1330 (warpers, do_sample only)
+//   processors ..................... TF:generation/logits_process.py RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper,
+//                                    TopKLogitsWarper, TopPLogitsWarper, MinPLogitsWarper; scores are fp32 (TF:generation/utils.py:2894)
+//
+// One 1024-thread block per row, one launch per step.  Every score is recomputed from the bf16 row on each pass (the row stays
+// in L2): s = bf16 logit, penalised through an LDS bitmap of the row's history tokens, then t = s / T.  Scores map to monotone
+// 32-bit keys, and both cut-offs are found by a radix select over those keys with LDS histograms (12 + 10 + 10 bits, three
+// passes each): top-k on counts, top-p on masses e_j = exp(t_j - t_max) held as 2^-40 fixed point, so every sum is an
+// integer sum and its order cannot change the result.  The draw inverts the prefix sum of the kept masses in index order.
+#include "common.h"
+#include "desta_hip.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int SNT = 1024;                      // threads per row
+constexpr int SBINS = 4096;                    // bins of the first radix digit (key bits 31..20); later digits use 1024
+constexpr int PEN_MAX_COLS = 262144;           // LDS bitmap of penalised tokens: 32 KiB
+constexpr float MASS_ONE = 1099511627776.0f;   // 2^40: fixed-point scale of exp(t - t_max) <= 1
+
+// monotone map of fp32 order onto u32; -0 maps onto +0 (they compare equal in torch)
+__device__ __forceinline__ unsigned f32_key(float v) {
+    unsigned b = __float_as_uint(v);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_f32(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+// f(c, bf16 bits) over a row, element c on thread c / 8 % SNT (16-B loads when the row is 16-B aligned)
+template <class F>
+__device__ __forceinline__ void row_strided(const bf16_t* __restrict__ row, int cols, bool vec, F&& f) {
+    int c = threadIdx.x;
+    if (vec) {
+        const int n8 = cols >> 3;
+        for (int g = threadIdx.x; g < n8; g += SNT) {
+            const u16x8 v = *(const u16x8*)(row + (long)g * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f(g * 8 + j, (bf16_t)v[j]);
+        }
+        c = n8 * 8 + threadIdx.x;
+    }
+    for (; c < cols; c += SNT) f(c, row[c]);
+}
+// f(c, bf16 bits) over this thread's contiguous chunk [c0, c1) (c0 a multiple of 8), in index order
+template <class F>
+__device__ __forceinline__ void row_chunk(const bf16_t* __restrict__ row, int c0, int c1, bool vec, F&& f) {
+    int c = c0;
+    if (vec)
+        for (; c + 8 <= c1; c += 8) {
+            const u16x8 v = *(const u16x8*)(row + c);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f(c + j, (bf16_t)v[j]);
+        }
+    for (; c < c1; ++c) f(c, row[c]);
+}
+
+__device__ __forceinline__ u64 wave_incl_scan(u64 v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const u64 y = __shfl_up(v, o, 64);
+        if (lane >= o) v += y;
+    }
+    return v;
+}
+
+// Radix step over bins[0, R * SNT) (thread t owns bins [t*R, t*R + R)).  mfun(total) gives the target rank m (< total); the
+// bin b with excl(b) <= m < excl(b) + bins[b] in ascending order is written to sel[0], excl(b) to sel[1].  Integer sums only.
+template <int R, class MF>
+__device__ __forceinline__ void select_bin(const u64* bins, u64* wred, u64* sel, MF&& mfun) {
+    const int tid = threadIdx.x;
+    u64 v[R], local = 0;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        v[j] = bins[tid * R + j];
+        local += v[j];
+    }
+    const u64 inc = wave_incl_scan(local);
+    if ((tid & 63) == 63) wred[tid >> 6] = inc;
+    __syncthreads();
+    u64 total = 0, before = 0;
+#pragma unroll
+    for (int w = 0; w < SNT / 64; ++w) {
+        total += wred[w];
+        before += w < (tid >> 6) ? wred[w] : 0ull;
+    }
+    const u64 m = mfun(total);
+    u64 excl = before + inc - local;
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        if (excl <= m && m < excl + v[j]) {
+            sel[0] = (u64)(tid * R + j);
+            sel[1] = excl;
+        }
+        excl += v[j];
+    }
+    __syncthreads();
+}
+
+// LDS bitmap of the distinct history tokens of row r (RepetitionPenaltyLogitsProcessor gathers from the original scores, so a
+// token that occurs several times is penalised once)
+__device__ __forceinline__ void build_penalty_bits(unsigned* pen_bits, int cols, const long* __restrict__ hist, long hist_ld, int hist_len) {
+    for (int i = threadIdx.x; i < (cols + 31) >> 5; i += SNT) pen_bits[i] = 0u;
+    __syncthreads();
+    const long* h = hist + (long)blockIdx.x * hist_ld;
+    for (int i = threadIdx.x; i < hist_len; i += SNT) {
+        const long id = h[i];
+        if (id >= 0 && id < cols) atomicOr(&pen_bits[id >> 5], 1u << (id & 31));
+    }
+    __syncthreads();
+}
+// the penalised fp32 score of token c: s < 0 ? s * p : s / p for history tokens
+__device__ __forceinline__ float penalised(const unsigned* pen_bits, bool pen, float penalty, int c, bf16_t b) {
+    float s = bf2f(b);
+    if (pen && ((pen_bits[c >> 5] >> (c & 31)) & 1u)) s = s < 0.f ? s * penalty : s / penalty;
+    return s;
+}
+
+// greedy (do_sample = 0): first index of the maximum penalised score, as torch.argmax
+__global__ __launch_bounds__(SNT) void sample_greedy_k(const bf16_t* __restrict__ x, long ld, int cols, const long* __restrict__ hist,
+                                                       long hist_ld, int hist_len, float penalty, long* __restrict__ out,
+                                                       unsigned char* __restrict__ keep_mask) {
+    __shared__ unsigned pen_bits[PEN_MAX_COLS / 32];
+    __shared__ u64 wred[SNT / 64];
+    const int tid = threadIdx.x, r = blockIdx.x;
+    const bf16_t* row = x + (long)r * ld;
+    const bool pen = penalty != 1.0f && hist_len > 0;
+    if (pen) build_penalty_bits(pen_bits, cols, hist, hist_ld, hist_len);
+    u64 best = 0;
+    row_strided(row, cols, ((uintptr_t)row & 15) == 0, [&](int c, bf16_t b) {
+        const u64 k = ((u64)f32_key(penalised(pen_bits, pen, penalty, c, b)) << 32) | (unsigned)(~(unsigned)c);
+        best = k > best ? k : best;
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const u64 ok = __shfl_xor(best, o, 64);
+        best = ok > best ? ok : best;
+    }
+    if ((tid & 63) == 0) wred[tid >> 6] = best;
+    __syncthreads();
+    best = wred[0];
+#pragma unroll
+    for (int w = 1; w < SNT / 64; ++w) best = wred[w] > best ? wred[w] : best;
+    const int pick = (int)(~(unsigned)(best & 0xffffffffu));
+    if (tid == 0) out[r] = pick;
+    if (keep_mask)
+        for (int c = tid; c < cols; c += SNT) keep_mask[(long)r * cols + c] = c == pick ? 1 : 0;
+}
+
+__global__ __launch_bounds__(SNT) void sample_chain_k(const bf16_t* __restrict__ x, long ld, int cols, const long* __restrict__ hist,
+                                                      long hist_ld, int hist_len, float penalty, float temp, int top_k, float top_p,
+                                                      float min_p, unsigned seed_lo, unsigned seed_hi, unsigned step,
+                                                      long* __restrict__ out, unsigned char* __restrict__ keep_mask) {
+    __shared__ u64 bins[SBINS];
+    __shared__ unsigned pen_bits[PEN_MAX_COLS / 32];
+    __shared__ u64 wred[SNT / 64];
+    __shared__ u64 sel[2];
+    const int tid = threadIdx.x, r = blockIdx.x;
+    const bf16_t* row = x + (long)r * ld;
+    const bool vec = ((uintptr_t)row & 15) == 0;
+    const bool pen = penalty != 1.0f && hist_len > 0;
+    if (pen) build_penalty_bits(pen_bits, cols, hist, hist_ld, hist_len);
+    auto score = [&](int c, bf16_t b) -> float { return penalised(pen_bits, pen, penalty, c, b); };
+
+    auto tval = [&](int c, bf16_t b) -> float { return score(c, b) / temp; };   // TemperatureLogitsWarper: an fp32 division
+    const bool do_k = top_k > 0 && top_k < cols;
+    const bool do_p = top_p < 1.0f;
+
+    // pass 0: row maximum (+ the first top-k digit histogram)
+    if (do_k) {
+        for (int i = tid; i < SBINS; i += SNT) bins[i] = 0ull;
+        __syncthreads();
+    }
+    unsigned kmax = 0u;
+    row_strided(row, cols, vec, [&](int c, bf16_t b) {
+        const unsigned k = f32_key(tval(c, b));
+        kmax = k > kmax ? k : kmax;
+        if (do_k) atomicAdd(&bins[k >> 20], 1ull);
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned ok = __shfl_xor(kmax, o, 64);
+        kmax = ok > kmax ? ok : kmax;
+    }
+    if ((tid & 63) == 0) wred[tid >> 6] = kmax;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < SNT / 64; ++w) kmax = (unsigned)wred[w] > kmax ? (unsigned)wred[w] : kmax;
+    const float tmax = key_f32(kmax);
+    auto mass = [&](float t) -> u64 {                            // exp(t - t_max) in 2^-40 units (0 for -inf)
+        return t > -INFINITY ? (u64)(__expf(t - tmax) * MASS_ONE) : 0ull;
+    };
+
+    // TopKLogitsWarper: keep t >= the k-th largest t (ties with it included) = the key of ascending rank cols - k
+    unsigned kthr = 0u;
+    if (do_k) {
+        u64 m = (u64)(cols - top_k);
+        unsigned prefix = 0u;
+        for (int pass = 0; pass < 3; ++pass) {
+            const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
+            if (pass > 0) {
+                bins[tid] = 0ull;
+                __syncthreads();
+                row_strided(row, cols, vec, [&](int c, bf16_t b) {
+                    const unsigned k = f32_key(tval(c, b));
+                    if ((k >> (shift + 10)) == (prefix >> (shift + 10))) atomicAdd(&bins[(k >> shift) & 1023u], 1ull);
+                });
+                __syncthreads();
+                select_bin<1>(bins, wred, sel, [&](u64) { return m; });
+            } else {
+                __syncthreads();
+                select_bin<SBINS / SNT>(bins, wred, sel, [&](u64) { return m; });
+            }
+            prefix |= (unsigned)sel[0] << shift;
+            m -= sel[1];
+            __syncthreads();
+        }
+        kthr = prefix;
+    }
+
+    // TopPLogitsWarper over the top-k survivors: keep key >= the smallest key K whose ascending cumulative mass exceeds
+    // (1 - top_p) * Z; tokens tied with K are all kept
+    unsigned pthr = 0u;
+    if (do_p) {
+        u64 m = 0;
+        unsigned prefix = 0u;
+        for (int pass = 0; pass < 3; ++pass) {
+            const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
+            const int nb = pass == 0 ? SBINS : 1024;
+            for (int i = tid; i < nb; i += SNT) bins[i] = 0ull;
+            __syncthreads();
+            row_strided(row, cols, vec, [&](int c, bf16_t b) {
+                const float t = tval(c, b);
+                const unsigned k = f32_key(t);
+                if (k >= kthr && (pass == 0 || (k >> (shift + 10)) == (prefix >> (shift + 10))))
+                    atomicAdd(&bins[pass == 0 ? (k >> 20) : ((k >> shift) & 1023u)], mass(t));
+            });
+            __syncthreads();
+            if (pass == 0) {
+                select_bin<SBINS / SNT>(bins, wred, sel, [&](u64 total) {
+                    u64 cut = (u64)((1.0 - (double)top_p) * (double)total);
+                    cut = cut < total ? cut : total - 1;                 // the maximum (mass 2^40) is always kept
+                    m = cut;
+                    return cut;
+                });
+            } else {
+                select_bin<1>(bins, wred, sel, [&](u64) { return m; });
+            }
+            prefix |= (unsigned)sel[0] << shift;
+            m -= sel[1];
+            __syncthreads();
+        }
+        pthr = prefix;
+    }
+    const unsigned thr = kthr > pthr ? kthr : pthr;
+
+    // MinPLogitsWarper on the survivors: p_i >= min_p * p_max  <=>  exp(t_i - t_max) >= min_p; then the kept masses per
+    // thread over a contiguous index chunk, so the draw's prefix sum runs in index order
+    auto kept = [&](float t) -> bool { return f32_key(t) >= thr && (min_p <= 0.f || expf(t - tmax) >= min_p); };
+    const int chunk = (((cols + SNT - 1) / SNT) + 7) & ~7;
+    const int c0 = min(cols, tid * chunk), c1 = min(cols, c0 + chunk);
+    u64 mine = 0;
+    row_chunk(row, c0, c1, vec, [&](int c, bf16_t b) {
+        const float t = tval(c, b);
+        const bool keep = kept(t);
+        if (keep) mine += mass(t);
+        if (keep_mask) keep_mask[(long)r * cols + c] = keep ? 1 : 0;
+    });
+    bins[tid] = mine;
+    __syncthreads();
+    u64 target = 0;
+    select_bin<1>(bins, wred, sel, [&](u64 total) {
+        const unsigned u = desta_rng32(seed_lo, seed_hi, ((unsigned long)step << 32) | (unsigned)r);
+        target = (u64)((double)(u >> 8) * (1.0 / 16777216.0) * (double)total);   // < total
+        if (total == 0) sel[0] = 0, sel[1] = 0;                                   // no finite score: token 0 (below)
+        return target;
+    });
+    if (tid == (int)sel[0]) {
+        const u64 rem = target - sel[1];
+        u64 run = 0;
+        int tok = -1;
+        row_chunk(row, c0, c1, vec, [&](int c, bf16_t b) {
+            if (tok >= 0) return;
+            const float t = tval(c, b);
+            if (kept(t)) {
+                run += mass(t);
+                if (run > rem) tok = c;
+            }
+        });
+        out[r] = tok >= 0 ? tok : 0;
+    }
+}
+
+}  // namespace
+
+extern "C" int desta_sample_bf16(const void* logits, int64_t ld, int rows, int cols, const int64_t* hist, int64_t hist_ld, int hist_len,
+                                 float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
+                                 uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream) {
+    DESTA_CHECK_ARG(logits && out && rows > 0 && cols > 0 && ld >= cols, "sample: bad argument");
+    DESTA_CHECK_ARG(temperature > 0.f, "sample: need temperature > 0");
+    DESTA_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "sample: need 0 < top_p <= 1");
+    DESTA_CHECK_ARG(top_k >= 0, "sample: need top_k >= 0");
+    DESTA_CHECK_ARG(min_p >= 0.f && min_p <= 1.f, "sample: need 0 <= min_p <= 1");
+    DESTA_CHECK_ARG(repetition_penalty > 0.f, "sample: need repetition_penalty > 0");
+    DESTA_CHECK_ARG(hist_len >= 0 && (hist_len == 0 || (hist && hist_ld >= hist_len)), "sample: bad token history");
+    DESTA_CHECK_ARG(repetition_penalty == 1.f || hist_len == 0 || cols <= PEN_MAX_COLS,
+                    "sample: a repetition penalty needs cols <= %d", PEN_MAX_COLS);
+    if (!do_sample)
+        hipLaunchKernelGGL(sample_greedy_k, dim3(rows), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
+                           (const long*)hist, (long)hist_ld, hist_len, repetition_penalty, (long*)out, keep_mask);
+    else
+        hipLaunchKernelGGL(sample_chain_k, dim3(rows), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
+                           (const long*)hist, (long)hist_ld, hist_len, repetition_penalty, temperature, top_k, top_p, min_p,
+                           (unsigned)seed, (unsigned)(seed >> 32), step, (long*)out, keep_mask);
+    DESTA_CHECK_LAUNCH("sample");
+    return DESTA_OK;
+}

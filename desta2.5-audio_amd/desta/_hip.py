@@ -582,6 +582,20 @@ def sample_top_p(logits, ld, rows, cols, temperature, top_p, seed, step, out, ke
                   stream()), "desta_sample_top_p_bf16")
 
 
+_sample_chain = _sig("desta_sample_bf16", vp, i64, i32, i32, vp, i64, i32, f32, i32, f32, i32, f32, f32, C.c_uint64, C.c_uint32,
+                     vp, vp, vp)
+
+
+def sample(logits, ld, rows, cols, out, *, do_sample=True, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, repetition_penalty=1.0,
+           hist=None, hist_len=0, seed=0, step=0, keep_mask=None):
+    """One step of HF's logits chain per row of bf16 logits: repetition penalty over the int64 token history hist[:, :hist_len],
+    then argmax (do_sample=False) or temperature -> top-k -> top-p -> min-p -> one draw (include/desta_hip.h desta_sample_bf16)."""
+    hist_ld = 0 if hist is None else hist.stride(0)
+    check(_sample_chain(p(logits), ld, rows, cols, p(hist), hist_ld, hist_len, repetition_penalty, int(bool(do_sample)), temperature,
+                        top_k, top_p, min_p, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, p(out), p(keep_mask), stream()),
+          "desta_sample_bf16")
+
+
 # ----------------------------------------------------------------------------- data-parallel exchange without torch.distributed
 class CommUniqueId(C.Structure):
     _fields_ = [("internal", C.c_char * 128)]

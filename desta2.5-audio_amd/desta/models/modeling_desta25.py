@@ -369,6 +369,45 @@ def rope_inv_freq(c: LLMConfig) -> torch.Tensor:
     return inv.float()
 
 
+# HF 5.15 global defaults of the settings the HIP decode loop honours (TF:generation/configuration_utils.py:609-641; min_p has none)
+_HF_GEN_DEFAULTS = {"do_sample": False, "temperature": 1.0, "top_k": 50, "top_p": 1.0, "min_p": None, "repetition_penalty": 1.0}
+# settings the HIP decode loop cannot honour, with the value that turns each of them off in HF
+_HF_GEN_UNSUPPORTED = {"num_beams": 1, "typical_p": 1.0, "epsilon_cutoff": 0.0, "eta_cutoff": 0.0, "top_h": None,
+                       "no_repeat_ngram_size": 0, "bad_words_ids": None, "suppress_tokens": None}
+
+
+def resolve_generation_kwargs(llm_generation_config: dict, **explicit) -> dict:
+    """The sampling settings HF's `generate` would use (TF:generation/utils.py:1806-1808): an explicit argument, else the
+    checkpoint's `generation_config.json`, else HF's global default (so top_k = 50 unless someone says otherwise).  `None`
+    counts as unset.  Keys other than the sampling settings (max_new_tokens, seed, ...) pass through.  Raises
+    NotImplementedError for any setting this path cannot honour that is set away from HF's default (beam search, typical_p,
+    epsilon / eta cutoffs, top_h, no_repeat_ngram_size, bad_words_ids, suppress_tokens)."""
+    file_cfg = dict(llm_generation_config or {})
+    bad = []
+    for k, off in _HF_GEN_UNSUPPORTED.items():
+        v = explicit.get(k) if explicit.get(k) is not None else file_cfg.get(k)
+        if v is not None and v != off and v != []:
+            bad.append(f"{k}={v!r}")
+    if bad:
+        raise NotImplementedError(f"generation settings not supported by the HIP decode loop: {', '.join(bad)}")
+    out = {k: v for k, v in explicit.items() if k not in _HF_GEN_UNSUPPORTED}
+    for k, default in _HF_GEN_DEFAULTS.items():
+        v = explicit.get(k)
+        out[k] = v if v is not None else (file_cfg[k] if file_cfg.get(k) is not None else default)
+    return out
+
+
+def check_sampling_args(top_k=None, min_p=None, repetition_penalty=None) -> None:
+    """HF's argument checks for the processors behind top_k / min_p / repetition_penalty (TF:generation/logits_process.py
+    RepetitionPenaltyLogitsProcessor, TopKLogitsWarper, MinPLogitsWarper); None means off, top_k = 0 too."""
+    if repetition_penalty is not None and not (isinstance(repetition_penalty, (int, float)) and repetition_penalty > 0):
+        raise ValueError(f"`penalty` has to be a strictly positive float, but is {repetition_penalty}")
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0):
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k}")
+    if min_p is not None and not (isinstance(min_p, (int, float)) and 0 <= min_p <= 1.0):
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+
+
 @dataclass
 class GenerationOutput:
     """modeling_desta25.py:492-496"""
@@ -1702,13 +1741,19 @@ class CausalLMHIP:
     def generate_greedy(self, x0_filler, B: int, S: int, kv_start: torch.Tensor, max_new_tokens: int, pad_token_id: int,
                         eos_token_ids=None, forced_tokens: Optional[torch.Tensor] = None, collect_logits: bool = False,
                         do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0, seed: int = 0, layer_hook=None,
-                        after_prompt=None):
+                        after_prompt=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
+                        repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None):
         """Prompt pass + KV-cached decode (greedy, or temperature / top-p sampling with the library's counter RNG).  Returns new token ids [B, n_new] (int64; finished sequences are
         filled with pad_token_id, generation stops early once every sequence has produced an EOS), and, with
         collect_logits, the per-step logits [n_new, B, V] (bf16).  `forced_tokens` [B, T] teacher-forces the
         continuation (parity tests compare per-step logits with the oracle on the same prefix).  `layer_hook(l, x)` runs behind every
-        decoder layer of the prompt pass ([B*S, h]) and of every decode step ([B, h]); `after_prompt()` between the two."""
+        decoder layer of the prompt pass ([B*S, h]) and of every decode step ([B, h]); `after_prompt()` between the two.
+        top_k / min_p (sampling) and repetition_penalty (both modes) switch to HF's whole processor chain in one kernel
+        (`desta_sample_bf16`); None = off.  The penalty's history is what HF's `input_ids` hold: `prompt_ids` [B, S] (text-only
+        chats, left padding included) followed by the tokens emitted so far, pad_token_id for finished rows."""
         assert max_new_tokens >= 1
+        use_pen = repetition_penalty is not None and float(repetition_penalty) != 1.0
+        chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0)))
         Smax = S + max_new_tokens
         self._gen_alloc(B, Smax)
         dev = self.dev
@@ -1719,6 +1764,13 @@ class CausalLMHIP:
         if after_prompt is not None:
             after_prompt()
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
+        P = 0
+        if chain:                                                            # token history = [prompt ids,] emitted tokens: out is its tail
+            P = 0 if prompt_ids is None else int(prompt_ids.shape[1])
+            hist = torch.full((B, P + max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
+            if P:
+                hist[:, :P] = prompt_ids.to(dev, torch.int64)
+            out = hist[:, P:]
         steps_logits = []
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
@@ -1726,7 +1778,11 @@ class CausalLMHIP:
         for t in range(max_new_tokens):
             if collect_logits:
                 steps_logits.append(logits[:, :self.V].clone())
-            if do_sample:
+            if chain:
+                H.sample(logits, self.Vp, B, self.V, self.g_next, do_sample=do_sample, temperature=float(temperature),
+                         top_k=int(top_k or 0), top_p=float(top_p), min_p=float(min_p or 0.0),
+                         repetition_penalty=float(repetition_penalty) if use_pen else 1.0, hist=hist, hist_len=P + t, seed=seed, step=t)
+            elif do_sample:
                 H.sample_top_p(logits, self.Vp, B, self.V, float(temperature), float(top_p), seed, t, self.g_next)
             else:
                 H.argmax_bf16(logits, self.Vp, B, self.V, self.g_next)
@@ -1864,6 +1920,12 @@ class DeSTA25AudioModel:
             if config.use_lora:
                 self.llm.attach_lora(self.arena, config.lora_r, config.lora_alpha, config.lora_dropout)
             self.orca = OrcaHIP(config, self.connector, self.device) if config.connector_mode == "orca_hybrid" else None
+            # the LLM checkpoint's own generation defaults (read only; `hf_generation_kwargs` applies them on request)
+            gp = os.path.join(str(config.llm_model_id), "generation_config.json")
+            self.llm_generation_config = {}
+            if os.path.isfile(gp):
+                with open(gp) as f:
+                    self.llm_generation_config = json.load(f)
             # Whisper's own decoder, when the checkpoint carries it: generate() then transcribes speech clips that arrive without text
             # itself (modeling_desta25.py:1580-1590) instead of asking for an injected `asr`
             self.asr_decoder = None
@@ -2177,12 +2239,18 @@ class DeSTA25AudioModel:
 
     @torch.no_grad()
     def _generate_step(self, inputs, pad_token_id, temperature=0.7, top_p=0.9, max_new_tokens=512, do_sample=True,
-                       eos_token_id=None, forced_tokens=None, collect_logits=False, seed=0):
+                       eos_token_id=None, forced_tokens=None, collect_logits=False, seed=0, top_k=None, min_p=None,
+                       repetition_penalty=None, prompt_in_history=False):
         """Reference `_generate_step` (modeling_desta25.py:1358-1431): audio features spliced into the prompt
         embeddings, then `llm_model.generate(inputs_embeds=…)` — here the KV-cached decoder on the HIP path.
         Returns ONLY the new tokens, as HF does for inputs_embeds prompts.  do_sample=False: greedy (temperature / top_p
         ignored, as the reference nulls them).  do_sample=True: temperature -> top-p -> one multinomial draw per step
-        with the library's counter RNG (`seed`; same distribution as HF, not torch's random stream)."""
+        with the library's counter RNG (`seed`; same distribution as HF, not torch's random stream).
+        top_k, min_p (sampling only) and repetition_penalty (both modes) add HF's TopK / MinP warpers and its
+        RepetitionPenaltyLogitsProcessor; None = off.  HF's history for the penalty is `input_ids`: empty for an
+        inputs_embeds prompt (only the generated tokens count, TF:generation/utils.py:1176-1181), the prompt ids for a text
+        prompt passed as input_ids (`prompt_in_history=True`, the text-only leg of `generate`)."""
+        check_sampling_args(top_k, min_p, repetition_penalty)
         cfg, dev = self.config, self.device
         input_ids = inputs["context_input_ids"].to(dev)                      # only the context (prompt) part of the batch
         attention_mask = inputs["context_attention_mask"].to(dev)
@@ -2229,9 +2297,17 @@ class DeSTA25AudioModel:
                 return self.llm.generate_greedy(fill, B, S, kv_start, int(max_new_tokens), int(pad_token_id), eos,
                                                 forced_tokens=forced_tokens, collect_logits=collect_logits, do_sample=bool(do_sample),
                                                 temperature=1.0 if temperature is None else float(temperature),
-                                                top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after)
+                                                top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after,
+                                                top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty,
+                                                prompt_ids=input_ids if prompt_in_history else None)
         finally:
             self.training = was_training
+
+    def hf_generation_kwargs(self, **explicit) -> dict:
+        """`resolve_generation_kwargs(self.llm_generation_config, **explicit)`: the settings HF's `generate` would use for this
+        checkpoint.  `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))` samples
+        as the reference does (modeling_desta25.py:1419-1427), top_k from the checkpoint or HF's default 50 included."""
+        return resolve_generation_kwargs(self.llm_generation_config, **explicit)
 
     def _asr_whisper(self, waves) -> List[str]:
         """`perception.whisper.generate(input_features, attention_mask=None, max_new_tokens=128)` + `processor.batch_decode(...,
@@ -2278,11 +2354,17 @@ class DeSTA25AudioModel:
         if asr is not None or not hasattr(self, "asr"):
             self.asr = asr if asr is not None else (self._asr_whisper if getattr(self, "asr_decoder", None) is not None else None)
 
-    def generate(self, messages, temperature=0.7, top_p=0.9, do_sample=True, max_new_tokens=512, seed=0):
+    def generate(self, messages, temperature=0.7, top_p=0.9, do_sample=True, max_new_tokens=512, seed=0, top_k=None, min_p=None,
+                 repetition_penalty=None):
         """The reference's chat-level `generate` (modeling_desta25.py:1491-1721): messages -> audio decode -> log-mel -> placeholder
         expansion of every `<|AUDIO|>` -> left-padded tokenisation, pad-shifted start positions, transcription ids ->
         `_generate_step` -> `GenerationOutput(text, audios, generated_ids)`.  Same messages schema, same errors; the front-end
-        models (tokenizer / VAD / ASR) are injected through `_setup_generation`."""
+        models (tokenizer / VAD / ASR) are injected through `_setup_generation`.  top_k / min_p / repetition_penalty: HF's
+        processors of the same names, None = off (see `_generate_step`).  To sample exactly as the reference's
+        `llm_model.generate` does, with the checkpoint's generation_config.json and HF's defaults (top_k = 50) filled in:
+        `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))`."""
+        check_sampling_args(top_k, min_p, repetition_penalty)
+        extra = dict(top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty)
         from ..trainer.data.simple_dataset import prepare_audio_context_and_start_positions
         from ..utils.audio import AudioSegment
         if not hasattr(self, "tokenizer") or not hasattr(self, "processor"):
@@ -2304,7 +2386,8 @@ class DeSTA25AudioModel:
             inputs = {"context_input_ids": enc["input_ids"], "context_attention_mask": enc["attention_mask"],
                       "context_batch_start_positions": [], "batch_transcription_ids": [], "batch_features": None}
             ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
-                                      do_sample=do_sample, eos_token_id=[tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")], seed=seed)
+                                      do_sample=do_sample, eos_token_id=[tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")], seed=seed,
+                                      prompt_in_history=True, **extra)
             rows = [r.tolist() for r in ids]
             return GenerationOutput(text=tok.batch_decode(rows, skip_special_tokens=True), audios=[], generated_ids=rows)
         waves, need_asr = [], []
@@ -2342,7 +2425,7 @@ class DeSTA25AudioModel:
                   "context_batch_start_positions": [(i, s + pad[i]) for i in range(len(starts)) for s in starts[i]]}
         self._last_generate_inputs = inputs
         ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
-                                  do_sample=do_sample, seed=seed)
+                                  do_sample=do_sample, seed=seed, **extra)
         return GenerationOutput(text=tok.batch_decode(ids, skip_special_tokens=True), audios=list(zip(audios, texts)), generated_ids=ids.tolist())
 
     def _target_rows(self, labels, B: int, S: int, s_major: bool = False):

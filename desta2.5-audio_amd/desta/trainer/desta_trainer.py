@@ -601,7 +601,7 @@ class DeSTA25Trainer:
 
     def _predict_step(self, batch: Dict[str, Any], generation_kwargs: Optional[Dict[str, Any]] = None) -> torch.Tensor:
         """desta_trainer.py:160-189: generate from the context part of the batch; decode when a tokenizer is attached."""
-        gk = dict(temperature=0.7, top_p=0.9, max_new_tokens=128, do_sample=False)
+        gk = dict(temperature=0.7, top_p=0.9, max_new_tokens=128, do_sample=False, top_k=None, min_p=None, repetition_penalty=None)
         cfg_gk = getattr(getattr(self.cfg, "model", None), "generation_kwargs", None) if self.cfg is not None else None
         for src in (cfg_gk, generation_kwargs):
             if src:
@@ -611,7 +611,8 @@ class DeSTA25Trainer:
         pad_id = eos_id if eos_id is not None else 0
         ids = self.model._generate_step(batch, pad_token_id=pad_id, temperature=gk["temperature"], top_p=gk["top_p"],
                                         max_new_tokens=gk["max_new_tokens"], do_sample=gk["do_sample"],
-                                        seed=self.global_step)
+                                        seed=self.global_step, top_k=gk["top_k"], min_p=gk["min_p"],
+                                        repetition_penalty=gk["repetition_penalty"])
         metas = batch.get("metadata") or [{} for _ in range(ids.shape[0])]
         if tok is not None:
             ctx = batch["context_input_ids"].clone()

@@ -455,6 +455,28 @@ int desta_argmax_bf16(const void* x, int64_t ld, int rows, int cols, int64_t* ou
 int desta_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int cols, float temperature, float top_p,
                             uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream);
 
+/* One decode step of HF's whole logits chain, one launch, one 1024-thread block per bf16 row (`rows` x `cols`, stride ld):
+ * the decode loop of `llm_model.generate(inputs_embeds=…)` (modeling_desta25.py:1419-1427) and of `llm_model.generate(input_ids)`
+ * for text-only chats (modeling_desta25.py:1703-1711), with HF's processors in HF's order (TF:generation/utils.py:1175,
+ * 1296-1330), each on the fp32 value of the logit (TF:generation/utils.py:2894):
+ *   1. RepetitionPenaltyLogitsProcessor: every DISTINCT token of row r's history hist[r*hist_ld + 0 .. hist_len) gets
+ *      s < 0 ? s * p : s / p once (ids outside [0, cols) are ignored); p == 1 or hist_len == 0: off.  Greedy mode too.
+ *   2. do_sample == 0: out[r] = first index of the maximum penalised score (torch.argmax); nothing below applies.
+ *   3. TemperatureLogitsWarper: t = s / T (fp32 division).
+ *   4. TopKLogitsWarper: keep t >= the k-th largest t (ties with it kept); top_k == 0 or >= cols: off.
+ *   5. TopPLogitsWarper on the top-k survivors: token i is kept iff the softmax mass of the kept tokens not more probable
+ *      than i exceeds 1 - top_p; ties with the boundary are kept; top_p == 1: off.
+ *   6. MinPLogitsWarper: keep exp(t_i - t_max) >= min_p (= p_i >= min_p * p_max); min_p == 0: off.
+ *   7. one draw per row from the kept masses (index-order prefix sum) with desta_rng32(seed, (step << 32) | row), the
+ *      counter of desta_sample_top_p_bf16.
+ * Sums are fixed point (2^-40 of the row maximum's mass), so results are deterministic per (seed, step, row).
+ * keep_mask (optional, uint8 [rows, cols]) exports the kept set (greedy: the pick).  DESTA_EINVAL unless T > 0,
+ * 0 < top_p <= 1, top_k >= 0, 0 <= min_p <= 1, repetition_penalty > 0, hist_len >= 0 (hist != NULL and hist_ld >= hist_len
+ * when hist_len > 0), and cols <= 262144 when the penalty is active. */
+int desta_sample_bf16(const void* logits, int64_t ld, int rows, int cols, const int64_t* hist, int64_t hist_ld, int hist_len,
+                      float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
+                      uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream);
+
 /* desta_rope (forward) on a fused q|k|v projection [rows, ld] that ALSO appends the rotated K heads and the V heads of
  * row (b, s) to a KV cache slab: kv_cache + b*kv_batch_stride + (slot0 + s)*kv_row_stride, K heads then V heads.
  * This is what `DynamicCache.update` does inside `llm_model.generate` (modeling_desta25.py:1419) for the prompt

@@ -3,6 +3,8 @@ decode on one MI355X.  Reports prompt ms, ms per generated token (whole batch), 
 rate of the decode GEMMs (bytes of frozen LLM weights read per token / token time; HBM peak ~8 TB/s).
 
   python tools/decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 8] [--ctx 64] [--prompt-tail 16] [--new 64]
+                               [--do-sample --temperature T --top-p P --top-k K --min-p M --repetition-penalty R]
+Without --do-sample the decode is greedy (with --repetition-penalty, through the full-chain sampler kernel).
 """
 import argparse
 import json
@@ -22,7 +24,15 @@ def main():
     ap.add_argument("--prompt-tail", type=int, default=16, help="text tokens after the audio span")
     ap.add_argument("--new", type=int, default=64)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--do-sample", action="store_true")
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--min-p", type=float, default=None)
+    ap.add_argument("--repetition-penalty", type=float, default=None)
     a = ap.parse_args()
+    gen = dict(do_sample=a.do_sample, temperature=a.temperature, top_p=a.top_p, top_k=a.top_k, min_p=a.min_p,
+               repetition_penalty=a.repetition_penalty)
     from desta.models.modeling_desta25 import DeSTA25AudioModel, DeSTA25Config
     from desta.synthetic import FULL_CONFIGS, RandomWeights, synthetic_inputs, synthetic_waveform
     from desta import _hip as H
@@ -42,7 +52,7 @@ def main():
         for _ in range(a.repeat):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            ids = model._generate_step(inputs, pad_token_id=0, max_new_tokens=new, do_sample=False, eos_token_id=[])
+            ids = model._generate_step(inputs, pad_token_id=0, max_new_tokens=new, eos_token_id=[], **gen)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             best = dt if best is None else min(best, dt)
@@ -54,7 +64,9 @@ def main():
     per_layer = (c.num_attention_heads + 2 * c.num_key_value_heads) * c.head_dim * c.hidden_size + c.num_attention_heads * c.head_dim * c.hidden_size \
         + 3 * c.hidden_size * c.intermediate_size
     wbytes = 2 * (c.num_hidden_layers * per_layer + c.vocab_size * c.hidden_size)
-    print(json.dumps({"workload": f"{a.config} generate B={B} prompt={S} new={a.new}", "prompt_ms": round(prompt_ms, 2),
+    mode = "sample " + " ".join(f"{k}={v}" for k, v in gen.items() if k != "do_sample" and v is not None) if a.do_sample else \
+        ("greedy" + (f" repetition_penalty={a.repetition_penalty}" if a.repetition_penalty is not None else ""))
+    print(json.dumps({"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "prompt_ms": round(prompt_ms, 2),
                       "ms_per_token_step": round(tok_ms, 3), "tokens_per_s": round(B / tok_ms * 1e3, 1),
                       "weight_bytes_per_step": wbytes, "weight_stream_GBps": round(wbytes / tok_ms / 1e6, 1),
                       "hbm_peak_GBps": 8000}))
