@@ -9,6 +9,11 @@ tokens): log-mel -> Whisper-large-v3 encoder -> Q-Former 6L -> projector -> spli
 CE -> backward (dX through the LLM, dW+dX through the connector) -> mean all-reduce of the flat
 gradient arena over RCCL (N>1) -> global-norm clip -> Adafactor -> LR schedule.  Inputs (waveforms,
 token ids) are resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write --dump-outputs, print
+the line.  --full adds everything else the bench measures: the box calibration before the warm-up, the untimed
+un-overlapped kernel pass after the timed region (`roofline`), the stored PyTorch-ROCm reference point and the CPU
+baselines (minutes on the host cores).
 """
 import argparse
 import json
@@ -275,12 +280,15 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cpu-full-step", action="store_true", help="only: one real full-depth B=1 oracle step on the host cores (minutes)")
-    ap.add_argument("--no-kernel-pass", action="store_true", help="skip the untimed per-kernel HBM / attention event pass")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: box calibration, the untimed kernel pass (roofline), the PyTorch-ROCm reference "
+                         "point and the CPU baselines (off by default: a plain run does the timed steps and prints their line)")
+    ap.add_argument("--no-kernel-pass", action="store_true", help="--full: skip the untimed per-kernel HBM / attention event pass")
     ap.add_argument("--config", default="desta25_llama31-8B_Qformer6L")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--ctx", type=int, default=64)
     ap.add_argument("--tgt", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--encoder-overlap", action=argparse.BooleanOptionalAction, default=True,
                     help="next batch's frozen Whisper forward on its own HIP stream beside the LLM (default on; --no-encoder-overlap: at the end of the step on the main stream)")
@@ -298,7 +306,7 @@ def main():
     ap.add_argument("--small-gemm-ring", type=int, default=None, help="A/B: option 6 of desta_gemm_set_option (0 = the 128x128 GEMM never takes its four-slot ring form, 1 = default, 2 = always)")
     ap.add_argument("--splitk-inkernel", action="store_true", help="A/B: reduce the K-slices of tail tiles inside the GEMM launch (scattered, ticketed) instead of by the fix-up launch")
     ap.add_argument("--launch-check", action="store_true", help="plumbing only: rendezvous + one all-reduce of the N ranks, no device work (CPU test of the self-launch path)")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the box_calibration block (fixed GEMM / copy workloads before the timed region)")
+    ap.add_argument("--no-calibration", action="store_true", help="--full: skip the box_calibration block (fixed GEMM / copy workloads before the timed region)")
     ap.add_argument("--no-rope-fusion", action="store_true", help="A/B: rotary embedding as its own kernel (forward and backward) instead of inside the q|k|v GEMM epilogue / attention-backward stores")
     ap.add_argument("--attn-r2-backward", action="store_true", help="A/B: attention backward on round 2's kernels (separate delta, 4-wave dQ beside dK/dV); implies --no-rope-fusion")
     ap.add_argument("--attn-r2-forward", action="store_true", help="A/B: attention forward AND backward on round 2's 4-wave kernels; implies --no-rope-fusion")
@@ -500,7 +508,7 @@ def main():
         _main.wait_stream(torch.cuda.current_stream(dev))
         torch.cuda.set_stream(_main)
     calib = None
-    if rank == 0 and not a.no_calibration:
+    if a.full and rank == 0 and not a.no_calibration:
         calib = box_calibration(H, dev)
     fence()
     run(a.warmup, 0)
@@ -523,7 +531,7 @@ def main():
     # duration reads long for a step that is SHORTER; the timed region above keeps every overlap (steps/s is the metric), the
     # per-kernel rates come from here (a kernel alone on the device, in situ: same operands, same cache state as in the step).
     prof, kprof, kp_steps = {}, {}, 3
-    if not a.no_kernel_pass:                             # every rank steps (the all-reduce is collective); rank 0 records
+    if a.full and not a.no_kernel_pass:                  # every rank steps (the all-reduce is collective); rank 0 records
         saved = (trainer._side, trainer._enc_stream, model.connector.kv_side, model.connector.overlap_dw)
         trainer.wait_update()
         torch.cuda.synchronize()
@@ -538,10 +546,6 @@ def main():
             prof = H.gemm_profile_stop(by_kernel=True)
         trainer._side, trainer._enc_stream, model.connector.kv_side, model.connector.overlap_dw = saved
     fence()
-    n_launch, flops, gemm_ms = prof.get(2, (0, 0.0, 0.0))                 # the dominant kernel: gemm_bf16_nt_256_kernel
-    n_other = sum(v[0] for k, v in prof.items() if k != 2)
-    ms_other = sum(v[2] for k, v in prof.items() if k != 2)
-    flops_other = sum(v[1] for k, v in prof.items() if k != 2)
     if dist.is_initialized():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -549,50 +553,9 @@ def main():
     final_loss = float(loss)
 
     if rank == 0:
-        achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        # L2-boundary bytes per launch of the dominant kernel: from separate rocprofv3 --pmc passes of this same command, committed
-        # under profiles/ (FETCH_SIZE doubled for gfx950 as MI355X_MICROARCH.md prescribes) — a STORED record, not a counter of
-        # this run (hardware counters need the profiler around the process); null if absent
-        traffic, traffic_src = None, None
-        tpath = next((pth for pth in (os.path.join(ROOT, "profiles", f) for f in ("r04_gemm_hbm_traffic.json", "r03_gemm_hbm_traffic.json",
-                                                                                    "r02_gemm_hbm_traffic.json")) if os.path.isfile(pth)), "")
-        if a.config == "desta25_llama31-8B_Qformer6L" and os.path.isfile(tpath):
-            with open(tpath) as f:
-                tj = json.load(f)
-            traffic = tj["fetch_bytes_per_launch"] + tj["write_bytes_per_launch"]
-            traffic_src = {"measured_in_this_run": False, "file": os.path.relpath(tpath, ROOT),
-                           "what": "TCC FETCH_SIZE x 2 + WRITE_SIZE per launch (L2 boundary: Infinity-Cache hits included), separate --pmc passes",
-                           "hbm_side": {k: tj[k] for k in ("dram_read_bytes_per_launch", "dram_read_counter", "hbm_read_fraction_of_fetch") if k in tj} or None}
         ms_step = 1e3 * elapsed / a.steps
-        # reference point measured on the same hardware with tools/hf_step_bench.py (the step composed from stock PyTorch-ROCm /
-        # transformers modules, as the reference composes it); NOT `vs_baseline` (BASELINE.md publishes no number for this metric)
-        torch_ref = None
-        rpath = os.path.join(ROOT, "profiles", "r04_hf_pytorch_step.json")
-        if not os.path.isfile(rpath):
-            rpath = os.path.join(ROOT, "profiles", "r02_hf_pytorch_step.json")
-        if a.config == "desta25_llama31-8B_Qformer6L" and world == 1 and os.path.isfile(rpath):
-            with open(rpath) as f:
-                torch_ref = json.load(f)
-            torch_ref["speedup_of_this_run"] = torch_ref["ms_per_step"] / ms_step
-            torch_ref["measured_in_this_run"] = False
-            torch_ref["note"] = (f"stored constant: tools/hf_step_bench.py measured once ({torch_ref.get('log')}; round 4: in the same lease as "
-                                 "profiles/r04_bench_driver_cmd.log, a box of gate_up calibration 1355 TFLOP/s where this bench ran 154.7 ms); only the "
-                                 "ratio uses this run's ms_per_step")
         mean_ps = sum(per_step) / max(1, len(per_step))
         sd_ps = (sum((x - mean_ps) ** 2 for x in per_step) / max(1, len(per_step) - 1)) ** 0.5
-        # executed FLOP per step: every GEMM launch of a step (HIP-event records carry 2MNK) + the attention kernels'
-        # MFMA FLOP (4 Sq Sk D per head forward, x2.5 backward, halved under the causal mask), both from the un-overlapped pass
-        attn = {t: v for t, v in kprof.items() if t.startswith("attn_")}
-        attn_flop_step = sum(v[1] for v in attn.values()) / kp_steps
-        gemm_flop_step = (flops + flops_other) / kp_steps
-        exec_flop = gemm_flop_step + attn_flop_step
-        hbm_kernels = {t: {"calls_per_step": v[0] / kp_steps, "algorithmic_GB_per_step": v[1] / kp_steps / 1e9, "ms_per_step": v[2] / kp_steps,
-                           "GBps": v[1] / (v[2] * 1e-3) / 1e9 if v[2] > 0 else 0.0, "frac_of_hbm_peak": (v[1] / (v[2] * 1e-3) / 1e9 / HBM_PEAK_GBS) if v[2] > 0 else 0.0}
-                       for t, v in sorted(kprof.items()) if not t.startswith("attn_")}
-        attn_kernels = {t: {"calls_per_step": v[0] / kp_steps, "GFLOP_per_call": v[1] / max(v[0], 1) / 1e9, "us_per_call": 1e3 * v[2] / max(v[0], 1),
-                            "TFLOPs": v[1] / (v[2] * 1e-3) / 1e12 if v[2] > 0 else 0.0,
-                            "frac_of_mfma_peak": (v[1] / (v[2] * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS) if v[2] > 0 else 0.0}
-                        for t, v in sorted(attn.items())}
         overlaps = []
         if not a.no_overlap:
             overlaps.append("all-reduce + clip + Adafactor + weight re-cast of step t on a side stream")
@@ -630,34 +593,81 @@ def main():
                                               "(rows whose logits the loss ignores / whose gradient nothing consumes are not computed; "
                                               "loss and every parameter gradient identical to the full grid, tests/test_gpu_model.py)")},
             "final_loss": final_loss,
-            "box_calibration": calib,
-            "pytorch_rocm_reference_point": torch_ref,
-            "roofline": {"bound": "mfma", "kernel": "gemm_bf16_nt_256_kernel", "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "measured_in": (f"untimed pass of {kp_steps} steps right after the timed region with every side stream OFF (a kernel's HIP-event "
-                                         "duration beside another stream includes the time-sharing); the timed region runs WITH the overlaps"),
-                         # in-situ rate of the dominant kernel / the same kernel alone on this box right before the run (gate_up shape)
-                         "frac_normalised": (achieved / calib["gemm_gate_up_tflops"]) if calib and achieved > 0 else None,
-                         "launches_per_step": n_launch / kp_steps, "avg_launch_us": 1e3 * gemm_ms / max(n_launch, 1),
-                         "flop_per_launch": flops / max(n_launch, 1), "gemm_ms_per_step": gemm_ms / kp_steps,
-                         "other_gemm_kernels": {"launches_per_step": n_other / kp_steps, "ms_per_step": ms_other / kp_steps,
-                                                "tflops": (flops_other / (ms_other * 1e-3) / 1e12) if ms_other > 0 else 0.0,
-                                                "note": "gemm_bf16_nt_kernel family (128x128 and the connector's small-GEMM kernels, incl. transposed-storage dW)"},
-                         # the WHOLE step against the same peak: executed FLOP (GEMMs + attention MFMA work; the fast path skips
-                         # lm_head rows without a target and the backward in front of the first audio span) / wall time of the TIMED region
-                         "whole_step": {"executed_flop_per_step": exec_flop, "gemm_flop_per_step": gemm_flop_step,
-                                        "attention_flop_per_step": attn_flop_step, "achieved": exec_flop / (ms_step * 1e-3) / 1e12,
-                                        "frac": exec_flop / (ms_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-                                        "reference_flop_per_step": 1.82e14,
-                                        "frac_on_reference_flop": 1.82e14 / (ms_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS
-                                        if a.config.startswith("desta25_llama31-8B") and (B, a.ctx, a.tgt) == (8, 64, 512) else None},
-                         # HBM-bound kernels of the step: ALGORITHMIC bytes / HIP-event time of the same untimed pass, vs 8 TB/s
-                         "hbm_kernels": hbm_kernels, "attention_kernels": attn_kernels},
         }
+        if a.full:
+            n_launch, flops, gemm_ms = prof.get(2, (0, 0.0, 0.0))             # the dominant kernel: gemm_bf16_nt_256_kernel
+            n_other = sum(v[0] for k, v in prof.items() if k != 2)
+            ms_other = sum(v[2] for k, v in prof.items() if k != 2)
+            flops_other = sum(v[1] for k, v in prof.items() if k != 2)
+            achieved = flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+            # L2-boundary bytes per launch of the dominant kernel: from separate rocprofv3 --pmc passes of this same command, committed
+            # under profiles/ (FETCH_SIZE doubled: gfx950 tallies a 128-byte request as 64 B) — a STORED record, not a counter of
+            # this run (hardware counters need the profiler around the process); null if absent
+            traffic, traffic_src = None, None
+            tpath = next((pth for pth in (os.path.join(ROOT, "profiles", f) for f in ("r04_gemm_hbm_traffic.json", "r03_gemm_hbm_traffic.json",
+                                                                                        "r02_gemm_hbm_traffic.json")) if os.path.isfile(pth)), "")
+            if a.config == "desta25_llama31-8B_Qformer6L" and os.path.isfile(tpath):
+                with open(tpath) as f:
+                    tj = json.load(f)
+                traffic = tj["fetch_bytes_per_launch"] + tj["write_bytes_per_launch"]
+                traffic_src = {"measured_in_this_run": False, "file": os.path.relpath(tpath, ROOT),
+                               "what": "TCC FETCH_SIZE x 2 + WRITE_SIZE per launch (L2 boundary: Infinity-Cache hits included), separate --pmc passes",
+                               "hbm_side": {k: tj[k] for k in ("dram_read_bytes_per_launch", "dram_read_counter", "hbm_read_fraction_of_fetch") if k in tj} or None}
+            # reference point measured on the same hardware with tools/hf_step_bench.py (the step composed from stock PyTorch-ROCm /
+            # transformers modules, as the reference composes it); NOT `vs_baseline` (BASELINE.md publishes no number for this metric)
+            torch_ref = None
+            rpath = os.path.join(ROOT, "profiles", "r04_hf_pytorch_step.json")
+            if not os.path.isfile(rpath):
+                rpath = os.path.join(ROOT, "profiles", "r02_hf_pytorch_step.json")
+            if a.config == "desta25_llama31-8B_Qformer6L" and world == 1 and os.path.isfile(rpath):
+                with open(rpath) as f:
+                    torch_ref = json.load(f)
+                torch_ref["speedup_of_this_run"] = torch_ref["ms_per_step"] / ms_step
+                torch_ref["measured_in_this_run"] = False
+                torch_ref["note"] = (f"stored constant: tools/hf_step_bench.py measured once ({torch_ref.get('log')}; round 4: in the same lease as "
+                                     "profiles/r04_bench_driver_cmd.log, a box of gate_up calibration 1355 TFLOP/s where this bench ran 154.7 ms); only the "
+                                     "ratio uses this run's ms_per_step")
+            # executed FLOP per step: every GEMM launch of a step (HIP-event records carry 2MNK) + the attention kernels'
+            # MFMA FLOP (4 Sq Sk D per head forward, x2.5 backward, halved under the causal mask), both from the un-overlapped pass
+            attn = {t: v for t, v in kprof.items() if t.startswith("attn_")}
+            attn_flop_step = sum(v[1] for v in attn.values()) / kp_steps
+            gemm_flop_step = (flops + flops_other) / kp_steps
+            exec_flop = gemm_flop_step + attn_flop_step
+            hbm_kernels = {t: {"calls_per_step": v[0] / kp_steps, "algorithmic_GB_per_step": v[1] / kp_steps / 1e9, "ms_per_step": v[2] / kp_steps,
+                               "GBps": v[1] / (v[2] * 1e-3) / 1e9 if v[2] > 0 else 0.0, "frac_of_hbm_peak": (v[1] / (v[2] * 1e-3) / 1e9 / HBM_PEAK_GBS) if v[2] > 0 else 0.0}
+                           for t, v in sorted(kprof.items()) if not t.startswith("attn_")}
+            attn_kernels = {t: {"calls_per_step": v[0] / kp_steps, "GFLOP_per_call": v[1] / max(v[0], 1) / 1e9, "us_per_call": 1e3 * v[2] / max(v[0], 1),
+                                "TFLOPs": v[1] / (v[2] * 1e-3) / 1e12 if v[2] > 0 else 0.0,
+                                "frac_of_mfma_peak": (v[1] / (v[2] * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS) if v[2] > 0 else 0.0}
+                            for t, v in sorted(attn.items())}
+            out["box_calibration"] = calib
+            out["pytorch_rocm_reference_point"] = torch_ref
+            out["roofline"] = {
+                "bound": "mfma", "kernel": "gemm_bf16_nt_256_kernel", "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS,
+                "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                "measured_in": (f"untimed pass of {kp_steps} steps right after the timed region with every side stream OFF (a kernel's HIP-event "
+                                "duration beside another stream includes the time-sharing); the timed region runs WITH the overlaps"),
+                # in-situ rate of the dominant kernel / the same kernel alone on this box right before the run (gate_up shape)
+                "frac_normalised": (achieved / calib["gemm_gate_up_tflops"]) if calib and achieved > 0 else None,
+                "launches_per_step": n_launch / kp_steps, "avg_launch_us": 1e3 * gemm_ms / max(n_launch, 1),
+                "flop_per_launch": flops / max(n_launch, 1), "gemm_ms_per_step": gemm_ms / kp_steps,
+                "other_gemm_kernels": {"launches_per_step": n_other / kp_steps, "ms_per_step": ms_other / kp_steps,
+                                       "tflops": (flops_other / (ms_other * 1e-3) / 1e12) if ms_other > 0 else 0.0,
+                                       "note": "gemm_bf16_nt_kernel family (128x128 and the connector's small-GEMM kernels, incl. transposed-storage dW)"},
+                # the WHOLE step against the same peak: executed FLOP (GEMMs + attention MFMA work; the fast path skips
+                # lm_head rows without a target and the backward in front of the first audio span) / wall time of the TIMED region
+                "whole_step": {"executed_flop_per_step": exec_flop, "gemm_flop_per_step": gemm_flop_step,
+                               "attention_flop_per_step": attn_flop_step, "achieved": exec_flop / (ms_step * 1e-3) / 1e12,
+                               "frac": exec_flop / (ms_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS,
+                               "reference_flop_per_step": 1.82e14,
+                               "frac_on_reference_flop": 1.82e14 / (ms_step * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS
+                               if a.config.startswith("desta25_llama31-8B") and (B, a.ctx, a.tgt) == (8, 64, 512) else None},
+                # HBM-bound kernels of the step: ALGORITHMIC bytes / HIP-event time of the same untimed pass, vs 8 TB/s
+                "hbm_kernels": hbm_kernels, "attention_kernels": attn_kernels}
         if prof_timed is not None:                                        # --timed-gemm-events: the rounds-1-3 bookkeeping, for comparison
             n2, f2, m2 = prof_timed.get(2, (0, 0.0, 0.0))
-            out["roofline"]["in_timed_region_with_overlaps"] = {"achieved": f2 / (m2 * 1e-3) / 1e12 if m2 > 0 else 0.0, "gemm_ms_per_step": m2 / a.steps,
-                                                                 "launches_per_step": n2 / a.steps}
+            out.setdefault("roofline", {})["in_timed_region_with_overlaps"] = {
+                "achieved": f2 / (m2 * 1e-3) / 1e12 if m2 > 0 else 0.0, "gemm_ms_per_step": m2 / a.steps, "launches_per_step": n2 / a.steps}
         if comm is not None:
             # data-parallel exchange of the timed region (rank 0's events): the flat fp32 gradient arena, one collective per step
             ar = [x.elapsed_time(y) for kind, x, y in comm if kind == "allreduce"]
@@ -669,10 +679,11 @@ def main():
             out["wait_update_stall_ms"] = sum(st) / max(1, len(st))        # main stream idle in front of the connector forward, waiting for the side-stream tail (connector backward + all-reduce + Adafactor + re-cast) of the previous step
             out["comm_hidden"] = bool(st) and out["wait_update_stall_ms"] < 0.05
             out["comm_backend"] = dist.get_backend() if dist.is_initialized() else None
-        if cfg.connector_mode == "orca_hybrid" and not a.no_cpu_baseline:
+        cpu_legs = a.full and not a.no_cpu_baseline
+        if cfg.connector_mode == "orca_hybrid" and cpu_legs:
             out["cpu_baseline"] = {"value": None, "unit": "steps/s", "cores": 0, "kind": "port",
                                    "sample": "not timed for the ORCA-hybrid side configs (the host leg restates the qformer_1 headline step)"}
-        elif not a.no_cpu_baseline and world == 1:
+        elif cpu_legs and world == 1:
             del trainer, model                                            # the host legs below need none of it
             torch.cuda.empty_cache()
             try:

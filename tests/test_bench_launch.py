@@ -1,6 +1,7 @@
 """bench.py launch contract: `python bench.py --gpus N` with N > 1 outside torchrun either launches N ranks
 itself (fresh `torch.distributed.run` child, before any GPU call) or exits non-zero — it never prints a line for fewer ranks."""
 import json
+import math
 import os
 import subprocess
 import sys
@@ -118,3 +119,25 @@ def test_two_rank_bench_on_one_card_reports_the_exchange(tmp_path):
     assert abs(float(loss[0]) - line["final_loss"]) < 1e-6 * max(1.0, abs(line["final_loss"]))
     assert params.shape == grads.shape == (1 << 22,) and np.isfinite(params).all() and np.isfinite(grads).all()
     assert np.count_nonzero(grads) > 0.9 * grads.size
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only_and_full_adds_the_legs():
+    """A plain run times the steps and prints their line without the legs that take work of their own; --full (CPU baselines
+    left out here: minutes on the host) adds the box calibration, the un-overlapped kernel pass and the reference point."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        p = subprocess.run(cmd + extra, env=ENV, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines[name] = _json_line(p.stdout)
+    for line in lines.values():
+        assert line["unit"] == "steps/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+        assert line["steps"] == 2 and line["warmup"] == 1 and len(line["ms_per_step_each"]) == 2
+        assert abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 and math.isfinite(line["final_loss"])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["metric"] == full["metric"] and plain["final_loss"] == full["final_loss"]      # the same steps, legs outside them
+    assert not {"box_calibration", "roofline", "pytorch_rocm_reference_point", "cpu_baseline"} & set(plain)
+    assert full["box_calibration"]["gemm_gate_up_tflops"] > 0 and full["pytorch_rocm_reference_point"]["speedup_of_this_run"] > 0
+    assert full["roofline"]["achieved"] > 0 and full["roofline"]["launches_per_step"] > 0 and full["roofline"]["hbm_kernels"]
+    assert "cpu_baseline" not in full

@@ -1,5 +1,5 @@
 """Per-step kernel-time breakdown from a rocprofv3 kernel trace of bench.py (steady-state steps only).
-  rocprofv3 --kernel-trace --output-format csv -d DIR -o tr -- python bench.py --steps 6 --warmup 2 --no-cpu-baseline
+  rocprofv3 --kernel-trace --output-format csv -d DIR -o tr -- python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline
   python tools/step_breakdown.py DIR/tr_kernel_trace.csv [out.csv]
 Steps are delimited by the Adafactor update kernel (`af_stats`, one launch per step); the first 3 and the last delimited
 intervals are dropped (warm-up / teardown)."""
