@@ -304,6 +304,7 @@ __global__ void local_mix_bwd_fin_k(const float* __restrict__ part, int nblk, co
 // gradient of coef * sum_{b,i,j} (xhat_i . yhat_j - [identity and i == j])^2 w.r.t. the UN-normalised rows of x:
 //   v = mult * coef * sum_j 2 s_ij yhat_j   (mult = 2 for the symmetric x == y case, where row i also appears as a y),
 //   dx_i += (v - (v . xhat_i) xhat_i) / ||x_i||.      One block per (b, i); rows of x / y / dx are picked through optional index lists.
+//   Below F.normalize's eps the row is x / eps, a plain scaling: dx_i += v / eps, nothing is projected out.
 __global__ __launch_bounds__(256) void sim_loss_bwd_k(const bf16_t* __restrict__ x, const int* __restrict__ xidx, long x_rows, const bf16_t* __restrict__ y,
                                                       const int* __restrict__ yidx, long y_rows, int Nx, int Ny, int H, int identity, float coef,
                                                       float* __restrict__ dx) {
@@ -314,7 +315,8 @@ __global__ __launch_bounds__(256) void sim_loss_bwd_k(const bf16_t* __restrict__
     const bf16_t* xr = x + xr_ * H;
     float q = 0.f;
     for (int k = threadIdx.x; k < H; k += 256) { const float v = bf2f(xr[k]); q += v * v; }
-    const float xn = fmaxf(sqrtf(block_sum(q, sh)), 1e-12f);
+    const float xraw = sqrtf(block_sum(q, sh)), xn = fmaxf(xraw, 1e-12f);
+    const float proj = xraw >= 1e-12f ? 1.0f : 0.0f;
     for (int j = 0; j < Ny; ++j) {
         const bf16_t* yr = y + ((long)b * y_rows + (yidx ? yidx[j] : j)) * H;
         float d = 0.f, n2 = 0.f;
@@ -330,7 +332,7 @@ __global__ __launch_bounds__(256) void sim_loss_bwd_k(const bf16_t* __restrict__
         for (int j = 0; j < Ny; ++j) v += sij[j] * bf2f(y[((long)b * y_rows + (yidx ? yidx[j] : j)) * H + k]) / ynorm[j];
         vdot += v * bf2f(xr[k]) / xn;
     }
-    vdot = block_sum(vdot, sh);
+    vdot = proj * block_sum(vdot, sh);
     for (int k = threadIdx.x; k < H; k += 256) {
         float v = 0.f;
         for (int j = 0; j < Ny; ++j) v += sij[j] * bf2f(y[((long)b * y_rows + (yidx ? yidx[j] : j)) * H + k]) / ynorm[j];

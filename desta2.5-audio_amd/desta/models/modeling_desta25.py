@@ -1040,6 +1040,17 @@ class OrcaHIP:
         self.conv_w = None
         self.B = 0
         self._tb: Dict[tuple, torch.Tensor] = {}
+        self._lidx: Dict[int, torch.Tensor] = {}
+
+    def local_index(self, Tl: int) -> Optional[torch.Tensor]:
+        """Rows of the local tokens the global / local orthogonality loss reads: all of them up to 100, else the reference's uniform
+        sample of 100 (:1190-1194), built like the reference's (`torch.linspace(..., dtype=torch.long, device=l_norm.device)`) on the
+        device, once per Tl, int32.  Shared by `losses` and `backward_tail`."""
+        if Tl <= 100:
+            return None
+        if Tl not in self._lidx:
+            self._lidx[Tl] = torch.linspace(0, Tl - 1, 100, dtype=torch.long, device=self.dev).to(torch.int32)
+        return self._lidx[Tl]
 
     def refresh_weights(self) -> None:
         """bf16 operand of the Conv1d as an im2col GEMM: [out, in, k] -> [out, k * in] (tap-major rows of the padded token stream)."""
@@ -1320,10 +1331,8 @@ class OrcaHIP:
         if loc16 is None:                                                        # orca_local_enabled = False: only the global branch is left
             con.backward((self.dglobal32 + d_af.float()).to(BF16))
             return
-        idx, ny = None, Tl
-        if Tl > 100:
-            idx = torch.linspace(0, Tl - 1, 100, dtype=torch.long).to(dev, torch.int32)
-            ny = 100
+        idx = self.local_index(Tl)
+        ny = Tl if idx is None else idx.numel()
         assert ny <= 128
         co = cfg.orca_ortho_weight_qformer_local / (B * Kg * ny)
         H.orca_sim_loss_bwd(g16, None, Kg, loc16, idx, Tl, B, Kg, ny, h, False, co, self.dglobal32)
@@ -1363,10 +1372,8 @@ class OrcaHIP:
         out["L_ortho_diversity"] = cfg.orca_ortho_diversity_weight * part.sum() / (B * Kg * Kg)
         if local16 is not None:
             Tl = local16.shape[0] // B
-            idx, ny = None, Tl
-            if Tl > 100:                                                          # uniform sample of 100 local tokens (:1190-1194)
-                idx = torch.linspace(0, Tl - 1, 100, dtype=torch.long).to(dev, torch.int32)
-                ny = 100
+            idx = self.local_index(Tl)                                            # uniform sample of 100 local tokens above 100 (:1190-1194)
+            ny = Tl if idx is None else idx.numel()
             part2 = torch.empty(B * Kg, dtype=F32, device=dev)
             H.orca_sim_loss(global16, local16, idx, B, Kg, ny, Tl, h, False, part2)
             out["L_ortho_qformer_local"] = cfg.orca_ortho_weight_qformer_local * part2.sum() / (B * Kg * ny)

@@ -199,7 +199,10 @@ def gated_cross_attention(w, d: Dims, o: OrcaDims, l: int, hs: Tensor, audio: Op
 
 
 # ----------------------------------------------------------------------------- losses (:1159-1206)
-def orca_losses(o: OrcaDims, g: Optional[Tensor], loc: Optional[Tensor], layer_align: List[Tensor]) -> Dict[str, Tensor]:
+def orca_losses(o: OrcaDims, g: Optional[Tensor], loc: Optional[Tensor], layer_align: List[Tensor],
+                local_index: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """local_index: the rows of the 100 sampled local tokens when there are more than 100 (default: the CPU `linspace` list; the
+    reference builds it on the local tokens' device, :1190-1194, which a caller can pass in)."""
     out: Dict[str, Tensor] = {}
     if g is not None:
         gn = F.normalize(g, dim=-1)
@@ -210,7 +213,8 @@ def orca_losses(o: OrcaDims, g: Optional[Tensor], loc: Optional[Tensor], layer_a
     if g is not None and loc is not None:
         gn, ln_ = F.normalize(g, dim=-1), F.normalize(loc, dim=-1)
         if ln_.shape[1] > 100:
-            ln_ = ln_[:, torch.linspace(0, ln_.shape[1] - 1, 100, dtype=torch.long), :]
+            idx = torch.linspace(0, ln_.shape[1] - 1, 100, dtype=torch.long) if local_index is None else local_index.to(torch.long).cpu()
+            ln_ = ln_[:, idx, :]
         if O._AC:
             gn, ln_ = gn.to(torch.bfloat16), ln_.to(torch.bfloat16)
         out["L_ortho_qformer_local"] = o.ortho_weight_qformer_local * (torch.einsum("bgh,blh->bgl", gn, ln_).float() ** 2).mean()
@@ -220,8 +224,9 @@ def orca_losses(o: OrcaDims, g: Optional[Tensor], loc: Optional[Tensor], layer_a
 
 
 # ----------------------------------------------------------------------------- model forward (:775-841)
-def model_forward(w, d: Dims, o: OrcaDims, batch: dict, training: bool = True, keep: Optional[dict] = None):
-    """-> (lm_loss | None, logits, orca_losses dict).  One audio per text row, in row order (the reference's cross-attention takes
+def model_forward(w, d: Dims, o: OrcaDims, batch: dict, training: bool = True, keep: Optional[dict] = None,
+                  local_index: Optional[Tensor] = None):
+    """-> (lm_loss | None, logits, orca_losses dict).  local_index: see `orca_losses`.  One audio per text row, in row order (the reference's cross-attention takes
     audio row b for text row b: `query=hidden_states [B, S, H], key=audio_local [N_audio, T', H]`)."""
     ids, am = batch["input_ids"], batch["attention_mask"]
     starts = [(int(r), int(s)) for r, s in batch.get("batch_start_positions", [])]
@@ -260,7 +265,7 @@ def model_forward(w, d: Dims, o: OrcaDims, batch: dict, training: bool = True, k
         keep["inputs_embeds"] = x
     logits = O.llm_forward(w, d, x, am, keep, layer_hook=hook if audio is not None else None)
     loss = O.causal_lm_loss(logits, batch["labels"]) if batch.get("labels") is not None else None
-    return loss, logits, orca_losses(o, g, loc, aligns)
+    return loss, logits, orca_losses(o, g, loc, aligns, local_index)
 
 
 def generate(w, d: Dims, o: OrcaDims, inputs: dict, max_new_tokens: int, pad_token_id: int, eos_token_ids: Optional[List[int]] = None,

@@ -206,19 +206,23 @@ def make_case(name, d, encoder_model_id="openai/whisper-tiny", with_generate=Tru
         print(name, "loss", float(out.loss), "->", path, os.path.getsize(path) // 1024, "KiB")
 
 
-def make_orca_case(gca: bool = False, local: bool = True):
+def make_orca_case(gca: bool = False, local: bool = True, enc_T: int = 0):
     """ORCA hybrid: the reference's own `ORCAHybridConnector`, `ORCAGatedCrossAttention` (deep injection
     wrappers installed by `_enable_orca_deep_injection`), `_prepare_inputs_for_llm`, the ORCA branch of `forward` and
     `compute_orca_losses` on a tiny local-config model in TRAINING mode (alignment loss on), fp32, dropout 0, with a 3-token
     transcription behind every audio (so the transcription-span pooling of the alignment loss is exercised) ->
     tests/golden/ref_orca_tiny.safetensors: weights of the ORCA tensors, batch, global / local tokens, logits, hidden states,
-    LM loss, every ORCA loss and every trainable gradient of (LM loss + sum of ORCA losses)."""
+    LM loss, every ORCA loss and every trainable gradient of (LM loss + sum of ORCA losses).
+    enc_T > 0: a longer encoder (Whisper positions) so that the local branch has more than 100 tokens and the global / local
+    orthogonality loss reads the reference's uniform sample of 100 of them (:1188-1194) -> the small ref_orca_tiny_long variant."""
     import desta_oracle as O
     import orca_oracle as R
     from safetensors.torch import save_file
     from transformers import BertConfig
     torch.manual_seed(0)
     d = O.tiny_dims(False)
+    if enc_T:
+        d.enc_T = enc_T
     NTR = 3
     o = R.OrcaDims(global_num_tokens=8, local_downsample=4, local_kernel_size=5, gate_init=0.1, audio_position_scale=2.5,
                    global_cross_attn=gca, local_enabled=local, ortho_diversity_weight=0.05, ortho_weight_qformer_local=0.05, align_weight_local=0.05)
@@ -299,7 +303,17 @@ def make_orca_case(gca: bool = False, local: bool = True):
     for k, v in out.orca_losses.items():
         blob["orca_loss::" + k] = v.detach().reshape(1)
     keep_grad = names
-    if gca or not local:
+    if enc_T:
+        # inputs (the longer mel), the losses and the connector gradients the sampled orthogonality loss reaches (the Conv1d weight,
+        # 1.3 MB in fp32, is left out; its bias and the layer norm around it stay)
+        sub = ("global_queries.0", "global_queries.3", "global_layer_weights", "global_qformer.layer.1.output.dense.bias", "global_proj.0.weight",
+               "global_proj.0.bias", "global_proj.1.weight", "global_proj.1.bias", "local_layer_weights", "local_proj_in.bias", "local_conv.bias",
+               "local_ln.weight", "local_ln.bias")
+        keep_grad = [n for n in names if n.startswith("perception.connector.") and any(n.endswith(x) for x in sub)]
+        blob["enc_T"] = torch.tensor([enc_T])
+        for k in ("logits", "global_tokens", "local_tokens", "hidden_last", "hidden_1", "logits_eval", "gen_ctx_len", "gen_ids"):
+            blob.pop(k, None)
+    elif gca or not local:
         # `orca_local_enabled: false` (with gca: only the global tokens are injected) resp.
         # the `orca_global_cross_attn: true` variant of the shipped ORCA configs (global | local tokens in the injected sequence): a
         # SMALL second file — losses, logits, generation and a representative subset of the gradients
@@ -311,7 +325,8 @@ def make_orca_case(gca: bool = False, local: bool = True):
             blob.pop(k, None)
     for n in keep_grad:                        # (weights are not stored: orca_oracle.init_weights(d, o, seed=7) regenerates them)
         blob["grad::" + n] = grads[n].contiguous() if n in grads else torch.zeros_like(w[n])
-    path = os.path.join(HERE, "ref_orca_tiny_nolocal.safetensors" if not local else "ref_orca_tiny_gca.safetensors" if gca else "ref_orca_tiny.safetensors")
+    path = os.path.join(HERE, "ref_orca_tiny_long.safetensors" if enc_T else "ref_orca_tiny_nolocal.safetensors" if not local
+                        else "ref_orca_tiny_gca.safetensors" if gca else "ref_orca_tiny.safetensors")
     save_file({k: v.contiguous() for k, v in blob.items()}, path)
     print("orca: lm loss", float(out.loss.detach()), {k: float(v.detach()) for k, v in out.orca_losses.items()}, "rope_theta read by the reference:", rope_theta_used,
           "->", path, os.path.getsize(path) // 1024, "KiB")
@@ -438,6 +453,8 @@ def main():
         make_orca_case(True)
     if "orca" in which or "orca_nolocal" in which:
         make_orca_case(True, local=False)
+    if "orca" in which or "orca_long" in which:
+        make_orca_case(False, enc_T=404)                          # Tl = (404 - 1) // 4 + 1 = 101 local tokens
     if "asr" in which:
         make_asr_case()
 

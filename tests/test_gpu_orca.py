@@ -103,6 +103,8 @@ def test_orca_kernels_vs_oracle(golden_dir):
     y = torch.empty(B * T, Hd, dtype=torch.bfloat16, device="cuda")
     H.orca_rope(x.cuda(), y, B, T, Hd, 10000.0, 2.5, round_cos_sin=False)
     assert rel_err(y.float().cpu().view(B, T, Hd), R.rope_whole_vector(x.float(), 10000.0, 2.5)) < 6e-3
+    H.orca_rope(x.cuda(), y, B, T, Hd, 10000.0, 2.5, round_cos_sin=True)          # what the model passes: bf16 cos / sin, as on a bf16 x
+    assert rel_err(y.float().cpu().view(B, T, Hd), R.rope_whole_vector(x, 10000.0, 2.5).float()) < 6e-3
     # local mix
     taps, rows, dd = 4, 50, 128
     e = torch.randn(taps, rows, dd, generator=gen).to(torch.bfloat16)
@@ -454,6 +456,71 @@ def test_orca_use_all_layers_vs_oracle():
     b = torch.cat([go[n].reshape(-1) for n in names])
     worst = max(errs, key=errs.get)
     print("orca all layers: grads rel", float((a - b).norm() / b.norm()), "cos", float((a @ b) / (a.norm() * b.norm())), worst, errs[worst])
+    assert float((a - b).norm() / b.norm()) < 2e-2 and float((a @ b) / (a.norm() * b.norm())) > 0.9995 and errs[worst] < 6.5e-2
+
+
+def test_orca_local_index_is_the_reference_device_linspace():
+    """The global / local orthogonality loss reads 100 sampled local tokens above 100 (modeling_desta25.py:1188-1194); the reference
+    builds the list with `torch.linspace(..., dtype=torch.long, device=l_norm.device)`.  For every Tl the shipped encoders can give
+    (101 .. 1500) the model's list is that device list, built once per Tl; how many differ from the CPU `linspace` is printed."""
+    from desta.models.modeling_desta25 import OrcaHIP
+    o = OrcaHIP.__new__(OrcaHIP)
+    o.dev, o._lidx = torch.device("cuda:0"), {}
+    assert o.local_index(24) is None and o.local_index(100) is None
+    differ = []
+    for Tl in range(101, 1501):
+        want = torch.linspace(0, Tl - 1, 100, dtype=torch.long, device="cuda:0")
+        got = o.local_index(Tl)
+        assert got.dtype == torch.int32 and got.device == want.device and torch.equal(got.long(), want), Tl
+        assert o.local_index(Tl) is got
+        if not torch.equal(want.cpu(), torch.linspace(0, Tl - 1, 100, dtype=torch.long)):
+            differ.append(Tl)
+    print(f"device vs CPU linspace: {len(differ)} of 1400 lists differ", differ[:20])
+
+
+def test_orca_sampled_local_tokens_vs_oracle():
+    """The shipped local-token path: a 1500-position encoder (whisper's 1500 frames) gives Tl = 375 local tokens, so
+    `L_ortho_qformer_local` reads the reference's sample of 100 of them (index list on the y side of the forward and on the x side of
+    the local gradient).  Loss, the three ORCA losses and every gradient against the oracle given the same (device) index list."""
+    from desta.models.modeling_desta25 import DeSTA25AudioModel
+    d = copy.copy(O.tiny_dims(False))
+    d.enc_T = 1500
+    kg = 4
+    o = R.OrcaDims(global_num_tokens=kg, local_downsample=4, local_kernel_size=5, ortho_diversity_weight=0.05, ortho_weight_qformer_local=0.5,
+                   align_weight_local=0.05)
+    w = R.init_weights(d, o, seed=17)
+    d.prompt_size = kg + 2
+    batch = O.synthetic_batch(d, B=2, S_ctx=6, S_tgt=10, seed=5, pad=[2, 0])
+    g = torch.Generator().manual_seed(4)
+    batch["batch_transcription_ids"] = [torch.randint(3, d.vocab, (1, 2), generator=g) for _ in range(2)]
+    cfg = cfg_from_dims(d, connector_mode="orca_hybrid", orca_enabled=True, orca_global_num_tokens=kg, orca_local_downsample=4,
+                        orca_local_kernel_size=5, orca_ortho_diversity_weight=0.05, orca_ortho_weight_qformer_local=0.5, orca_align_weight_local=0.05)
+    model = DeSTA25AudioModel(cfg, weights=w)
+    names = R.trainable_names(d, o)
+    model.train()
+    out = model(**batch, keep_logits=True)
+    assert out.audio_local.shape[1] == 375
+    idx = model.orca.local_index(375)
+    assert idx is not None and idx.numel() == 100
+    for n in names:
+        w[n].requires_grad_(True)
+    loss_o, logits_o, losses_o = R.model_forward(w, d, o, batch, training=True, local_index=idx)
+    R.total_loss(loss_o, losses_o).backward()
+    m = batch["attention_mask"].bool()
+    assert abs(float(out.loss) - float(loss_o)) < 3e-3 and rel_err(out.logits.float().cpu()[m], logits_o.detach()[m]) < 2e-2
+    assert sorted(out.orca_losses) == sorted(losses_o) == ["L_align_layerwise", "L_ortho_diversity", "L_ortho_qformer_local"]
+    for k, v in losses_o.items():
+        assert abs(float(out.orca_losses[k]) - float(v)) < 2e-2 * abs(float(v)) + 2e-6, (k, float(out.orca_losses[k]), float(v))
+    model.backward()
+    go = {n: w[n].grad.detach().double() for n in names}
+    gn = sorted(float(go[n].norm()) for n in names)
+    floor = gn[len(gn) // 2] * 1e-2
+    errs = {n: float((model.arena.grad(n).double().cpu() - go[n].reshape(model.arena.shapes[n])).norm() / max(float(go[n].norm()), floor)) for n in names}
+    a = torch.cat([model.arena.grad(n).reshape(-1).double().cpu() for n in names])
+    b = torch.cat([go[n].reshape(-1) for n in names])
+    worst = max(errs, key=errs.get)
+    print("orca sampled local tokens:", {k: float(v) for k, v in out.orca_losses.items()}, "grads rel", float((a - b).norm() / b.norm()),
+          "cos", float((a @ b) / (a.norm() * b.norm())), worst, errs[worst])
     assert float((a - b).norm() / b.norm()) < 2e-2 and float((a @ b) / (a.norm() * b.norm())) > 0.9995 and errs[worst] < 6.5e-2
 
 

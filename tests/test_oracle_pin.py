@@ -313,6 +313,55 @@ def test_orca_oracle_matches_reference_golden(golden_dir):
     assert worst < 2e-3, worst
 
 
+def test_orca_oracle_sampled_local_tokens_match_reference_golden(golden_dir):
+    """The oracle's `Tl > 100` branch of the global / local orthogonality loss (the reference's uniform sample of 100 local tokens,
+    modeling_desta25.py:1188-1194), which every shipped config takes (1500 Whisper frames -> 375 local tokens) and the base golden
+    (Tl = 24) does not reach: a 404-position encoder gives Tl = 101 (tests/golden/ref_orca_tiny_long.safetensors, a small variant
+    file: inputs, losses, connector gradients).  Also shows the golden pins the sample: all 101 tokens give another loss."""
+    import copy
+    import torch.nn.functional as F
+    import orca_oracle as R
+    g = load_file(os.path.join(golden_dir, "ref_orca_tiny_long.safetensors"))
+    kg, ds, ks, ntr = (int(x) for x in g["orca_dims"])
+    d = O.tiny_dims(False)
+    d.enc_T = int(g["enc_T"])
+    o = R.OrcaDims(global_num_tokens=kg, local_downsample=ds, local_kernel_size=ks, ortho_diversity_weight=0.05, ortho_weight_qformer_local=0.05,
+                   align_weight_local=0.05)
+    w = R.init_weights(d, o, seed=7)
+    d = copy.copy(d)
+    d.prompt_size = kg + ntr
+    n = g["starts"].shape[0]
+    batch = {"input_ids": g["input_ids"], "attention_mask": g["attention_mask"], "labels": g["labels"], "batch_features": g["batch_features"],
+             "batch_start_positions": [(int(b), int(s)) for b, s in g["starts"].tolist()],
+             "batch_transcription_ids": [g["transcription_ids"][i:i + 1] for i in range(n)]}
+    names = R.trainable_names(d, o)
+    for nm in names:
+        w[nm].requires_grad_(True)
+    keep = {}
+    orig = R.rope_whole_vector
+    R.rope_whole_vector = lambda x, theta, scale: orig(x, float(g["rope_theta_used"]), scale)
+    try:
+        loss, _, losses = R.model_forward(w, d, o, batch, training=True, keep=keep)
+        R.total_loss(loss, losses).backward()
+    finally:
+        R.rope_whole_vector = orig
+    Tl = keep["local_tokens"].shape[1]
+    assert Tl == (d.enc_T - 1) // ds + 1 == 101
+    assert abs(float(loss.detach()) - float(g["loss"])) < 2e-5
+    assert sorted(losses) == sorted(k[len("orca_loss::"):] for k in g if k.startswith("orca_loss::"))
+    for k, v in losses.items():
+        assert abs(float(v.detach()) - float(g["orca_loss::" + k])) < 1e-6 + 1e-4 * abs(float(g["orca_loss::" + k])), k
+    sub = [k[len("grad::"):] for k in g if k.startswith("grad::")]
+    assert len(sub) >= 10 and "perception.connector.local_layer_weights" in sub
+    for nm in sub:
+        assert rel_err(w[nm].grad, g["grad::" + nm]) < 2e-3, nm
+    with torch.no_grad():                               # every local token instead of the sample: the golden tells them apart
+        gn, ln_ = F.normalize(keep["global_tokens"], dim=-1), F.normalize(keep["local_tokens"], dim=-1)
+        every = o.ortho_weight_qformer_local * (torch.einsum("bgh,blh->bgl", gn, ln_) ** 2).mean()
+    ref = float(g["orca_loss::L_ortho_qformer_local"])
+    assert abs(float(every) - ref) > 1e-3 * ref, (float(every), ref)
+
+
 def rel_err(a, b):
     a, b = a.detach().double(), b.detach().double()
     return float((a - b).norm() / (b.norm() + 1e-30))
