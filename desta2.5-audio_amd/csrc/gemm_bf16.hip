@@ -24,6 +24,9 @@
 
 namespace {
 
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;                 // 16 KiB per operand tile
 
@@ -42,7 +45,10 @@ struct GemmArgs {
     unsigned drop_thresh, seed_lo, seed_hi; float drop_scale;   // dropout on (acc+bias) after act, before residual (0 = off)
     int tilesM, tilesN;
     int full_tiles, split;                              // 256-kernel: tiles [0,full) whole-K; the rest in `split` K-slices
-    float* ws;                                          // fp32 partial slabs [(tile-full)*split + slice][256][256]
+    union {                                             // (one slot: the skinny kernel has no split-K slabs, and GemmArgs keeps its size)
+        float* ws;                                      // fp32 partial slabs [(tile-full)*split + slice][256][256]
+        const float* b_scale;                           // skinny kernel, W8 form: B holds e4m3 bytes, b_scale[n] the power-of-two scale of weight row n
+    };
     int* tickets;                                       // per split tile: arrivals of its K-slices (in-kernel reduction) or null
     const float* rms_w; float rms_eps;                  // skinny kernel: RMSNorm(A rows; weight rms_w) applied on the fly
     const float* rope_cs; const int* rope_pos; int rope_cols, rope_hd;   // rotary embedding of output columns [0, rope_cols) in adjacent pairs
@@ -1329,10 +1335,28 @@ __global__ __launch_bounds__(256) void gemm_splitk_fixup_kernel(GemmArgs p) {
 // chunks: the loads of group i+1 are in flight while group i feeds the MFMAs, so a block streams continuously
 // instead of paying one memory latency per group.  Partial sums of the 8 waves are reduced through LDS in
 // fixed order (deterministic).
-template <int COLS, int U>
+template <int COLS, int U, bool W8>
 struct SkinnyStage {
     bf16x8 w0[U][COLS / 16], w1[U][COLS / 16], x0[U], x1[U];
 };
+template <int COLS, int U>
+struct SkinnyStage<COLS, U, true> {
+    u32x4 wq[U][COLS / 16];                                              // 16 e4m3 bytes = the 16 k of this lane's chunk slice
+    bf16x8 x0[U], x1[U];
+};
+
+// 16 OCP e4m3 bytes -> the two bf16 MFMA fragments (k 0..7, k 8..15).  Exact: e4m3 has 3 mantissa bits and its whole range,
+// subnormals included, lies inside bf16's normal range, so the upper half of the fp32 conversion IS the value.
+__device__ __forceinline__ void e4m3x16_to_bf16(const u32x4& q, bf16x8& lo, bf16x8& hi) {
+    union { unsigned u[8]; bf16x8 v[2]; } o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[i], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[i], true);
+        o.u[2 * i] = __builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u);
+        o.u[2 * i + 1] = __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u);
+    }
+    lo = o.v[0]; hi = o.v[1];
+}
 
 // SWIGLU: B holds gate rows [0,N) and up rows [N,2N) (the concatenated gate|up projection); a tile is 8 output
 // columns = the 8 gate + 8 matching up rows, the epilogue stores bf16(silu(gate)) * up to C[M,N] with the
@@ -1346,11 +1370,18 @@ struct SkinnyStage {
 // The grid is PERSISTENT (<= 2 blocks per CU): a block walks column tiles blockIdx.x, +gridDim.x, ... and the
 // two-stage load pipeline runs across tile boundaries, so the weight stream never drains while a tile is being
 // reduced and the RMS prologue is paid once per block, not once per tile.
+// W8 (desta_gemm_w8a16_nt): B holds OCP e4m3 bytes, one 16-byte load per lane and chunk instead of two; the bytes become the
+// same two bf16 fragments in registers, feed the same MFMAs in the same order, and the power-of-two scale of each weight row
+// multiplies the reduced fp32 sum before anything else in the epilogue.  Scaling by a power of two commutes with every fp32
+// rounding, so the result equals the bf16 form run on the dequantised weight bit for bit.
 constexpr int SKINNY_XS_BYTES = 8 * 4096 * 2;                           // M * 2K must fit: 8 rows x 4096
 struct SkinnyCursor { int tile, grp; };
+#ifndef SKINNY_W8_U
+#define SKINNY_W8_U 2                                                   // pipeline depth of the weight-only FP8 form (2 or 4; option 11 overrides for act 0)
+#endif
 
-template <int COLS, int U, bool SWIGLU, bool RMS>
-__global__ __launch_bounds__(512, (COLS == 16 && U == 2) ? 2 : 1) void gemm_bf16_nt_skinny_kernel(GemmArgs p, int ntiles) {
+template <int COLS, int U, bool SWIGLU, bool RMS, bool W8 = false>
+__global__ __launch_bounds__(512, (COLS == 16 && (U == 2 || W8)) ? 2 : 1) void gemm_bf16_nt_skinny_kernel(GemmArgs p, int ntiles) {
     static_assert(!SWIGLU || COLS == 16, "SwiGLU pairing uses one 16-row weight tile");
     constexpr int T = COLS / 16;
     constexpr int RED_BYTES = 8 * T * 64 * 16;                           // one buffer of per-wave partial tiles
@@ -1360,6 +1391,7 @@ __global__ __launch_bounds__(512, (COLS == 16 && U == 2) ? 2 : 1) void gemm_bf16
     const int r = lane & 15, g = lane >> 4;
     const bool mok = r < p.M;
     const bf16_t* Bz = p.B + (long)z * p.sB + g * 16;
+    const char* Bq = (const char*)p.B + (long)z * p.sB + g * 16;        // W8: one byte per element
     const bf16_t* ap = p.A + (long)z * p.sA + (long)(mok ? r : 0) * p.lda + g * 16;
     const int nchunks = p.K >> 6;
     constexpr int STEP = 8 * U;
@@ -1371,7 +1403,7 @@ __global__ __launch_bounds__(512, (COLS == 16 && U == 2) ? 2 : 1) void gemm_bf16
     f32x4 acc[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    SkinnyStage<COLS, U> sa, sb;
+    SkinnyStage<COLS, U, W8> sa, sb;
     SkinnyCursor lc = {(int)blockIdx.x, 0}, mc = {(int)blockIdx.x, 0};
     int parity = 0;
 
@@ -1380,17 +1412,23 @@ __global__ __launch_bounds__(512, (COLS == 16 && U == 2) ? 2 : 1) void gemm_bf16
     {                                                                                       \
         const int n0 = lc.tile * (SWIGLU ? 8 : COLS), c0 = wave + lc.grp * STEP;            \
         const bf16_t* bp[T];                                                                \
+        const char* bq[T];                                                                  \
         _Pragma("unroll") for (int t = 0; t < T; ++t) {      /* clamped rows: computed, never stored */ \
             const int wrow = SWIGLU ? (r < 8 ? min(n0 + r, p.N - 1) : p.N + min(n0 + r - 8, p.N - 1)) \
                                     : min(n0 + t * 16 + r, p.N - 1);                        \
             bp[t] = Bz + (long)wrow * p.ldb;                                                \
+            bq[t] = Bq + (long)wrow * p.ldb;                                                \
         }                                                                                   \
         _Pragma("unroll") for (int u = 0; u < U; ++u) {                                     \
             const int cc = c0 + 8 * u;                                                      \
             if (cc < nchunks) {                                                             \
                 _Pragma("unroll") for (int t = 0; t < T; ++t) {                             \
-                    S.w0[u][t] = *(const bf16x8*)(bp[t] + (long)cc * 64);                   \
-                    S.w1[u][t] = *(const bf16x8*)(bp[t] + (long)cc * 64 + 8);               \
+                    if constexpr (W8) {                                                     \
+                        S.wq[u][t] = *(const u32x4*)(bq[t] + (long)cc * 64);                \
+                    } else {                                                                \
+                        S.w0[u][t] = *(const bf16x8*)(bp[t] + (long)cc * 64);               \
+                        S.w1[u][t] = *(const bf16x8*)(bp[t] + (long)cc * 64 + 8);           \
+                    }                                                                       \
                 }                                                                           \
                 if (!RMS) {                                                                 \
                     S.x0[u] = *(const bf16x8*)(ap + (long)cc * 64);                         \
@@ -1413,8 +1451,15 @@ __global__ __launch_bounds__(512, (COLS == 16 && U == 2) ? 2 : 1) void gemm_bf16
                 }                                                                           \
                 const bf16x8 a0 = mok ? S.x0[u] : zero, a1 = mok ? S.x1[u] : zero;          \
                 _Pragma("unroll") for (int t = 0; t < T; ++t) {                             \
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(S.w0[u][t], a0, acc[t], 0, 0, 0); \
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(S.w1[u][t], a1, acc[t], 0, 0, 0); \
+                    if constexpr (W8) {                                                     \
+                        bf16x8 w0, w1;                                                      \
+                        e4m3x16_to_bf16(S.wq[u][t], w0, w1);                                \
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, a0, acc[t], 0, 0, 0); \
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, a1, acc[t], 0, 0, 0); \
+                    } else {                                                                \
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(S.w0[u][t], a0, acc[t], 0, 0, 0); \
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(S.w1[u][t], a1, acc[t], 0, 0, 0); \
+                    }                                                                       \
                 }                                                                           \
             }                                                                               \
         }                                                                                   \
@@ -1434,6 +1479,13 @@ __global__ __launch_bounds__(512, (COLS == 16 && U == 2) ? 2 : 1) void gemm_bf16
 #pragma unroll
             for (int w = 1; w < 8; ++w) sum += red[w][wave][lane];
             const int n0 = tile * (SWIGLU ? 8 : COLS);
+            if constexpr (W8) {                                          // the weight row's scale, before any rounding or activation
+                const int n = SWIGLU ? n0 + (g & 1) * 4 : n0 + wave * 16 + g * 4;
+                if (n < p.N) {                                           // N % 4 == 0: the four rows exist together
+                    const float4 s = *(const float4*)(p.b_scale + (SWIGLU && g >= 2 ? p.N : 0) + n);
+                    sum[0] *= s.x; sum[1] *= s.y; sum[2] *= s.z; sum[3] *= s.w;
+                }
+            }
             if (SWIGLU) {
                 // lane groups 0,1 hold gate columns n0+4g.., groups 2,3 the matching up columns: fetch up from lane+32
                 u16x4 o;
@@ -1501,6 +1553,7 @@ static int g_phases2 = 1;         // automatic choice uses the 2-phase (32 MFMAs
 extern "C" int desta_gemm_set_persistent(int on) { g_persistent = on; return DESTA_OK; }
 static int g_skinny = 0;          // 0 auto, else COLS*10 + U of the skinny (M <= 16) kernel (tuning)
 static int g_skinny_blocks = 512;  // persistent grid of the skinny kernel (2 blocks per CU)
+static int g_skinny_w8 = 0;        // option 11: 0 auto, else 162 / 164 = pipeline depth U of the weight-only FP8 form (act 0; tuning)
 static int g_tail_skip = 1;        // option 10: the 2-phase 256x256 kernel stops its half-tile stream at the last K-tile (1, default) or re-loads dead slots (0: rounds 1-3)
 extern "C" int desta_gemm_set_option(int option, int value) {
     if (option == 0) g_persistent = value;
@@ -1516,6 +1569,10 @@ extern "C" int desta_gemm_set_option(int option, int value) {
     else if (option == 5) g_inkernel_splitk = value;
     else if (option == 6) g_small_ring = value;
     else if (option == 10) g_tail_skip = value;
+    else if (option == 11) {
+        if (value != 0 && value != 162 && value != 164) { desta_set_error("gemm_set_option: FP8 skinny variant %d unknown (162 164)", value); return DESTA_EINVAL; }
+        g_skinny_w8 = value;
+    }
     else if (option == 3) {
         if (value < 1 || value > 65535) { desta_set_error("gemm_set_option: skinny grid %d out of range", value); return DESTA_EINVAL; }
         g_skinny_blocks = value;
@@ -1685,5 +1742,51 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
     }
     DESTA_CHECK_LAUNCH("gemm_bf16_nt");
     g_last_kernel = big ? 2 : 1;
+    return DESTA_OK;
+}
+
+// Weight-only FP8 form of the decode projections: the skinny kernel above with W8 = true.  Everything the bf16 entry point
+// offers beyond what a decode step asks for (bias, GELU, pre-activation copies, dropout, transposed operands, rotary epilogue,
+// batches) is rejected, not ignored.
+extern "C" int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scale, void* stream) {
+    DESTA_CHECK_ARG(d && d->A && d->B && d->C, "gemm_w8: null operand");
+    DESTA_CHECK_ARG(b_scale, "gemm_w8: null scale pointer");
+    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm_w8: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
+    DESTA_CHECK_ARG(d->M <= 16, "gemm_w8: M=%d, the weight-only FP8 kernel is the decode path (M <= 16)", d->M);
+    DESTA_CHECK_ARG(d->act == 0 || d->act == 4, "gemm_w8: act %d unsupported (0, or 4 = SwiGLU over concatenated gate|up rows)", d->act);
+    DESTA_CHECK_ARG(d->K % BK == 0, "gemm_w8: K=%d must be a multiple of %d", d->K, BK);
+    DESTA_CHECK_ARG(d->N % 4 == 0, "gemm_w8: N=%d must be a multiple of 4", d->N);
+    DESTA_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 16 == 0 && d->ldc % 4 == 0, "gemm_w8: lda must be a multiple of 8, ldb (e4m3 elements) of 16, ldc of 4");
+    DESTA_CHECK_ARG(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0) && ((uintptr_t)b_scale % 16 == 0),
+                    "gemm_w8: operands and scales must be 16-byte aligned");
+    DESTA_CHECK_ARG(d->batch == 1, "gemm_w8: batch %d unsupported (1)", d->batch);
+    DESTA_CHECK_ARG(!d->bias && !d->preact && !d->aux && d->dropout_p == 0.f && !d->trans_a && !d->trans_b && !d->rope_cos_sin,
+                    "gemm_w8: bias, preact, aux, dropout, transposed operands and the rotary epilogue are unsupported");
+    DESTA_CHECK_ARG(!d->residual || d->ldr % 4 == 0, "gemm_w8: ldr must be a multiple of 4");
+    DESTA_CHECK_ARG(d->act != 4 || (!d->out_f32 && !d->residual), "gemm_w8: act 4 needs a bf16 output and no residual");
+    DESTA_CHECK_ARG(!d->a_rms_weight || ((size_t)d->M * 2 * (size_t)d->K <= (size_t)SKINNY_XS_BYTES && d->K % 512 == 0),
+                    "gemm_w8: a_rms_weight (fused RMSNorm of A) needs M*2K <= %d bytes of LDS and K %% 512 == 0", SKINNY_XS_BYTES);
+    GemmArgs a = {};
+    a.A = (const bf16_t*)d->A; a.B = (const bf16_t*)d->B; a.C = d->C;
+    a.M = d->M; a.N = d->N; a.K = d->K;
+    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
+    a.res = d->residual; a.ldr = d->ldr; a.res_f32 = d->residual_f32;
+    a.act = d->act; a.out_f32 = d->out_f32; a.alpha = d->alpha; a.drop_scale = 1.0f;
+    a.rms_w = d->a_rms_weight; a.rms_eps = d->a_rms_eps; a.b_scale = b_scale;
+    const int u = d->act != 4 && g_skinny_w8 ? g_skinny_w8 % 10 : SKINNY_W8_U;
+    const int ntiles = d->act == 4 ? (d->N + 7) / 8 : (d->N + 15) / 16;
+    a.tilesM = 1; a.tilesN = ntiles; a.full_tiles = ntiles; a.split = 1;
+    const dim3 grid(ntiles < g_skinny_blocks ? ntiles : g_skinny_blocks, 1);
+    hipStream_t st = (hipStream_t)stream;
+    const bool rms = a.rms_w != nullptr;
+#define SK8_LAUNCH(U_, SW_) \
+    do { if (rms) hipLaunchKernelGGL((gemm_bf16_nt_skinny_kernel<16, U_, SW_, true, true>), grid, dim3(512), 0, st, a, ntiles); \
+         else hipLaunchKernelGGL((gemm_bf16_nt_skinny_kernel<16, U_, SW_, false, true>), grid, dim3(512), 0, st, a, ntiles); } while (0)
+    if (d->act == 4) SK8_LAUNCH(SKINNY_W8_U, true);
+    else if (u == 4) SK8_LAUNCH(4, false);
+    else SK8_LAUNCH(2, false);
+#undef SK8_LAUNCH
+    DESTA_CHECK_LAUNCH("gemm_w8a16_nt_skinny");
+    g_last_kernel = 3;
     return DESTA_OK;
 }

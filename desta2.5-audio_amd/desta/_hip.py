@@ -126,6 +126,49 @@ def rms_fusable(M: int, K: int) -> bool:
     return M <= 16 and M * 2 * K <= 8 * 4096 * 2 and K % 512 == 0
 
 
+_quantize_rows_e4m3 = _sig("desta_quantize_rows_e4m3", vp, i32, i32, i64, vp, vp, vp)
+_gemm_w8 = _sig("desta_gemm_w8a16_nt", C.POINTER(GemmDesc), vp, vp)
+GEMM_W8_CALLS = 0                  # weight-only FP8 projections issued by this process (tests assert which path a projection took)
+
+
+def quantize_rows_e4m3(w, rows=None, cols=None, ld=None, q=None, scale=None):
+    """bf16 weight [rows, cols] (row stride ld) -> (q [rows, cols] uint8 holding OCP e4m3fn bytes, scale [rows] fp32).
+    One power-of-two scale per row, the smallest with amax(row) / scale <= 448; q * scale is exact in bf16."""
+    assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1
+    rows = w.shape[0] if rows is None else rows
+    cols = w.shape[1] if cols is None else cols
+    ld = w.stride(0) if ld is None else ld
+    q = torch.empty(rows, cols, dtype=torch.uint8, device=w.device) if q is None else q
+    scale = torch.empty(rows, dtype=torch.float32, device=w.device) if scale is None else scale
+    check(_quantize_rows_e4m3(p(w), rows, cols, ld, p(q), p(scale), stream()), "desta_quantize_rows_e4m3")
+    return q, scale
+
+
+def gemm_w8(A, B8, scale, out, M, N, K, *, lda=None, ldb=None, ldc=None, residual=None, ldr=None, act=0, alpha=1.0,
+            a_rms_weight=None, a_rms_eps=0.0):
+    """out[M,N] = act(alpha * scale[n] * (A[M,K] @ e4m3(B8)[N,K]^T)) + residual for M <= 16: the decode projections on weights
+    stored as OCP e4m3fn bytes with one power-of-two fp32 scale per row (`quantize_rows_e4m3`).  act 4: B8 / scale hold the
+    concatenated gate|up rows [2N].  Same bits as `gemm` on the dequantised weight bf16(B8 * scale)."""
+    global GEMM_W8_CALLS
+    d = GemmDesc()
+    d.A, d.B, d.C = p(A), p(B8), p(out)
+    d.M, d.N, d.K, d.batch = M, N, K, 1
+    d.lda = K if lda is None else lda
+    d.ldb = K if ldb is None else ldb
+    d.ldc = N if ldc is None else ldc
+    d.residual = p(residual)
+    d.ldr = N if ldr is None else ldr
+    d.residual_f32 = int(residual is not None and residual.dtype == torch.float32)
+    d.act = act
+    d.out_f32 = int(out.dtype == torch.float32)
+    d.ldp = N
+    d.alpha = alpha
+    d.a_rms_weight, d.a_rms_eps = p(a_rms_weight), a_rms_eps
+    check(_gemm_w8(C.byref(d), p(scale), stream()), "desta_gemm_w8a16_nt")
+    GEMM_W8_CALLS += 1
+    return out
+
+
 _gemm_prof = None
 _gemm_ws = {}                      # (device, stream) -> split-K scratch
 GEMM_WS_BYTES = (64 << 20) + 4096

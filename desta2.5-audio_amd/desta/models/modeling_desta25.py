@@ -1450,7 +1450,34 @@ class CausalLMHIP:
         self.lora = None
         self.skip_dead_rows = True                  # A/B switch (bench.py --no-dead-row-skip): last layer on the target tail, layer-0 dX on the audio rows
         self.fuse_swiglu = True                     # A/B switch (bench.py --no-swiglu-fusion): silu(gate) * up and its backward inside the gate|up / d(act) GEMM epilogues
+        self.decode_weights = "bf16"                # `set_decode_weights`: what the projections of a KV-cached decode step stream
+        self.head8 = None
 
+    # -- weight-only FP8 (e4m3) decode: a second, half-size copy of the frozen decode-side weights -------------------------------
+    DECODE_WEIGHT_KINDS = ("bf16", "fp8")
+
+    def set_decode_weights(self, kind: str) -> None:
+        """What `decode_step` streams: "bf16" (default, the reference's arithmetic) or "fp8" = OCP e4m3 bytes with one power-of-two
+        scale per output row (W8A16; activations, KV cache and accumulation unchanged).  The copies are made at the first decode
+        step that needs them and freed by "bf16".  The prompt pass and training always use the bf16 weights."""
+        if kind not in self.DECODE_WEIGHT_KINDS:
+            raise ValueError(f"decode_weights must be one of {self.DECODE_WEIGHT_KINDS}, got {kind!r}")
+        self.decode_weights = kind
+        if kind == "bf16":
+            self.head8 = None
+            for ly in self.layers:
+                ly.pop("q8", None)
+
+    def _fp8_decode_weights(self) -> None:
+        """Quantise once: q|k|v, o, gate|up (the concatenated decode copy) and down of every layer, and the lm_head (tied
+        embeddings: the bf16 table stays for the gather).  With adapters the q|k|v projection is left out: its merged weight
+        changes with training."""
+        if self.head8 is not None:
+            return
+        names = ("wo", "wgu", "wd") if self.lora is not None else ("wqkv", "wo", "wgu", "wd")
+        for ly in self.layers:
+            ly["q8"] = {n: H.quantize_rows_e4m3(ly[n]) for n in names}
+        self.head8 = H.quantize_rows_e4m3(self.head)
     # -- LoRA adapters on q/k/v (reference: peft, modeling_desta25.py:720-729; published layer: y = W x + (alpha / r) B A drop(x)) --------
     LORA_KP = 64                                    # the three rank-r adapters side by side, padded to one 64-wide GEMM K block
 
@@ -1722,14 +1749,25 @@ class CausalLMHIP:
         x = self.g_x
         fuse = H.rms_fusable(B, h)                      # RMSNorm folded into the projection that consumes it
 
-        def proj(xin, nw, w, out, N, **kw):
+        fp8 = self.decode_weights == "fp8"
+        if fp8:
+            self._fp8_decode_weights()
+
+        def mm(xin, w, w8, out, N, K, **kw):            # one projection on the bf16 weight, or on its e4m3 copy (q, scale)
+            if w8 is not None:
+                H.gemm_w8(xin, w8[0], w8[1], out, B, N, K, **kw)
+            else:
+                H.gemm(xin, w, out, B, N, K, **kw)
+
+        def proj(xin, nw, w, w8, out, N, **kw):
             if fuse:
-                H.gemm(xin, w, out, B, N, h, a_rms_weight=nw, a_rms_eps=c.rms_norm_eps, **kw)
+                mm(xin, w, w8, out, N, h, a_rms_weight=nw, a_rms_eps=c.rms_norm_eps, **kw)
             else:
                 H.rmsnorm_fwd(xin, nw, c.rms_norm_eps, self.g_hb, self.g_r)
-                H.gemm(self.g_hb, w, out, B, N, h, **kw)
+                mm(self.g_hb, w, w8, out, N, h, **kw)
         for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
-            proj(x, ly["n1"], ly["wqkv"] if self.lora is None else self._lora_merged(li), self.g_qkv, self.qkvw)
+            q8 = ly["q8"] if fp8 else {}
+            proj(x, ly["n1"], ly["wqkv"] if self.lora is None else self._lora_merged(li), q8.get("wqkv"), self.g_qkv, self.qkvw)
             H.rope_kv_append(self.g_qkv, self.qkvw, B, 1, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"),
                              c.rms_norm_eps, pos_shift, cache, Smax * self.kvw, self.kvw, cur)     # rotate q,k + append K|V at slot cur
             ad = H.attn_desc(self.g_qkv, cache, cache, self.g_att, self.g_lse, batch=B, hq=self.hq, hkv=self.hkv, sq=1, sk=cur + 1,
@@ -1737,12 +1775,12 @@ class CausalLMHIP:
                              q_rs=self.qkvw, k_rs=self.kvw, v_rs=self.kvw, o_rs=self.hq * self.hd,
                              q_bs=self.qkvw, k_bs=Smax * self.kvw, v_bs=Smax * self.kvw, o_bs=self.hq * self.hd)
             H.attention_fwd(ad)
-            H.gemm(self.g_att, ly["wo"], self.g_xm, B, h, self.hq * self.hd, residual=x)
-            proj(self.g_xm, ly["n2"], ly["wgu"], self.g_act, self.I, act=4)                    # norm + gate|up projection + SwiGLU
-            H.gemm(self.g_act, ly["wd"], self.g_x, B, h, self.I, residual=self.g_xm)
+            mm(self.g_att, ly["wo"], q8.get("wo"), self.g_xm, h, self.hq * self.hd, residual=x)
+            proj(self.g_xm, ly["n2"], ly["wgu"], q8.get("wgu"), self.g_act, self.I, act=4)     # norm + gate|up projection + SwiGLU
+            mm(self.g_act, ly["wd"], q8.get("wd"), self.g_x, h, self.I, residual=self.g_xm)
             if layer_hook is not None:                                        # ORCA deep injection on the new row of every sequence
                 layer_hook(li, self.g_x)
-        proj(self.g_x, self.norm, self.head, self.g_logits, self.V, ldc=self.Vp)
+        proj(self.g_x, self.norm, self.head, self.head8 if fp8 else None, self.g_logits, self.V, ldc=self.Vp)
         return self.g_logits
 
     def generate_greedy(self, x0_filler, B: int, S: int, kv_start: torch.Tensor, max_new_tokens: int, pad_token_id: int,
@@ -2075,6 +2113,13 @@ class DeSTA25AudioModel:
     def train(self, mode=True):
         self.training = mode
         return self
+
+    def set_decode_weights(self, kind: str) -> None:
+        """Weights the LLM's KV-cached decode steps stream: "bf16" (default) or "fp8" (weight-only OCP e4m3, per-row power-of-two
+        scales; `CausalLMHIP.set_decode_weights`).  `generate`, `_generate_step` and the trainer's evaluate use whatever is set."""
+        if kind not in CausalLMHIP.DECODE_WEIGHT_KINDS:
+            raise ValueError(f"decode_weights must be one of {CausalLMHIP.DECODE_WEIGHT_KINDS}, got {kind!r}")
+        self.llm.set_decode_weights(kind)
 
     def eval(self):
         return self.train(False)

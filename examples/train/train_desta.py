@@ -161,6 +161,18 @@ def create_training_args(cfg: Cfg):
                          if cfg.dataset.train_ds.get("synthetic", False) else None))
 
 
+DECODE_WEIGHTS = ("bf16", "fp8")
+
+
+def decode_weights_kind(cfg: Cfg) -> str:
+    """trainer.decode_weights (this port's key; absent = "bf16"): what the KV-cached decode steps of evaluate / generate stream.
+    "fp8" = weight-only OCP e4m3 copies of the frozen LLM weights (`DeSTA25AudioModel.set_decode_weights`)."""
+    kind = str(cfg.trainer.get("decode_weights", "bf16"))
+    if kind not in DECODE_WEIGHTS:
+        raise ValueError(f"trainer.decode_weights={kind!r} is not supported (choose one of {', '.join(DECODE_WEIGHTS)})")
+    return kind
+
+
 def load_pretrained_weights(model, path: str) -> None:
     """Lightning-style {'state_dict': ...} with a 'model.' prefix (reference :73-83); tensors only."""
     import torch
@@ -222,12 +234,14 @@ def main(argv=None):
     os.makedirs(cfg.exp_dir, exist_ok=True)
     if cfg.get("resume_from_checkpoint") and cfg.get("init_from_pretrained_weights"):
         raise AssertionError("Cannot provide both resume_from_checkpoint and init_from_pretrained_weights")
+    decode_weights = decode_weights_kind(cfg)                               # a bad value fails here, before any GPU work
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device(f"cuda:{local}"))
     from desta.trainer.desta_trainer import DeSTA25Trainer
     model = create_model(cfg, device=f"cuda:{local}")
+    model.set_decode_weights(decode_weights)
     if cfg.get("init_from_pretrained_weights"):
         load_pretrained_weights(model, cfg.init_from_pretrained_weights)
     train_ds, eval_ds, collate, tok = create_datasets(cfg, model, rank)

@@ -131,8 +131,29 @@ int desta_gemm_set_persistent(int on);   /* = desta_gemm_set_option(0, on) */
  * the GEMM launch instead of by the fix-up launch (default 0), 6 = four-slot software-pipelined ring form of the 128x128 kernel:
  * 0 never, 1 (default) when the grid leaves one block per CU (<= 256 tiles), 2 always; 10 = the two-phase 256x256 kernel stops its
  * half-tile stream at the last K-tile (default 1; 0 = re-load dead slots as rounds 1-3 did); bit-identical results in every setting.
+ * 11 = pipeline depth of the weight-only FP8 skinny kernel (0 auto, else 162 / 164; act 0 only; same bits either way).
  * Options 7, 8 (round 3's de-synchronised start) and 9 (round 4's polynomial GELU) were removed and return DESTA_EINVAL. */
 int desta_gemm_set_option(int option, int value);
+
+/* ------------------------------------------------------------------------------------------
+ * Weight-only FP8 (W8A16) decode: the frozen LLM weights a second time as OCP e4m3fn bytes with one power-of-two fp32
+ * scale per output row, streamed by the projections of a KV-cached decode step (additive to ABI 8: no struct changes).
+ * Serves llm_model.generate, modeling_desta25.py:1419-1427 (the nn.Linear calls of
+ * TF:models/llama/modeling_llama.py:163-176 (MLP), 230-281 (attention projections), 480 (lm_head)) when the caller opts in;
+ * the default path keeps the bf16 weights.
+ *
+ * desta_quantize_rows_e4m3: w [rows, cols] bf16 (row stride ld elements) -> q [rows, cols] e4m3fn bytes (contiguous) and
+ *   scale [rows].  scale = 2^e with e the smallest integer such that amax(row) * 2^-e <= 448; an all-zero row gets 1.
+ *   q = e4m3fn(w / scale), round to nearest even (OCP encoding, not the MI300 fnuz one; nothing saturates by construction).
+ *   q * scale is exactly representable in bf16.
+ * desta_gemm_w8a16_nt: C[M,N] = epilogue( b_scale[n] * (A[M,K] . e4m3(B)[N,K]^T) ) for M <= 16, batch 1.  The descriptor is
+ *   desta_gemm_desc unchanged: B points at e4m3 bytes [N, K] ([2N, K] for act 4), ldb counts elements (= bytes, a multiple
+ *   of 16), b_scale [N] ([2N] for act 4: gate and up rows carry their own scales) fp32, 16-byte aligned.  Supported: act 0 and 4, residual, ldc,
+ *   a_rms_weight / a_rms_eps, alpha, fp32 or bf16 output; anything else returns DESTA_EINVAL.  e4m3 -> bf16 in registers
+ *   (exact), the bf16 skinny kernel's MFMA accumulation in the same K order, the row scale on the fp32 sum before any
+ *   rounding or activation: bit-identical to desta_gemm_bf16_nt on the dequantised weight bf16(q * scale). */
+int desta_quantize_rows_e4m3(const void* w_bf16, int rows, int cols, int64_t ld, uint8_t* q, float* scale, void* stream);
+int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Global-norm clip + Adafactor over a flat fp32 arena.

@@ -4,7 +4,11 @@ rate of the decode GEMMs (bytes of frozen LLM weights read per token / token tim
 
   python tools/decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 8] [--ctx 64] [--prompt-tail 16] [--new 64]
                                [--do-sample --temperature T --top-p P --top-k K --min-p M --repetition-penalty R]
+                               [--weights {bf16,fp8}] [--ab [--rounds R]]
 Without --do-sample the decode is greedy (with --repetition-penalty, through the full-chain sampler kernel).
+--weights: what the decode steps stream (`set_decode_weights`; fp8 = weight-only OCP e4m3, half the bytes).  --ab alternates
+bf16 and fp8 in ONE process on one model (R rounds of bf16, fp8) and prints one line per leg and round plus a summary with the
+spread over the rounds: the bf16 leg of the same process is the yardstick, never a number from another box.
 """
 import argparse
 import json
@@ -30,6 +34,9 @@ def main():
     ap.add_argument("--top-k", type=int, default=None)
     ap.add_argument("--min-p", type=float, default=None)
     ap.add_argument("--repetition-penalty", type=float, default=None)
+    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--ab", action="store_true", help="alternate bf16 / fp8 decode weights in this process")
+    ap.add_argument("--rounds", type=int, default=3, help="--ab: alternations")
     a = ap.parse_args()
     gen = dict(do_sample=a.do_sample, temperature=a.temperature, top_p=a.top_p, top_k=a.top_k, min_p=a.min_p,
                repetition_penalty=a.repetition_penalty)
@@ -46,31 +53,56 @@ def main():
               "context_batch_start_positions": t["batch_start_positions"], "batch_features": mel,
               "batch_transcription_ids": t["batch_transcription_ids"]}
     S = t["input_ids"].shape[1]
-    res = []
-    for new in (1, a.new):
-        best = None
-        for _ in range(a.repeat):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            ids = model._generate_step(inputs, pad_token_id=0, max_new_tokens=new, eos_token_id=[], **gen)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            best = dt if best is None else min(best, dt)
-        assert ids.shape == (B, new)
-        res.append(best)
-    prompt_ms = res[0] * 1e3
-    tok_ms = (res[1] - res[0]) * 1e3 / (a.new - 1)
     c = cfg.llm_config
     per_layer = (c.num_attention_heads + 2 * c.num_key_value_heads) * c.head_dim * c.hidden_size + c.num_attention_heads * c.head_dim * c.hidden_size \
         + 3 * c.hidden_size * c.intermediate_size
-    wbytes = 2 * (c.num_hidden_layers * per_layer + c.vocab_size * c.hidden_size)
+    welems = c.num_hidden_layers * per_layer + c.vocab_size * c.hidden_size
     mode = "sample " + " ".join(f"{k}={v}" for k, v in gen.items() if k != "do_sample" and v is not None) if a.do_sample else \
         ("greedy" + (f" repetition_penalty={a.repetition_penalty}" if a.repetition_penalty is not None else ""))
-    print(json.dumps({"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "prompt_ms": round(prompt_ms, 2),
-                      "ms_per_token_step": round(tok_ms, 3), "tokens_per_s": round(B / tok_ms * 1e3, 1),
-                      "weight_bytes_per_step": wbytes, "weight_stream_GBps": round(wbytes / tok_ms / 1e6, 1),
-                      "hbm_peak_GBps": 8000}))
 
+    def leg(kind):
+        model.set_decode_weights(kind)
+        res = []
+        for new in (1, a.new):
+            best = None
+            for _ in range(a.repeat):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ids = model._generate_step(inputs, pad_token_id=0, max_new_tokens=new, eos_token_id=[], **gen)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                best = dt if best is None else min(best, dt)
+            assert ids.shape == (B, new)
+            res.append(best)
+        prompt_ms = res[0] * 1e3
+        tok_ms = (res[1] - res[0]) * 1e3 / (a.new - 1)
+        wbytes = welems * (1 if kind == "fp8" else 2)
+        r = {"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "decode_weights": kind, "prompt_ms": round(prompt_ms, 2),
+             "ms_per_token_step": round(tok_ms, 3), "tokens_per_s": round(B / tok_ms * 1e3, 1),
+             "weight_bytes_per_step": wbytes, "weight_stream_GBps": round(wbytes / tok_ms / 1e6, 1), "hbm_peak_GBps": 8000}
+        print(json.dumps(r), flush=True)
+        return r
+
+    if not a.ab:
+        leg(a.weights)
+        return
+    leg("fp8")                                                               # warm-up: quantise once, touch both paths
+    runs = {"bf16": [], "fp8": []}
+    for _ in range(a.rounds):
+        for kind in ("bf16", "fp8"):
+            if kind == "fp8":
+                model.set_decode_weights("fp8")
+                model.llm._fp8_decode_weights()                              # (re-made after the bf16 leg freed them: outside the timed region)
+            runs[kind].append(leg(kind)["ms_per_token_step"])
+    lo = {k: min(v) for k, v in runs.items()}
+    hi = {k: max(v) for k, v in runs.items()}
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+    print(json.dumps({"ab": f"{a.config} B={B} prompt={S} new={a.new} {mode}", "rounds": a.rounds,
+                      "bf16_ms_per_step": runs["bf16"], "fp8_ms_per_step": runs["fp8"],
+                      "spread_ms": {k: round(hi[k] - lo[k], 3) for k in runs},
+                      "median_speedup": round(med["bf16"] / med["fp8"], 3),
+                      "margin_ms_worst_case": round(lo["bf16"] - hi["fp8"], 3),
+                      "fp8_faster_beyond_spread": bool(lo["bf16"] - hi["fp8"] > max(hi[k] - lo[k] for k in runs))}))
 
 if __name__ == "__main__":
     main()
