@@ -4,6 +4,8 @@
 //                    cat(audio_features, transcription_embeddings) at each start position)
 //   CE ............. TF:loss/loss_utils.py:49-71 (`ForCausalLMLoss`: fp32 upcast of the bf16 logits,
 //                    labels shifted left by one, mean over labels != -100) and its autograd backward
+//   token logprobs . the same fp32 log-softmax, kept per target row and with the logits left intact (scoring: ranking answer
+//                    options by log-likelihood); compact_labels + 1 of desta_target_rows is its label vector (row i predicts it)
 //   tap mix ........ modeling_desta25.py:600-604 (softmax(layer_weights) weighted sum over the 4 taps)
 #include "common.h"
 #include "desta_hip.h"
@@ -215,6 +217,99 @@ __global__ __launch_bounds__(1024) void ce_row_reg_k(bf16_t* __restrict__ logits
     }
 }
 
+// Token log-probabilities (scoring): logprob[r] = x[r, lab] - logsumexp(x[r, :V]) of a bf16 row, READ ONLY — the quantity
+// ce_row_k folds into the mean loss before it overwrites the row with its gradient.  One 1024-thread block per row, one pass:
+// every thread keeps a running (maximum m, sum s of exp(x - m)) pair, rescaled once per 16-byte chunk; pairs merge in a fixed
+// order (wave butterfly, then the 16 waves in turn), so a row's result does not depend on timing.  The row is cut into the
+// elements in front of the first 16-byte boundary, whole 16-byte chunks (four loads in flight per thread) and a tail, so rows
+// of any alignment (ld % 8 != 0) take the vector loads.
+// is_top1: the label is torch.argmax's pick (first index of the row maximum, as sample_greedy_k) iff no entry exceeds x[lab]
+// (m <= x[lab]) and no entry in FRONT of it reaches x[lab] (`early`; a chunk that lies wholly in front is judged by its maximum).
+constexpr int LPT = 1024;
+
+// (m, s) <- (m, s) merged with (m2, s2); -inf maxima (no finite entry yet) carry zero mass and never reach an exponent as inf - inf
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+    const float mn = fmaxf(m, m2), ms = mn == -INFINITY ? 0.f : mn;
+    s = s * __expf(m - ms) + s2 * __expf(m2 - ms);
+    m = mn;
+}
+
+__global__ __launch_bounds__(LPT) void token_logprob_k(const bf16_t* __restrict__ logits, long ld, const long* __restrict__ labels,
+                                                       int V, float* __restrict__ logprob, unsigned char* __restrict__ is_top1) {
+    __shared__ float red_m[LPT / 64], red_s[LPT / 64];
+    __shared__ int red_e[LPT / 64];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const long tgt = labels[r];
+    if (tgt < 0 || tgt >= V) {                                   // ignored (-100) or out of range: nothing of the row is read
+        if (tid == 0) {
+            logprob[r] = 0.f;
+            if (is_top1) is_top1[r] = 0;
+        }
+        return;
+    }
+    const bf16_t* row = logits + (long)r * ld;
+    const int lab = (int)tgt;
+    const float xl = bf2f(row[lab]);
+    float m = -INFINITY, s = 0.f;
+    int early = 0;
+    auto one = [&](int c, bf16_t b) {
+        const float x = bf2f(b);
+        early |= (c < lab) & (x >= xl);
+        lse_merge(m, s, x, 1.0f);
+    };
+    auto chunk = [&](int c0, const u16x8& v) {
+        float x[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = bf2f(v[e]);
+        const float cm = fmaxf(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])), fmaxf(fmaxf(x[4], x[5]), fmaxf(x[6], x[7])));
+        if (c0 + 8 <= lab) early |= cm >= xl;
+        else if (c0 < lab) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) early |= (c0 + e < lab) & (x[e] >= xl);
+        }
+        const float mn = fmaxf(m, cm), ms = mn == -INFINITY ? 0.f : mn;
+        float a = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a += __expf(x[e] - ms);
+        s = s * __expf(m - ms) + a;
+        m = mn;
+    };
+    const int head = min(V, (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 1));      // elements in front of the first 16-byte boundary
+    const int n8 = (V - head) >> 3;
+    const bf16_t* body = row + head;
+    if (tid < head) one(tid, row[tid]);
+    int g = tid;
+    for (; g + 3 * LPT < n8; g += 4 * LPT) {
+        const u16x8 v0 = *(const u16x8*)(body + (long)g * 8);
+        const u16x8 v1 = *(const u16x8*)(body + (long)(g + LPT) * 8);
+        const u16x8 v2 = *(const u16x8*)(body + (long)(g + 2 * LPT) * 8);
+        const u16x8 v3 = *(const u16x8*)(body + (long)(g + 3 * LPT) * 8);
+        chunk(head + g * 8, v0);
+        chunk(head + (g + LPT) * 8, v1);
+        chunk(head + (g + 2 * LPT) * 8, v2);
+        chunk(head + (g + 3 * LPT) * 8, v3);
+    }
+    for (; g < n8; g += LPT) chunk(head + g * 8, *(const u16x8*)(body + (long)g * 8));
+    for (int c = head + n8 * 8 + tid; c < V; c += LPT) one(c, row[c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+        lse_merge(m, s, m2, s2);
+        early |= __shfl_xor(early, o, 64);
+    }
+    if ((tid & 63) == 0) { red_m[tid >> 6] = m; red_s[tid >> 6] = s; red_e[tid >> 6] = early; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < LPT / 64; ++w) {
+            lse_merge(m, s, red_m[w], red_s[w]);
+            early |= red_e[w];
+        }
+        // x[lab] - m is exact in fp32 for bf16 inputs of like magnitude; a -inf label entry has probability 0
+        logprob[r] = xl == -INFINITY ? -INFINITY : (xl - m) - logf(s);
+        if (is_top1) is_top1[r] = (xl >= m && !early) ? 1 : 0;
+    }
+}
+
 __global__ __launch_bounds__(256) void ce_finish_k(const float* __restrict__ row_loss, int M, const float* __restrict__ scal,
                                                    float* __restrict__ loss) {
     __shared__ float red[4];
@@ -379,6 +474,16 @@ extern "C" int desta_causal_lm_loss(void* logits, int64_t ld, const int64_t* lab
 #undef CE_ARGS
     hipLaunchKernelGGL(ce_finish_k, dim3(1), dim3(256), 0, st, (const float*)row_loss, M, (const float*)scal, loss);
     DESTA_CHECK_LAUNCH("causal_lm_loss");
+    return DESTA_OK;
+}
+
+extern "C" int desta_token_logprobs(const void* logits_bf16, int64_t ld, const int64_t* labels, int rows, int vocab,
+                                    float* logprob, uint8_t* is_top1, void* stream) {
+    DESTA_CHECK_ARG(logits_bf16 && labels && logprob, "token_logprobs: null argument");
+    DESTA_CHECK_ARG(rows > 0 && vocab > 0 && ld >= vocab, "token_logprobs: bad shape");
+    hipLaunchKernelGGL(token_logprob_k, dim3(rows), dim3(LPT), 0, (hipStream_t)stream, (const bf16_t*)logits_bf16, (long)ld,
+                       (const long*)labels, vocab, logprob, is_top1);
+    DESTA_CHECK_LAUNCH("token_logprobs");
     return DESTA_OK;
 }
 

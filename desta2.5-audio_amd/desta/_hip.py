@@ -415,6 +415,7 @@ _gather = _sig("desta_gather_rows_bf16", vp, vp, i32, i32, vp, vp)
 lib.desta_ce_workspace_floats.restype = c_size_t
 lib.desta_ce_workspace_floats.argtypes = [i32, i32]
 _ce = _sig("desta_causal_lm_loss", vp, i64, vp, i32, i32, i32, vp, vp, i32, vp)
+_token_logprobs = _sig("desta_token_logprobs", vp, i64, vp, i32, i32, vp, vp, vp)
 _mix_fwd = _sig("desta_tap_mix_fwd", vp, vp, i32, i32, i32, i32, vp, vp)
 _mix_bwd = _sig("desta_tap_mix_bwd", vp, vp, vp, i32, i32, i32, i32, vp, vp, vp)
 
@@ -432,6 +433,14 @@ def causal_lm_loss(logits, ld, labels, batch, seq, vocab, loss, write_grad=True)
     ws = scratch(lib.desta_ce_workspace_floats(batch, seq), logits.device, "ce")
     check(_ce(p(logits), ld, p(labels), batch, seq, vocab, p(loss), p(ws), int(write_grad), stream()),
           "desta_causal_lm_loss")
+
+
+@_profiled("token_logprobs", lambda logits, ld, labels, rows, vocab, out, is_top1=None: 2 * rows * vocab)
+def token_logprobs(logits, ld, labels, rows, vocab, out, is_top1=None):
+    """out[r] = log_softmax(logits[r, :vocab])[labels[r]] (fp32) of bf16 rows with stride ld, which stay untouched; row r predicts
+    labels[r] (int64; negative or >= vocab: ignored, 0).  is_top1 (uint8 [rows], optional): the label is the row's argmax
+    (include/desta_hip.h desta_token_logprobs)."""
+    check(_token_logprobs(p(logits), ld, p(labels), rows, vocab, p(out), p(is_top1), stream()), "desta_token_logprobs")
 
 
 def tap_mix_fwd(x, lw, taps, batch, prompt, d, out):

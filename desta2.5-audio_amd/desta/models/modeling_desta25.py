@@ -416,6 +416,35 @@ class GenerationOutput:
     text: list
 
 
+@dataclass
+class ScoreOutput:
+    """`score_batch`: log-likelihood of every row's target tokens under the model (targets = labels != -100 after the causal shift)."""
+    sum_logprob: torch.Tensor          # [B] fp32: sum of the row's token log-probs
+    n_tokens: torch.Tensor             # [B] int64: target tokens of the row
+    token_logprobs: list               # B 1-D fp32 tensors, sequence order
+    top1_match: torch.Tensor           # [B] int64: target tokens that are the argmax of their logits row
+    loss: torch.Tensor                 # the scalar `forward` returns for the same batch (token-mean CE)
+
+
+@dataclass
+class ChoiceScores:
+    """`score`: one conversation, ranked answer options."""
+    scores: torch.Tensor               # [n_choices] fp32: sum of token log-probs ("sum") or that sum / n_tokens ("mean")
+    best: int                          # argmax of `scores`
+    token_logprobs: list               # n_choices 1-D fp32 tensors: the choice's tokens, then EOS
+    n_tokens: torch.Tensor             # [n_choices] int64
+
+
+def check_score_args(choices, normalize) -> None:
+    if normalize not in ("sum", "mean"):
+        raise ValueError(f"`normalize` has to be \"sum\" or \"mean\", but is {normalize!r}")
+    if not isinstance(choices, (list, tuple)) or len(choices) == 0:
+        raise ValueError("`choices` has to be a non-empty list of strings")
+    for c in choices:
+        if not isinstance(c, str) or len(c) == 0:
+            raise ValueError(f"every choice has to be a non-empty string, got {c!r}")
+
+
 class _Out:
     """`CausalLMOutputWithPast`-shaped result (`.loss` 0-d fp32 tensor, `.logits` [B,S,V])."""
 
@@ -2154,8 +2183,9 @@ class DeSTA25AudioModel:
             hit = self._slot_cache[key] = (pos.to(self.device), val.to(self.device), pos.to(self.device, torch.int32))
         return hit
 
-    def _src_rows(self, input_ids, batch_transcription_ids, batch_start_positions, audio_lengths):
-        """int32 map [B*S]: >=0 token row of the embedding table, <0 -(audio_row+1)."""
+    def _src_rows(self, input_ids, batch_transcription_ids, batch_start_positions, audio_lengths, audio_index=None):
+        """int32 map [B*S]: >=0 token row of the embedding table, <0 -(audio_row+1).  audio_index[a] (optional): the audio whose
+        connector rows span a reads, when several spans share one encoded audio (`score`); default: span a reads audio a."""
         B, S = input_ids.shape
         K = self.audio_tokens
         src = input_ids.to(torch.int32).clone()
@@ -2164,6 +2194,8 @@ class DeSTA25AudioModel:
             assert start + K + batch_transcription_ids[a].numel() <= S, "audio span exceeds the sequence"
         if starts:
             pos, val, _ = self._audio_slots(starts, B, S, False)
+            if audio_index is not None:
+                val = -(torch.tensor(audio_index, dtype=torch.int32).view(-1, 1) * K + torch.arange(K, dtype=torch.int32) + 1).view(-1).to(src.device)
             src.view(-1).index_copy_(0, pos, val)                             # one launch for every audio span of the batch
         for a, (row, start) in enumerate(starts):
             tr = batch_transcription_ids[a].reshape(-1)
@@ -2192,6 +2224,9 @@ class DeSTA25AudioModel:
         if labels is not None:
             labels = self._h2d(labels)
         N_audio = len(batch_start_positions)
+        # score(): audio_index[a] = row of batch_features that span a splices in (every answer option reads the one encoded audio)
+        audio_index = kwargs.get("audio_index")
+        N_enc = N_audio if audio_index is None or N_audio == 0 else int(batch_features.shape[0])
         with torch.cuda.device(dev):
             if self._weights_dirty:
                 self.refresh_weights()
@@ -2203,20 +2238,27 @@ class DeSTA25AudioModel:
             if N_audio > 0 or self.llm.lora is not None:
                 self._fwd_count += 1
             if N_audio > 0:
-                assert len(batch_start_positions) == len(batch_transcription_ids) == batch_features.shape[0], \
+                assert len(batch_start_positions) == len(batch_transcription_ids) == (batch_features.shape[0] if audio_index is None else len(audio_index)), \
                     "batch_start_positions, batch_transcription_ids, audio_features, speech_feature_lengths must have the same length."
-                self._encode(batch_features, N_audio)
+                self._encode(batch_features, N_enc)
                 self.connector.p_drop = cfg.qformer_dropout if self.training else 0.0
                 self.connector.seed_base = seed_base
-                af = self.connector.forward(self.enc_all, N_audio)
-                src = self._src_rows(input_ids, [self._h2d(t) for t in batch_transcription_ids], batch_start_positions, None)
+                af = self.connector.forward(self.enc_all, N_enc)
+                if self.orca is not None and audio_index is not None:
+                    # ORCA pairs audio row b with text row b: repeat the encoded audios' global tokens per span (the encoder ran once)
+                    af = af.view(N_enc, -1, af.shape[-1])[torch.as_tensor(audio_index, device=dev)].reshape(-1, af.shape[-1]).contiguous()
+                src = self._src_rows(input_ids, [self._h2d(t) for t in batch_transcription_ids], batch_start_positions, None,
+                                     audio_index=None if self.orca is not None else audio_index)
             else:
                 src = input_ids.to(torch.int32).reshape(-1).contiguous()
             kv_start = (attention_mask == 0).sum(dim=1).to(torch.int32).contiguous()
             h = cfg.llm_config.hidden_size
+            # score_batch(): eval forward with the lm_head on the target rows only (batch-major grid; the logits stay logits)
+            compact_eval = bool(kwargs.get("compact_targets", False)) and labels is not None and not self.training
             if self.orca is not None:
                 return self._forward_orca(input_ids, attention_mask, batch_transcription_ids, batch_start_positions, labels, af, src, kv_start, N_audio,
-                                          keep_logits=bool(kwargs.get("keep_logits", False)))
+                                          keep_logits=bool(kwargs.get("keep_logits", False)),
+                                          target_rows=self._target_rows(labels, B, S) if compact_eval else None, audio_index=audio_index)
 
             def fill(buf):
                 H.embed_gather(self.llm.embed, af, src, B * S, h, buf)
@@ -2228,9 +2270,11 @@ class DeSTA25AudioModel:
                 s_major = True
                 src = src.view(B, S).t().contiguous().view(-1)
                 target_rows = self._target_rows(labels, B, S, s_major=True)
+            elif compact_eval:
+                target_rows = self._target_rows(labels, B, S)
             logits = self.llm.forward(fill, B, S, kv_start, labels, self.training, target_rows=target_rows, s_major=s_major)
             V = cfg.llm_config.vocab_size
-            out_logits = logits.view(B, S, self.llm.Vp)[:, :, :V]
+            out_logits = None if compact_eval else logits.view(B, S, self.llm.Vp)[:, :, :V]
             loss = None
             if labels is not None:
                 labels = labels.to(dev).contiguous()
@@ -2248,7 +2292,8 @@ class DeSTA25AudioModel:
                              has_grad=labels is not None and self.training and (N_audio > 0 or self.llm.lora is not None), s_major=s_major)
         return _Out(loss, out_logits)
 
-    def _forward_orca(self, input_ids, attention_mask, batch_transcription_ids, batch_start_positions, labels, af, src, kv_start, N_audio, keep_logits=False):
+    def _forward_orca(self, input_ids, attention_mask, batch_transcription_ids, batch_start_positions, labels, af, src, kv_start, N_audio, keep_logits=False,
+                      target_rows=None, audio_index=None):
         """The ORCA branch of the reference's forward (modeling_desta25.py:775-841): global tokens spliced at the audio
         positions, the local tokens injected behind every decoder layer through the gated cross-attention, LM loss + `orca_losses`
         (the trainer adds them up, desta_trainer.py:56-92).  Batch-major token grid; in training mode the activations the backward needs
@@ -2262,7 +2307,13 @@ class DeSTA25AudioModel:
         if N_audio > 0:
             rows = [int(r) for r, _ in batch_start_positions]
             assert N_audio == B and rows == list(range(B)), "orca_hybrid: one audio per text row, in row order"
-            local16 = orca.local_forward(self.enc_all, N_audio)
+            if audio_index is None:
+                local16 = orca.local_forward(self.enc_all, N_audio)
+            else:                                                                # score(): local tokens of each encoded audio, repeated per text row
+                n_enc = int(self.enc_all.shape[1]) // cfg.encoder_config.max_source_positions
+                local16 = orca.local_forward(self.enc_all, n_enc)
+                if local16 is not None:
+                    local16 = local16.view(n_enc, -1, hdim)[torch.as_tensor(audio_index, device=dev)].reshape(-1, hdim).contiguous()
             Kg = cfg.orca_global_num_tokens
             spans = [(int(r), int(s) + Kg, int(s) + Kg + int(t.numel())) for (r, s), t in zip(batch_start_positions, batch_transcription_ids)]
             orca.begin(af, local16, B, S, spans, self.training, save=need_grad)
@@ -2273,11 +2324,11 @@ class DeSTA25AudioModel:
 
         def fill(buf):
             H.embed_gather(self.llm.embed, af, src, B * S, hdim, buf)
-        logits = self.llm.forward(fill, B, S, kv_start, labels, need_grad, layer_hook=hook)
-        out_logits = logits.view(B, S, self.llm.Vp)[:, :, :V]
+        logits = self.llm.forward(fill, B, S, kv_start, labels, need_grad, layer_hook=hook, target_rows=target_rows)
+        out_logits = None if target_rows is not None else logits.view(B, S, self.llm.Vp)[:, :, :V]
         loss = None
         if labels is not None:
-            if need_grad:                                                    # dlogits overwrite the logits buffer (as on the qformer_1 path)
+            if need_grad and out_logits is not None:                         # dlogits overwrite the logits buffer (as on the qformer_1 path)
                 out_logits = out_logits.clone() if keep_logits else None
             loss = self.llm.loss_and_grad(labels.to(dev).contiguous(), write_grad=need_grad).clone().view(())
         out = _Out(loss, out_logits)
@@ -2417,6 +2468,24 @@ class DeSTA25AudioModel:
         `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))`."""
         check_sampling_args(top_k, min_p, repetition_penalty)
         extra = dict(top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty)
+        tok, inputs, audios, texts = self._chat_inputs(messages)
+        if not audios:
+            # no audio: plain LLM generation on the chat template; stops on eos or <|eot_id|>
+            ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
+                                      do_sample=do_sample, eos_token_id=[tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")], seed=seed,
+                                      prompt_in_history=True, **extra)
+            rows = [r.tolist() for r in ids]
+            return GenerationOutput(text=tok.batch_decode(rows, skip_special_tokens=True), audios=[], generated_ids=rows)
+        self._last_generate_inputs = inputs
+        ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
+                                  do_sample=do_sample, seed=seed, **extra)
+        return GenerationOutput(text=tok.batch_decode(ids, skip_special_tokens=True), audios=list(zip(audios, texts)), generated_ids=ids.tolist())
+
+    def _chat_inputs(self, messages):
+        """The front half of the reference's chat-level `generate` (modeling_desta25.py:1491-1700), shared by `generate` and
+        `score`: chat template with the generation prompt, audio decode, VAD / ASR rules, log-mel, `<start_audio>` / `<end_audio>`
+        indicator, placeholder expansion, left-padded tokenisation, pad-shifted start positions, transcription ids.
+        -> (tokenizer, `_generate_step` inputs, audios, texts); a chat without audio has no features and no spans."""
         from ..trainer.data.simple_dataset import prepare_audio_context_and_start_positions
         from ..utils.audio import AudioSegment
         if not hasattr(self, "tokenizer") or not hasattr(self, "processor"):
@@ -2433,15 +2502,10 @@ class DeSTA25AudioModel:
                 audios += [a["audio"] for a in au]
                 texts += [a.get("text") for a in au]
         if not audios:
-            # no audio: plain LLM generation on the chat template; stops on eos or <|eot_id|>
             enc = tok(tok.apply_chat_template(conversations, tokenize=False, add_generation_prompt=True), return_tensors="pt", padding=True)
             inputs = {"context_input_ids": enc["input_ids"], "context_attention_mask": enc["attention_mask"],
                       "context_batch_start_positions": [], "batch_transcription_ids": [], "batch_features": None}
-            ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
-                                      do_sample=do_sample, eos_token_id=[tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")], seed=seed,
-                                      prompt_in_history=True, **extra)
-            rows = [r.tolist() for r in ids]
-            return GenerationOutput(text=tok.batch_decode(rows, skip_special_tokens=True), audios=[], generated_ids=rows)
+            return tok, inputs, audios, texts
         waves, need_asr = [], []
         for i, (a, t) in enumerate(zip(audios, texts)):
             if isinstance(a, str) and not os.path.exists(a):
@@ -2475,10 +2539,89 @@ class DeSTA25AudioModel:
                   "batch_transcription_ids": [tok.encode(t, add_special_tokens=False, return_tensors="pt").long() for t in texts],
                   "context_input_ids": enc["input_ids"], "context_attention_mask": enc["attention_mask"],
                   "context_batch_start_positions": [(i, s + pad[i]) for i in range(len(starts)) for s in starts[i]]}
-        self._last_generate_inputs = inputs
-        ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
-                                  do_sample=do_sample, seed=seed, **extra)
-        return GenerationOutput(text=tok.batch_decode(ids, skip_special_tokens=True), audios=list(zip(audios, texts)), generated_ids=ids.tolist())
+        return tok, inputs, audios, texts
+
+    # -- scoring: token log-probabilities ------------------------------------------------------------------------
+    @torch.no_grad()
+    def score_batch(self, input_ids, attention_mask, batch_features, batch_transcription_ids, batch_start_positions, labels, **kwargs) -> ScoreOutput:
+        """Log-likelihood of every row's target tokens (labels != -100 after the causal shift): `forward`'s inputs, in eval mode
+        (no Q-Former dropout; the training flag is restored) and without gradients.  The prefill runs once with the lm_head on
+        the target rows only (`desta_target_rows`, batch-major grid), the loss kernel reads those compact logits without
+        writing a gradient, and `desta_token_logprobs` reads them again for the per-token values; a row's tokens are one
+        contiguous segment of the compact list, summed in a fixed order, so two calls agree bit for bit.  Scoring runs the
+        prefill kernels on the bf16 weights: `set_decode_weights("fp8")` changes the KV-cached decode steps only, not this.
+        ORCA: the auxiliary losses of the forward are computed once and are not part of `loss` (the LM loss, as `forward`)."""
+        if labels is None:
+            raise ValueError("score_batch() needs labels: they select the tokens to score")
+        B, S = input_ids.shape
+        was_training = self.training
+        self.training = False
+        try:
+            out = self.forward(input_ids, attention_mask, batch_features, batch_transcription_ids, batch_start_positions, labels=labels,
+                               compact_targets=True, **kwargs)
+            dev = self.device
+            lab = labels.detach().to("cpu")
+            n_host = (lab[:, 1:] != -100).sum(dim=1)                               # row (b, s) predicts labels[b, s + 1]
+            n_list = [int(n) for n in n_host.tolist()]
+            _, lab_c, Mc = self.llm.compact
+            assert Mc == sum(n_list), "compact target rows do not match the labels"
+            with torch.cuda.device(dev):
+                lp = torch.zeros(Mc, dtype=F32, device=dev)
+                top = torch.zeros(Mc, dtype=torch.uint8, device=dev)
+                if Mc > 0:
+                    # compact row i predicts lab_c[1 + i] (the layout desta_causal_lm_loss(batch = 1) consumes, shifted by one)
+                    H.token_logprobs(self.llm.logits, self.llm.Vp, lab_c[1:], Mc, self.config.llm_config.vocab_size, lp, top)
+                n_tokens = n_host.to(dev)
+                # segments of the compact list -> [B, longest] (zero padded), one fixed-order sum per row
+                T = max(n_list) if n_list else 0
+                seg = torch.arange(T, device=dev).unsqueeze(0) < n_tokens.unsqueeze(1)
+                lp_pad = torch.zeros(B, T, dtype=F32, device=dev)
+                top_pad = torch.zeros(B, T, dtype=torch.int64, device=dev)
+                lp_pad[seg] = lp
+                top_pad[seg] = top.to(torch.int64)
+                return ScoreOutput(sum_logprob=lp_pad.sum(dim=1), n_tokens=n_tokens, token_logprobs=list(torch.split(lp, n_list)),
+                                   top1_match=top_pad.sum(dim=1), loss=out.loss)
+        finally:
+            self.training = was_training
+
+    def score(self, messages, choices, normalize="sum") -> ChoiceScores:
+        """Rank answer options by their log-likelihood as the assistant's reply to ONE conversation (`generate`'s messages schema,
+        with or without audios): the context is built exactly as `generate` builds it (`_chat_inputs`), every choice's token ids
+        (`add_special_tokens=False`) and the tokenizer's EOS are appended, rows are left-padded to a common length and only the
+        choice tokens and the EOS carry labels.  Each audio is decoded, log-mel'd and encoded ONCE: every row's audio span
+        points at the same connector output rows.  normalize: "sum" (log-likelihood) or "mean" (per token, length-normalised)."""
+        check_score_args(choices, normalize)
+        tok, inputs, audios, _ = self._chat_inputs(messages)
+        ctx_ids, ctx_mask = inputs["context_input_ids"], inputs["context_attention_mask"]
+        if ctx_ids.shape[0] != 1:
+            raise ValueError("score() takes one conversation")
+        ctx = ctx_ids[0][ctx_mask[0].bool()].tolist()
+        pad0 = int(ctx_ids.shape[1]) - len(ctx)
+        tails = []
+        for c in choices:
+            ids = tok.encode(c, add_special_tokens=False)
+            ids = ids[0].tolist() if torch.is_tensor(ids) else list(ids)
+            if not ids:
+                raise ValueError(f"choice {c!r} has no tokens")
+            tails.append(ids + [int(tok.eos_token_id)])
+        n, S = len(tails), len(ctx) + max(len(t) for t in tails)
+        input_ids = torch.full((n, S), int(tok.pad_token_id), dtype=torch.long)
+        attention_mask = torch.zeros(n, S, dtype=torch.long)
+        labels = torch.full((n, S), -100, dtype=torch.long)
+        starts, trs, audio_index = [], [], []
+        for i, t in enumerate(tails):
+            pad = S - len(ctx) - len(t)
+            input_ids[i, pad:] = torch.tensor(ctx + t)
+            attention_mask[i, pad:] = 1
+            labels[i, S - len(t):] = torch.tensor(t)
+            for a, (_, s0) in enumerate(inputs["context_batch_start_positions"]):
+                starts.append((i, int(s0) - pad0 + pad))
+                trs.append(inputs["batch_transcription_ids"][a])
+                audio_index.append(a)
+        extra = dict(audio_index=audio_index) if audios else {}
+        out = self.score_batch(input_ids, attention_mask, inputs["batch_features"], trs, starts, labels, **extra)
+        scores = out.sum_logprob if normalize == "sum" else out.sum_logprob / out.n_tokens.to(F32)
+        return ChoiceScores(scores=scores, best=int(scores.argmax()), token_logprobs=out.token_logprobs, n_tokens=out.n_tokens)
 
     def _target_rows(self, labels, B: int, S: int, s_major: bool = False):
         """Index list / compact labels / host-visible count of the rows that carry a target, on a side stream: it waits for

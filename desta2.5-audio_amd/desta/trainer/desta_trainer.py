@@ -471,7 +471,9 @@ class DeSTA25Trainer:
     # -- evaluation (desta_trainer.py:104-189): eval loss / perplexity + generation through `_generate_step` ----------
     def evaluate(self, eval_batches: Optional[Iterable[Dict[str, Any]]] = None, metric_key_prefix: str = "eval",
                  generation_kwargs: Optional[Dict[str, Any]] = None) -> Dict[str, float]:
-        """Eval-mode forward (no Q-Former dropout) for loss / ppl on every batch, then `_predict_step`.  Metrics keep the
+        """Eval-mode forward (no Q-Former dropout) for loss / ppl on every batch, then `_predict_step`.  The forward is
+        `score_batch`, whose per-token argmax flags come from the same logits: `eval_token_accuracy` = target tokens that are
+        the argmax / target tokens, summed over batches (and ranks) — teacher-forced next-token accuracy, no second pass.  Metrics keep the
         reference's names (`eval_loss`, `eval_ppl`); accuracy scoring needs the reference's text metrics and a tokenizer
         (`processing_class`) and is reported only when predictions could be decoded (`prediction_step_outputs`)."""
         dp = self.world > 1 and dist.is_available() and dist.is_initialized()
@@ -490,6 +492,7 @@ class DeSTA25Trainer:
         was_training = self.model.training
         self.model.eval()
         losses: List[torch.Tensor] = []
+        hits = torch.zeros(2, dtype=torch.float64, device=self.model.device)          # (target tokens that are the argmax, target tokens)
         self.prediction_step_outputs: List[Dict[str, Any]] = []
         try:
             for batch in eval_batches:
@@ -498,13 +501,15 @@ class DeSTA25Trainer:
                     continue
                 fwd = {k: batch[k] for k in ("input_ids", "attention_mask", "batch_features", "batch_transcription_ids",
                                              "batch_start_positions", "labels") if k in batch}
-                losses.append(self.model(**fwd).loss.detach().clone())
+                sc = self.model.score_batch(**fwd)
+                losses.append(sc.loss.detach().clone())
+                hits += torch.stack([sc.top1_match.sum(), sc.n_tokens.sum()]).double()
                 if "context_input_ids" in batch:
                     self._predict_step(batch, generation_kwargs)
         finally:
             self.model.train(was_training)
         ls = torch.stack(losses).double() if losses else torch.zeros(0, dtype=torch.float64, device=self.model.device)
-        agg = torch.stack([ls.sum(), torch.exp(ls).sum(), torch.tensor(float(len(losses)), dtype=torch.float64, device=self.model.device)])
+        agg = torch.stack([ls.sum(), torch.exp(ls).sum(), torch.tensor(float(len(losses)), dtype=torch.float64, device=self.model.device), hits[0], hits[1]])
         preds = self.prediction_step_outputs
         if sharded:
             if dist.get_backend() != "nccl":
@@ -517,7 +522,8 @@ class DeSTA25Trainer:
             self.prediction_step_outputs = preds
         cnt = float(agg[2])
         metrics = {f"{metric_key_prefix}_loss": float(agg[0]) / cnt if cnt else 0.0,
-                   f"{metric_key_prefix}_ppl": float(agg[1]) / cnt if cnt else 0.0}
+                   f"{metric_key_prefix}_ppl": float(agg[1]) / cnt if cnt else 0.0,
+                   f"{metric_key_prefix}_token_accuracy": float(agg[3]) / float(agg[4]) if float(agg[4]) else 0.0}
         # desta_trainer.py:134-152: predictions JSONL + accuracy report under <exp_dir>/results/val, accuracy metrics
         exp_dir = self._cfg_get("exp_dir")
         decoded = bool(preds) and all("prediction" in r and "label" in r for r in preds)

@@ -314,6 +314,19 @@ size_t desta_ce_workspace_floats(int batch, int seq);
 int desta_causal_lm_loss(void* logits, int64_t ld, const int64_t* labels, int batch, int seq, int vocab,
                          float* loss, float* workspace, int write_grad, void* stream);
 
+/* Token log-probabilities for scoring (multiple-choice ranking by log-likelihood; what `ForCausalLMLoss`
+ * TF:loss/loss_utils.py:49-71 averages, kept per token: -F.cross_entropy(..., reduction="none") and the argmax match).
+ * logits bf16 [rows, ld] (ld >= vocab, any alignment), READ ONLY — unlike desta_causal_lm_loss, whose buffer becomes dlogits.
+ * Row r predicts labels[r]: the caller does the causal shift.  compact_labels + 1 of desta_target_rows is already aligned
+ * this way (compact row i predicts compact_labels[1 + i]), so the compact lm_head grid is scored without another pass.
+ *   0 <= labels[r] < vocab:  logprob[r] = x[r, labels[r]] - logsumexp(x[r, :vocab]) in fp32, maximum subtracted first; -inf
+ *                            entries carry no mass, a -inf label entry gives -inf.  is_top1[r] (optional, may be NULL) = 1 iff
+ *                            labels[r] is the FIRST index of the row maximum (torch.argmax, as desta_sample_bf16's greedy mode).
+ *   labels[r] < 0 (-100) or >= vocab:  ignored, logprob[r] = 0, is_top1[r] = 0, the row is not read.
+ * One 1024-thread block per row, one pass over the row; fixed reduction order (bitwise reproducible). */
+int desta_token_logprobs(const void* logits_bf16, int64_t ld, const int64_t* labels, int rows, int vocab,
+                         float* logprob, uint8_t* is_top1 /* may be NULL */, void* stream);
+
 /* Connector tap mix (modeling_desta25.py:600-604): x fp32 [taps][batch*prompt][d], layer_weights
  * fp32 [prompt][taps]; out[b,k,:] = sum_j softmax(layer_weights[k,:])_j x[j,b,k,:]; and its backward. */
 int desta_tap_mix_fwd(const float* x, const float* layer_weights, int taps, int batch, int prompt, int d,
