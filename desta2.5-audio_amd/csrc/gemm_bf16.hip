@@ -1539,6 +1539,199 @@ __global__ __launch_bounds__(512, (COLS == 16 && (U == 2 || W8)) ? 2 : 1) void g
 #undef SK_MMA
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Wide skinny GEMM, 17 <= M <= 64 (decode at batch 17..64; desta_gemm_wide_nt).  The same weight streaming with MF = ceil(M/16)
+// activation fragments per weight fragment.  With the 16-column tile above a block would pull MF activation bytes from L2 per
+// weight byte (4 at M = 64), so an item here is 64 weight rows (T = 4 MFMA tiles) over all M rows: one 64-element K-chunk of a
+// wave is 8 KiB of bf16 weights against <= 8 KiB of activations (W8: 4 KiB of weight bytes, so 1.5 / 2 activation bytes per weight
+// byte at MF = 3 / 4; a 128-row item would restore 1 and needs 32 accumulator tiles, more than one block per CU holds).  The 8 waves of a block interleave the chunks of the item as above and
+// their partial tiles are reduced through LDS in wave order.  64-row tiles leave few items at N = 4096, so the host cuts K into
+// `ks` slices (a function of the tile and chunk counts only, never of M or of the grid): item = (slice, tile), slice s walks
+// chunks [s*cps, (s+1)*cps).  With ks > 1 a block stores the raw fp32 sums of its slice to the workspace slab [ks][M][weight rows]
+// and gemm_bf16_nt_skinny_wide_fixup_kernel adds the slices in slice order and runs the epilogue: every sum has one fixed order
+// whatever the grid, and no atomics.  Rows >= M and weight rows >= N are computed on clamped addresses and never stored.
+// SWIGLU: an item is 32 gate rows (tiles 0, 1) and the 32 matching up rows (tiles 2, 3); a lane holds gate and up of the same
+// output in acc[t] / acc[t + 2].  W8: as in the 16-row kernel (bytes -> bf16 fragments in registers, same MFMAs in the same order,
+// row scale on the reduced sum).
+template <int MF, bool W8>
+struct WideStage {
+    bf16x8 w0[4], w1[4], x0[MF], x1[MF];
+};
+template <int MF>
+struct WideStage<MF, true> {
+    u32x4 wq[4];
+    bf16x8 x0[MF], x1[MF];
+};
+struct WideCursor { int item, grp, tile, slice; };
+
+// silu(gate) * up with the rounding points of the unfused path (projection rounded to bf16, then swiglu_fwd)
+__device__ __forceinline__ u16x4 swiglu4_bf16(const f32x4& gs, const f32x4& us, float alpha) {
+    u16x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float gt = bf2f(f2bf(gs[e] * alpha)), uu = bf2f(f2bf(us[e] * alpha));
+        o[e] = f2bf(bf2f(f2bf(gt / (1.0f + __expf(-gt)))) * uu);
+    }
+    return o;
+}
+
+template <int MF, bool SWIGLU, bool W8>
+__global__ __launch_bounds__(512) void gemm_bf16_nt_skinny_wide_kernel(GemmArgs p, int ntiles, int ks, int cps, float* part) {
+    constexpr int T = 4;
+    __shared__ __attribute__((aligned(16))) char smem[8 * T * MF * 1024];
+    f32x4 (*red)[T * MF][64] = (f32x4 (*)[T * MF][64])smem;              // red[wave][t * MF + f][lane]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int ntot = SWIGLU ? 2 * p.N : p.N;                             // weight rows = columns of the partial slab
+    const bf16_t* Bz = p.B + g * 16;
+    const char* Bq = (const char*)p.B + g * 16;                          // W8: one byte per element
+    const bf16_t* ap[MF];
+#pragma unroll
+    for (int f = 0; f < MF; ++f) ap[f] = p.A + (long)min(f * 16 + r, p.M - 1) * p.lda + g * 16;
+    const int nchunks = p.K >> 6;
+    const int gpt = (cps + 7) >> 3;                                      // groups (one chunk per wave) per item
+    const int items = ntiles * ks;
+    const int my_items = ((int)blockIdx.x < items) ? (items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    const int G = my_items * gpt;
+    f32x4 acc[T][MF];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int f = 0; f < MF; ++f) acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    WideStage<MF, W8> sa, sb;
+    WideCursor lc = {(int)blockIdx.x, 0, (int)blockIdx.x % ntiles, (int)blockIdx.x / ntiles}, mc = lc;
+
+    auto advance = [&](WideCursor& c) {
+        if (++c.grp == gpt) { c.grp = 0; c.item += (int)gridDim.x; c.tile = c.item % ntiles; c.slice = c.item / ntiles; }
+    };
+    // weight row of MFMA tile t, row q of it; ok = it exists
+    auto wrow = [&](int tile, int t, int q, bool& ok) -> int {
+        if (SWIGLU) {
+            const int n = tile * 32 + (t & 1) * 16 + q;
+            ok = n < p.N;
+            return (t >= 2 ? p.N : 0) + min(n, p.N - 1);
+        }
+        const int n = tile * 64 + t * 16 + q;
+        ok = n < p.N;
+        return min(n, p.N - 1);
+    };
+#define WD_LOAD(S)                                                                          \
+    {                                                                                       \
+        const int cc = lc.slice * cps + wave + lc.grp * 8;                                  \
+        if (cc < min((lc.slice + 1) * cps, nchunks)) {                                      \
+            _Pragma("unroll") for (int t = 0; t < T; ++t) {                                 \
+                bool ok;                                                                    \
+                const long row = wrow(lc.tile, t, r, ok);                                   \
+                if constexpr (W8) {                                                         \
+                    S.wq[t] = *(const u32x4*)(Bq + row * p.ldb + (long)cc * 64);            \
+                } else {                                                                    \
+                    S.w0[t] = *(const bf16x8*)(Bz + row * p.ldb + (long)cc * 64);           \
+                    S.w1[t] = *(const bf16x8*)(Bz + row * p.ldb + (long)cc * 64 + 8);       \
+                }                                                                           \
+            }                                                                               \
+            _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                \
+                S.x0[f] = *(const bf16x8*)(ap[f] + (long)cc * 64);                          \
+                S.x1[f] = *(const bf16x8*)(ap[f] + (long)cc * 64 + 8);                      \
+            }                                                                               \
+        }                                                                                   \
+        advance(lc);                                                                        \
+    }
+#define WD_MMA(S)                                                                           \
+    {                                                                                       \
+        const int cc = mc.slice * cps + wave + mc.grp * 8;                                  \
+        if (cc < min((mc.slice + 1) * cps, nchunks)) {                                      \
+            _Pragma("unroll") for (int t = 0; t < T; ++t) {                                 \
+                bf16x8 w0, w1;                                                              \
+                if constexpr (W8) e4m3x16_to_bf16(S.wq[t], w0, w1);                         \
+                else { w0 = S.w0[t]; w1 = S.w1[t]; }                                        \
+                _Pragma("unroll") for (int f = 0; f < MF; ++f) {                            \
+                    acc[t][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, S.x0[f], acc[t][f], 0, 0, 0); \
+                    acc[t][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, S.x1[f], acc[t][f], 0, 0, 0); \
+                }                                                                           \
+            }                                                                               \
+        }                                                                                   \
+        if (mc.grp == gpt - 1) finish_item(mc.tile, mc.slice);                              \
+        advance(mc);                                                                        \
+    }
+    // the 8 waves' partial tiles, summed in wave order
+    auto reduced = [&](int t, int f) -> f32x4 {
+        f32x4 sum = red[0][t * MF + f][lane];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) sum += red[w][t * MF + f][lane];
+        return sum;
+    };
+    auto scaled = [&](f32x4 sum, int row) -> f32x4 {                     // W8: the weight row's scale, before any rounding or activation
+        if constexpr (W8) {
+            const float4 s = *(const float4*)(p.b_scale + row);
+            sum[0] *= s.x; sum[1] *= s.y; sum[2] *= s.z; sum[3] *= s.w;
+        }
+        return sum;
+    };
+    auto finish_item = [&](int tile, int slice) {
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int f = 0; f < MF; ++f) { red[wave][t * MF + f][lane] = acc[t][f]; acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        __syncthreads();
+        if (ks > 1) {                                                    // raw sums of this K-slice; the fix-up launch finishes them
+            for (int u = wave; u < T * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int row = wrow(tile, t, g * 4, ok);                // N % 4 == 0: the four rows exist together
+                if (ok && m < p.M) *(f32x4*)(part + ((long)slice * p.M + m) * ntot + row) = reduced(t, f);
+            }
+        } else if (SWIGLU) {
+            for (int u = wave; u < 2 * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int n = wrow(tile, t, g * 4, ok);
+                if (ok && m < p.M)
+                    *(u16x4*)((bf16_t*)p.C + (long)m * p.ldc + n) = swiglu4_bf16(scaled(reduced(t, f), n), scaled(reduced(t + 2, f), p.N + n), p.alpha);
+            }
+        } else {
+            for (int u = wave; u < T * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int n = wrow(tile, t, g * 4, ok);
+                if (ok && m < p.M) epilogue4(p, 0, m, n, scaled(reduced(t, f), n));
+            }
+        }
+        __syncthreads();                                                 // red is free again before the next item's partial tiles land
+    };
+
+    if (G > 0) WD_LOAD(sa)
+    for (int gi = 0; gi < G; gi += 2) {
+        if (gi + 1 < G) WD_LOAD(sb)
+        WD_MMA(sa)
+        if (gi + 2 < G) WD_LOAD(sa)
+        if (gi + 1 < G) WD_MMA(sb)
+    }
+#undef WD_LOAD
+#undef WD_MMA
+}
+
+// adds the K-slice slabs of the wide kernel in slice order and runs its epilogue; one thread per 4 consecutive outputs of a row
+template <bool SWIGLU>
+__global__ __launch_bounds__(256) void gemm_bf16_nt_skinny_wide_fixup_kernel(GemmArgs p, int ks, const float* part, const float* b_scale) {
+    const int n4 = p.N >> 2;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)p.M * n4) return;
+    const int m = (int)(idx / n4), n = (int)(idx % n4) * 4;
+    const int ntot = SWIGLU ? 2 * p.N : p.N;
+    auto total = [&](int row) -> f32x4 {
+        const float* q = part + (long)m * ntot + row;
+        f32x4 sum = *(const f32x4*)q;
+        for (int s = 1; s < ks; ++s) sum += *(const f32x4*)(q + (long)s * p.M * ntot);
+        if (b_scale) {
+            const float4 sc = *(const float4*)(b_scale + row);
+            sum[0] *= sc.x; sum[1] *= sc.y; sum[2] *= sc.z; sum[3] *= sc.w;
+        }
+        return sum;
+    };
+    if (SWIGLU) *(u16x4*)((bf16_t*)p.C + (long)m * p.ldc + n) = swiglu4_bf16(total(n), total(p.N + n), p.alpha);
+    else epilogue4(p, 0, m, n, total(n));
+}
+
 }  // namespace
 
 static int g_last_kernel = 0;      // kernel family of the most recent launch: 1 = 128x128, 2 = 256x256 (+ split-K fix-up), 3 = skinny
@@ -1787,6 +1980,72 @@ extern "C" int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scal
     else SK8_LAUNCH(2, false);
 #undef SK8_LAUNCH
     DESTA_CHECK_LAUNCH("gemm_w8a16_nt_skinny");
+    g_last_kernel = 3;
+    return DESTA_OK;
+}
+
+// Decode projections at batch 17..64: the wide skinny kernel.  b_scale == NULL: B is bf16; otherwise B holds e4m3 bytes and b_scale
+// one power-of-two scale per weight row (2N rows for act 4).  One path per M: M <= 16 belongs to desta_gemm_bf16_nt /
+// desta_gemm_w8a16_nt, and nothing beyond what a decode step asks for is accepted.
+extern "C" int desta_gemm_wide_nt(const desta_gemm_desc* d, const float* b_scale, void* stream) {
+    DESTA_CHECK_ARG(d && d->A && d->B && d->C, "gemm_wide: null operand");
+    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm_wide: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
+    DESTA_CHECK_ARG(d->M > 16 && d->M <= 64, "gemm_wide: M=%d, the wide weight-streaming kernel takes 17 <= M <= 64 (M <= 16: desta_gemm_bf16_nt / desta_gemm_w8a16_nt)", d->M);
+    DESTA_CHECK_ARG(d->act == 0 || d->act == 4, "gemm_wide: act %d unsupported (0, or 4 = SwiGLU over concatenated gate|up rows)", d->act);
+    DESTA_CHECK_ARG(d->K % BK == 0, "gemm_wide: K=%d must be a multiple of %d", d->K, BK);
+    DESTA_CHECK_ARG(d->N % 4 == 0, "gemm_wide: N=%d must be a multiple of 4", d->N);
+    DESTA_CHECK_ARG(d->lda % 8 == 0 && d->ldb % (b_scale ? 16 : 8) == 0 && d->ldc % 4 == 0,
+                    "gemm_wide: lda must be a multiple of 8, ldb of 8 (bf16) or 16 (e4m3), ldc of 4");
+    DESTA_CHECK_ARG(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0) && ((uintptr_t)b_scale % 16 == 0),
+                    "gemm_wide: operands and scales must be 16-byte aligned");
+    DESTA_CHECK_ARG(d->batch == 1, "gemm_wide: batch %d unsupported (1)", d->batch);
+    DESTA_CHECK_ARG(!d->bias && !d->preact && !d->aux && d->dropout_p == 0.f && !d->trans_a && !d->trans_b && !d->rope_cos_sin &&
+                    !d->out_f32 && !d->a_rms_weight,
+                    "gemm_wide: bias, preact, aux, dropout, transposed operands, the rotary epilogue, fp32 output and a_rms_weight are unsupported");
+    DESTA_CHECK_ARG(!d->residual || (d->ldr % 4 == 0 && !d->residual_f32), "gemm_wide: the residual is bf16 and ldr a multiple of 4");
+    DESTA_CHECK_ARG(d->act != 4 || !d->residual, "gemm_wide: act 4 takes no residual");
+    GemmArgs a = {};
+    a.A = (const bf16_t*)d->A; a.B = (const bf16_t*)d->B; a.C = d->C;
+    a.M = d->M; a.N = d->N; a.K = d->K;
+    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
+    a.res = d->residual; a.ldr = d->ldr;
+    a.act = d->act; a.alpha = d->alpha; a.drop_scale = 1.0f;
+    a.b_scale = b_scale;
+    // K-slices: enough items for one block per CU, at least 16 chunks (two per wave) each.  A function of the tile and chunk counts
+    // alone, so every M, both weight kinds and act 4 against its plain 2N-row form sum in the same order.
+    const int swiglu = d->act == 4;
+    const int ntiles = swiglu ? (d->N + 31) / 32 : (d->N + 63) / 64, nchunks = d->K / BK;
+    const long ntot = swiglu ? 2L * d->N : d->N;
+    int ks = 256 / ntiles;
+    if (ks > nchunks / 16) ks = nchunks / 16;
+    if (ks > 8) ks = 8;
+    if (ks < 1) ks = 1;
+    // the last 4 KiB of the workspace belong to the tile kernels' tickets and queue counters
+    const bool ws_ok = d->workspace && ((uintptr_t)d->workspace % 16) == 0 && (size_t)ks * d->M * ntot * sizeof(float) + 4096 <= d->workspace_bytes;
+    DESTA_CHECK_ARG(ks == 1 || ws_ok, "gemm_wide: N=%d K=%d is cut into %d K-slices and needs %zu workspace bytes", d->N, d->K, ks,
+                    (size_t)ks * d->M * ntot * sizeof(float) + 4096);
+    const int cps = (nchunks + ks - 1) / ks;
+    float* part = ks > 1 ? (float*)d->workspace : nullptr;
+    const int items = ntiles * ks, blocks = g_skinny_blocks > 1 ? g_skinny_blocks / 2 : 1;     // one block per CU where the 16-row kernel has two
+    const dim3 grid(items < blocks ? items : blocks);
+    hipStream_t st = (hipStream_t)stream;
+    const int mf = (d->M + 15) / 16;
+#define WD_LAUNCH(MF_) \
+    do { if (swiglu && b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, true, true>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); \
+         else if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, true, false>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); \
+         else if (b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, false, true>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); \
+         else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, false, false>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); } while (0)
+    if (mf == 2) WD_LAUNCH(2);
+    else if (mf == 3) WD_LAUNCH(3);
+    else WD_LAUNCH(4);
+#undef WD_LAUNCH
+    DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny_wide");
+    if (ks > 1) {
+        const dim3 fgrid((unsigned)(((long)d->M * (d->N / 4) + 255) / 256));
+        if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<true>), fgrid, dim3(256), 0, st, a, ks, part, b_scale);
+        else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<false>), fgrid, dim3(256), 0, st, a, ks, part, b_scale);
+        DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny_wide_fixup");
+    }
     g_last_kernel = 3;
     return DESTA_OK;
 }

@@ -105,10 +105,7 @@ def gemm(A, B, out, M, N, K, *, lda=None, ldb=None, ldc=None, bias=None, residua
         assert cs_.dtype == torch.float32 and pos_.dtype == torch.int32 and pos_.numel() >= M and cs_.is_contiguous()
         d.rope_cos_sin, d.rope_pos, d.rope_cols, d.rope_head_dim = p(cs_), p(pos_), int(cols_), int(hd_)
     st = stream()
-    ws = _gemm_ws.get((A.device, st))                       # one split-K scratch per STREAM: GEMMs of one stream run serially,
-    if ws is None:                                          # GEMMs of two streams (encoder prefetch beside the LLM) must not share it
-        ws = _gemm_ws[(A.device, st)] = torch.zeros(GEMM_WS_BYTES // 4, dtype=torch.float32, device=A.device)   # zeroed: the arrival tickets of the in-kernel split-K reduce live in its last 4 KiB
-    d.workspace, d.workspace_bytes = ws.data_ptr(), GEMM_WS_BYTES
+    d.workspace, d.workspace_bytes = _workspace(A.device, st).data_ptr(), GEMM_WS_BYTES
     if _gemm_prof is not None:
         # HIP events on the launch stream around this one kernel (bench.py roofline leg)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -169,9 +166,48 @@ def gemm_w8(A, B8, scale, out, M, N, K, *, lda=None, ldb=None, ldc=None, residua
     return out
 
 
+_gemm_wide = _sig("desta_gemm_wide_nt", C.POINTER(GemmDesc), vp, vp)
+GEMM_WIDE_CALLS = 0                # wide (17 <= M <= 64) weight-streaming projections issued by this process
+DECODE_MAX_ROWS = 64               # sequences per KV-cached decode step: what the weight-streaming projections take
+
+
+def gemm_wide(A, B, out, M, N, K, *, scale=None, lda=None, ldb=None, ldc=None, residual=None, ldr=None, act=0, alpha=1.0):
+    """out[M,N] = act(alpha * A[M,K] @ B[N,K]^T) + residual for 17 <= M <= 64: the decode projections of a wide batch, every weight
+    byte read once.  scale=None: B is bf16; otherwise B holds e4m3 bytes and scale one power-of-two fp32 scale per row
+    (`quantize_rows_e4m3`), same bits as the bf16 form on bf16(B * scale).  act 4: B (and scale) hold the concatenated gate|up
+    rows [2N].  bf16 output, bf16 residual; K-slice partial sums go through the stream's GEMM workspace."""
+    global GEMM_WIDE_CALLS
+    d = GemmDesc()
+    d.A, d.B, d.C = p(A), p(B), p(out)
+    d.M, d.N, d.K, d.batch = M, N, K, 1
+    d.lda = K if lda is None else lda
+    d.ldb = K if ldb is None else ldb
+    d.ldc = N if ldc is None else ldc
+    d.residual = p(residual)
+    d.ldr = N if ldr is None else ldr
+    d.residual_f32 = int(residual is not None and residual.dtype == torch.float32)
+    d.act = act
+    d.out_f32 = int(out.dtype == torch.float32)
+    d.ldp = N
+    d.alpha = alpha
+    d.workspace, d.workspace_bytes = _workspace(A.device, stream()).data_ptr(), GEMM_WS_BYTES
+    check(_gemm_wide(C.byref(d), p(scale), stream()), "desta_gemm_wide_nt")
+    GEMM_WIDE_CALLS += 1
+    return out
+
+
 _gemm_prof = None
 _gemm_ws = {}                      # (device, stream) -> split-K scratch
 GEMM_WS_BYTES = (64 << 20) + 4096
+
+
+def _workspace(device, st):
+    """One split-K scratch per STREAM: GEMMs of one stream run serially, GEMMs of two streams (encoder prefetch beside the LLM)
+    must not share it."""
+    ws = _gemm_ws.get((device, st))
+    if ws is None:                 # zeroed: the arrival tickets of the in-kernel split-K reduce live in its last 4 KiB
+        ws = _gemm_ws[(device, st)] = torch.zeros(GEMM_WS_BYTES // 4, dtype=torch.float32, device=device)
+    return ws
 
 
 def gemm_profile_start():

@@ -408,6 +408,12 @@ def check_sampling_args(top_k=None, min_p=None, repetition_penalty=None) -> None
         raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
 
 
+def check_decode_rows(B: int) -> None:
+    """A KV-cached decode step streams the weights once for all its rows; its projections take at most H.DECODE_MAX_ROWS of them."""
+    if B > H.DECODE_MAX_ROWS:
+        raise ValueError(f"generate: a batch of {B} sequences, the KV-cached decode step takes at most {H.DECODE_MAX_ROWS}: split the batch")
+
+
 @dataclass
 class GenerationOutput:
     """modeling_desta25.py:492-496"""
@@ -1782,8 +1788,10 @@ class CausalLMHIP:
         if fp8:
             self._fp8_decode_weights()
 
-        def mm(xin, w, w8, out, N, K, **kw):            # one projection on the bf16 weight, or on its e4m3 copy (q, scale)
-            if w8 is not None:
+        def mm(xin, w, w8, out, N, K, wide=B > 16, **kw):   # one projection on the bf16 weight, or on its e4m3 copy (q, scale)
+            if wide:                                    # B = 17..64: every weight byte once for all rows
+                H.gemm_wide(xin, w if w8 is None else w8[0], out, B, N, K, scale=None if w8 is None else w8[1], **kw)
+            elif w8 is not None:
                 H.gemm_w8(xin, w8[0], w8[1], out, B, N, K, **kw)
             else:
                 H.gemm(xin, w, out, B, N, K, **kw)
@@ -1796,7 +1804,10 @@ class CausalLMHIP:
                 mm(self.g_hb, w, w8, out, N, h, **kw)
         for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
             q8 = ly["q8"] if fp8 else {}
-            proj(x, ly["n1"], ly["wqkv"] if self.lora is None else self._lora_merged(li), q8.get("wqkv"), self.g_qkv, self.qkvw)
+            if self.lora is None:
+                proj(x, ly["n1"], ly["wqkv"], q8.get("wqkv"), self.g_qkv, self.qkvw)
+            else:                                                             # the merged weight stays on H.gemm at every B
+                proj(x, ly["n1"], self._lora_merged(li), None, self.g_qkv, self.qkvw, wide=False)
             H.rope_kv_append(self.g_qkv, self.qkvw, B, 1, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"),
                              c.rms_norm_eps, pos_shift, cache, Smax * self.kvw, self.kvw, cur)     # rotate q,k + append K|V at slot cur
             ad = H.attn_desc(self.g_qkv, cache, cache, self.g_att, self.g_lse, batch=B, hq=self.hq, hkv=self.hkv, sq=1, sk=cur + 1,
@@ -1826,6 +1837,7 @@ class CausalLMHIP:
         (`desta_sample_bf16`); None = off.  The penalty's history is what HF's `input_ids` hold: `prompt_ids` [B, S] (text-only
         chats, left padding included) followed by the tokens emitted so far, pad_token_id for finished rows."""
         assert max_new_tokens >= 1
+        check_decode_rows(B)
         use_pen = repetition_penalty is not None and float(repetition_penalty) != 1.0
         chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0)))
         Smax = S + max_new_tokens
@@ -2358,6 +2370,7 @@ class DeSTA25AudioModel:
         input_ids = inputs["context_input_ids"].to(dev)                      # only the context (prompt) part of the batch
         attention_mask = inputs["context_attention_mask"].to(dev)
         B, S = input_ids.shape
+        check_decode_rows(B)                                                 # before the encoder and the prompt pass run
         starts = inputs["context_batch_start_positions"]
         N_audio = len(starts)
         was_training = self.training

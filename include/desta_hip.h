@@ -156,6 +156,22 @@ int desta_quantize_rows_e4m3(const void* w_bf16, int rows, int cols, int64_t ld,
 int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decode at batch 17..64: the projections of a KV-cached decode step (llm_model.generate, modeling_desta25.py:1419-1427; the
+ * nn.Linear calls of TF:models/llama/modeling_llama.py:163-176 (MLP), 230-281 (attention projections), 480 (lm_head)) as one
+ * weight-streaming launch that reads every weight byte once for up to 64 rows (additive to ABI 8: no struct changes).
+ *
+ * desta_gemm_wide_nt: C[M,N] = epilogue( A[M,K] . B[N,K]^T ) for 17 <= M <= 64, batch 1; M outside that range returns
+ *   DESTA_EINVAL (M <= 16 is desta_gemm_bf16_nt / desta_gemm_w8a16_nt).  b_scale == NULL: B is bf16.  Otherwise B holds e4m3
+ *   bytes [N, K] ([2N, K] for act 4; ldb in elements = bytes, a multiple of 16) and b_scale one power-of-two fp32 scale per row
+ *   ([2N] for act 4), 16-byte aligned; the result is bit-identical to the bf16 form on the dequantised weight.  Supported: act 0
+ *   with an optional bf16 residual, act 4 (SwiGLU over concatenated gate|up rows, the rounding points of the 16-row kernel), alpha,
+ *   ldc, bf16 output; anything else (bias, GELU, preact, aux, dropout, transposed operands, rotary epilogue, out_f32, batch > 1,
+ *   a_rms_weight) returns DESTA_EINVAL.  Shapes with few 64-column tiles are cut into K-slices whose fp32 partial sums go
+ *   through desta_gemm_desc.workspace (slices * M * N * 4 bytes, 2N for act 4, plus 4096; too small: DESTA_EINVAL) and a
+ *   fix-up launch that adds them in slice order: results do not depend on the grid (desta_gemm_set_option 3) or on M. */
+int desta_gemm_wide_nt(const desta_gemm_desc* d, const float* b_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Global-norm clip + Adafactor over a flat fp32 arena.
  * Replaces `clip_grad_norm_(params, max_grad_norm)` (TF:trainer.py:1780-1782) followed by
  * `Adafactor.step` (TF:optimization.py:1203-1294; scale_parameter=False, relative_step=False,
