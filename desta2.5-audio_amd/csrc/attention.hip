@@ -1607,6 +1607,237 @@ __global__ __launch_bounds__(256) void attn_dq_sum_k(AttnArgs p, const float* __
     }
 }
 
+// ------------------------------------------------------------------------------------------ decode (seq_q = 1), split-KV
+// One token per sequence against a KV cache (llm_model.generate, modeling_desta25.py:1419): the forward kernel above gives
+// that shape one block per QUERY head, which walks the whole cache serially and re-reads K / V once per head of the GQA group.
+// Here a work item is (batch row, KV head, key chunk of DESTA_ATTN_DECODE_CHUNK keys): the G = Hq / Hkv query rows of the
+// group share every K / V byte, and the chunks of one row run on different CUs.  Chunk c is keys [c * CH, (c + 1) * CH) of the
+// cache whatever the batch, kv_start or the grid are, so a row's result is a function of that row's data alone.
+//   * four waves, CH / 4 consecutive keys each.  K and V go straight from global memory to registers (no LDS round trip for the
+//     streamed operands): every load of the wave's keys is issued before the first use, clamped to [kv_start, seq_k) rows.
+//   * scores: S^T = K . Q^T by mfma_f32_16x16x32_bf16, keys on the A rows, the group's query rows on B columns 0..G-1 (the other
+//     columns are zero).  Accumulator register r of lane l is key 16 t + 4 (l >> 4) + r, query row l & 15.
+//   * softmax in fp32, log2 domain, against the BLOCK's maximum (one LDS exchange of 4 x 8 floats), so the four waves' sums add.
+//   * P . V on the fp32 VALU: V rows are d-contiguous, an MFMA operand wants its k (= key) index on the lane, and a transpose
+//     through LDS is what this kernel avoids.  Lane l owns columns 8 (l & 15) .. + 7 of keys = (l >> 4) mod 4 for every query
+//     row; P comes back from a [key][8] fp32 LDS image as broadcast reads.  P is never rounded to bf16.
+//   * the four key classes of a wave fold by a reduce-scatter over the query rows (xor 32, xor 16), the waves through LDS.
+// A row with one chunk is finished here (O, lse).  Otherwise each item writes (max, sum, unnormalised O) in fp32 and
+// attn_decode_combine_k merges a row's chunks in ascending order: no atomics, no tickets, a second launch.
+// Empty chunk (all keys masked): max = -inf, sum = 0, O = 0; the combine skips it.
+template <int GP>                                          // G rounded up to 1, 2, 4, 8
+__global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
+    constexpr int CH = DESTA_ATTN_DECODE_CHUNK, KW = CH / 4, NT16 = KW / 16, NV = KW / 4;
+    __shared__ __attribute__((aligned(16))) float s_p[4][KW][8];
+    __shared__ __attribute__((aligned(16))) float s_red[4][GP][128];
+    __shared__ float s_m[4][8], s_l[4][8];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c16 = lane & 15, q4 = lane >> 4;
+    const int G = p.Hq / p.Hkv;
+    int id = blockIdx.x;
+    const int c = id % nch; id /= nch;
+    const int hk = id % p.Hkv, b = id / p.Hkv;
+    const int kv_lo = p.kv_start ? max(0, min(p.kv_start[b], p.Sk)) : 0;
+    const int k0 = c * CH + wave * KW;
+    const bool live = k0 < p.Sk && k0 + KW > kv_lo;        // wave-uniform: some key of this wave is visible
+    const int row_lo = min(kv_lo, p.Sk - 1), row_hi = p.Sk - 1;
+
+    bf16x8 kf[NT16][4];
+    uint4 vf[NV];
+    bf16x8 qf[4];
+    if (live) {
+        const bf16_t* kbase = p.K + (long)b * p.k_bs + (long)hk * 128 + 8 * q4;
+        const bf16_t* vbase = p.V + (long)b * p.v_bs + (long)hk * 128 + 8 * c16;
+#pragma unroll
+        for (int t = 0; t < NT16; ++t) {
+            const int row = min(max(k0 + 16 * t + c16, row_lo), row_hi);
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) kf[t][ks] = *(const bf16x8*)(kbase + (long)row * p.k_rs + 32 * ks);
+        }
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int row = min(max(k0 + 4 * i + q4, row_lo), row_hi);
+            vf[i] = *(const uint4*)(vbase + (long)row * p.v_rs);
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < NT16; ++t)
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) kf[t][ks][j] = (__bf16)0.f;
+#pragma unroll
+        for (int i = 0; i < NV; ++i) vf[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    {
+        const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)(hk * G + min(c16, G - 1)) * 128 + 8 * q4;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            qf[ks] = *(const bf16x8*)(qptr + 32 * ks);
+            if (c16 >= G)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) qf[ks][j] = (__bf16)0.f;
+        }
+    }
+
+    // scores of the wave's KW keys, masked and scaled; st[t][r]: key k0 + 16 t + 4 q4 + r, query row c16
+    f32x4 st[NT16];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < NT16; ++t) {
+        st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][ks], qf[ks], st[t], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int key = k0 + 16 * t + 4 * q4 + r;
+            st[t][r] = (key >= kv_lo && key < p.Sk) ? st[t][r] * p.scale_log2 : -INFINITY;
+            mx = fmaxf(mx, st[t][r]);
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (lane < 8) s_m[wave][lane] = mx;
+    __syncthreads();
+    const int g8 = c16 & 7;
+    const float mblk = fmaxf(fmaxf(s_m[0][g8], s_m[1][g8]), fmaxf(s_m[2][g8], s_m[3][g8]));
+    const float muse = (mblk == -INFINITY) ? 0.f : mblk;
+    float ls = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT16; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float pv = __builtin_amdgcn_exp2f(st[t][r] - muse);
+            ls += pv;
+            if (c16 < 8) s_p[wave][16 * t + 4 * q4 + r][c16] = pv;
+        }
+    ls += __shfl_xor(ls, 16, 64);
+    ls += __shfl_xor(ls, 32, 64);
+    if (lane < 8) s_l[wave][lane] = ls;
+    __syncthreads();
+
+    // P . V: acc[g][j] = sum over this lane's keys of P[g][key] * V[key][8 c16 + j]
+    float acc[GP][8];
+#pragma unroll
+    for (int g = 0; g < GP; ++g)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const float* pr = &s_p[wave][4 * i + q4][0];
+        float pg[GP];
+        if constexpr (GP >= 4) {
+#pragma unroll
+            for (int g = 0; g < GP; g += 4) {
+                const f32x4 t4 = *(const f32x4*)(pr + g);
+                pg[g] = t4[0]; pg[g + 1] = t4[1]; pg[g + 2] = t4[2]; pg[g + 3] = t4[3];
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < GP; ++g) pg[g] = pr[g];
+        }
+        const unsigned w[4] = {vf[i].x, vf[i].y, vf[i].z, vf[i].w};
+#pragma unroll
+        for (int j2 = 0; j2 < 4; ++j2) {
+            const float v0 = __builtin_bit_cast(float, w[j2] << 16), v1 = __builtin_bit_cast(float, w[j2] & 0xffff0000u);
+#pragma unroll
+            for (int g = 0; g < GP; ++g) {
+                acc[g][2 * j2] = fmaf(pg[g], v0, acc[g][2 * j2]);
+                acc[g][2 * j2 + 1] = fmaf(pg[g], v1, acc[g][2 * j2 + 1]);
+            }
+        }
+    }
+    // fold the four key classes (lanes l, l ^ 16, l ^ 32, l ^ 48): each exchange halves the query rows a lane keeps
+    const bool hi32 = (lane & 32) != 0, hi16 = (lane & 16) != 0;
+    constexpr int G1 = GP >= 2 ? GP / 2 : GP, G2 = GP >= 4 ? GP / 4 : G1;
+    float a1[G1][8], a2[G2][8];
+#pragma unroll
+    for (int g = 0; g < G1; ++g)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if constexpr (GP >= 2) {
+                const float keep = hi32 ? acc[g + G1][j] : acc[g][j], send = hi32 ? acc[g][j] : acc[g + G1][j];
+                a1[g][j] = keep + __shfl_xor(send, 32, 64);
+            } else {
+                a1[g][j] = acc[g][j] + __shfl_xor(acc[g][j], 32, 64);
+            }
+        }
+#pragma unroll
+    for (int g = 0; g < G2; ++g)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if constexpr (GP >= 4) {
+                const float keep = hi16 ? a1[g + G2][j] : a1[g][j], send = hi16 ? a1[g][j] : a1[g + G2][j];
+                a2[g][j] = keep + __shfl_xor(send, 16, 64);
+            } else {
+                a2[g][j] = a1[g][j] + __shfl_xor(a1[g][j], 16, 64);
+            }
+        }
+    {
+        // query rows this lane now holds: GP >= 4: (hi32 ? G1 : 0) + (hi16 ? G2 : 0) + g;  GP == 2: hi32 (both lanes of an
+        // xor-16 pair hold the same sums: one writes);  GP == 1: row 0 on every lane (lanes 0..15 write)
+        const int gbase = (GP >= 2 && hi32 ? G1 : 0) + (GP >= 4 && hi16 ? G2 : 0);
+        const bool writer = GP >= 4 ? true : (GP == 2 ? !hi16 : lane < 16);
+        if (writer)
+#pragma unroll
+            for (int g = 0; g < G2; ++g) {
+                float* dst = &s_red[wave][gbase + g][8 * c16];
+                *(f32x4*)dst = f32x4{a2[g][0], a2[g][1], a2[g][2], a2[g][3]};
+                *(f32x4*)(dst + 4) = f32x4{a2[g][4], a2[g][5], a2[g][6], a2[g][7]};
+            }
+    }
+    __syncthreads();
+
+    // the block's result: thread t < 32 GP sums the four waves for query row t / 32, columns 4 (t % 32) .. + 3
+    const int tg = threadIdx.x >> 5, d4 = threadIdx.x & 31;
+    if (tg < G) {
+        f32x4 o = *(const f32x4*)&s_red[0][tg][4 * d4];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) o += *(const f32x4*)&s_red[w][tg][4 * d4];
+        const float m = fmaxf(fmaxf(s_m[0][tg], s_m[1][tg]), fmaxf(s_m[2][tg], s_m[3][tg]));
+        const float l = ((s_l[0][tg] + s_l[1][tg]) + s_l[2][tg]) + s_l[3][tg];
+        const int h = hk * G + tg;
+        if (nch == 1) {
+            u16x4 ob;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ob[e] = f2bf(l > 0.f ? o[e] / l : 0.f);
+            *(u16x4*)(p.O + (long)b * p.o_bs + (long)h * 128 + 4 * d4) = ob;
+            if (p.lse && d4 == 0) p.lse[(long)b * p.Hq + h] = l > 0.f ? m + log2f(l) : INFINITY;
+        } else {
+            const long r = ((long)b * p.Hq + h) * nch + c;
+            *(f32x4*)(ws_o + r * 128 + 4 * d4) = o;
+            if (d4 == 0) { ws_ml[2 * r] = m; ws_ml[2 * r + 1] = l; }
+        }
+    }
+}
+
+// Merge of a row's chunk partials, chunks in ascending order, fp32.  32 threads per (batch, query head), 8 heads per block.
+__global__ __launch_bounds__(256) void attn_decode_combine_k(AttnArgs p, const float* __restrict__ ws_ml, const float* __restrict__ ws_o, int nch) {
+    const long bh = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    const int d4 = threadIdx.x & 31;
+    if (bh >= (long)p.B * p.Hq) return;
+    const float* ml = ws_ml + 2 * bh * nch;
+    const float* po = ws_o + bh * nch * 128 + 4 * d4;
+    float m = -INFINITY;
+    for (int c = 0; c < nch; ++c) m = fmaxf(m, ml[2 * c]);
+    f32x4 o = {0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    for (int c = 0; c < nch; ++c) {
+        const float mc = ml[2 * c], lc = ml[2 * c + 1];
+        if (mc == -INFINITY || !(lc > 0.f)) continue;      // empty chunk
+        const float w = __builtin_amdgcn_exp2f(mc - m);
+        const f32x4 oc = *(const f32x4*)(po + (long)c * 128);
+        l = fmaf(w, lc, l);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = fmaf(w, oc[e], o[e]);
+    }
+    const int b = (int)(bh / p.Hq), h = (int)(bh % p.Hq);
+    u16x4 ob;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ob[e] = f2bf(l > 0.f ? o[e] / l : 0.f);
+    *(u16x4*)(p.O + (long)b * p.o_bs + (long)h * 128 + 4 * d4) = ob;
+    if (p.lse && d4 == 0) p.lse[bh] = l > 0.f ? m + log2f(l) : INFINITY;
+}
+
 int fill_args(const desta_attn_desc* d, AttnArgs& a) {
     DESTA_CHECK_ARG(d && d->Q && d->K && d->V, "attention: null operand");
     DESTA_CHECK_ARG(d->head_dim == 64 || d->head_dim == 128, "attention: head_dim %d unsupported (64 or 128)", d->head_dim);
@@ -1683,6 +1914,59 @@ extern "C" int desta_attention_fwd(const desta_attn_desc* d, void* stream) {
     else if (a.drop_thresh) hipLaunchKernelGGL((attn_fwd_k<64, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL((attn_fwd_k<64, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
     DESTA_CHECK_LAUNCH("attention_fwd");
+    return DESTA_OK;
+}
+
+// Decode workspace (rows of more than one chunk only): (max, sum) pairs [batch][n_q_heads][chunks][2], padded to 16 bytes,
+// then the unnormalised fp32 outputs [batch][n_q_heads][chunks][head_dim].
+static_assert(DESTA_ATTN_DECODE_CHUNK % 64 == 0 && DESTA_ATTN_DECODE_CHUNK >= 64, "the decode chunk is a multiple of 64 keys");
+namespace {
+inline size_t decode_ml_floats(size_t items) { return (2 * items + 3) / 4 * 4; }
+}
+extern "C" int desta_attention_decode_chunk(void) { return DESTA_ATTN_DECODE_CHUNK; }
+extern "C" size_t desta_attention_decode_workspace_bytes(int batch, int n_q_heads, int seq_k, int head_dim) {
+    if (batch <= 0 || n_q_heads <= 0 || seq_k <= DESTA_ATTN_DECODE_CHUNK || head_dim <= 0) return 0;
+    const size_t nch = ((size_t)seq_k + DESTA_ATTN_DECODE_CHUNK - 1) / DESTA_ATTN_DECODE_CHUNK;
+    const size_t items = (size_t)batch * n_q_heads * nch;
+    return (decode_ml_floats(items) + items * (size_t)head_dim) * sizeof(float);
+}
+
+extern "C" int desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    DESTA_CHECK_ARG(d, "attention_decode: null descriptor");
+    DESTA_CHECK_ARG(d->seq_q == 1, "attention_decode: seq_q %d unsupported (one query row per sequence)", d->seq_q);
+    DESTA_CHECK_ARG(d->head_dim == 128, "attention_decode: head_dim %d unsupported (128)", d->head_dim);
+    DESTA_CHECK_ARG(!d->causal, "attention_decode: causal must be 0 (the one query row sees every key of [kv_start, seq_k))");
+    DESTA_CHECK_ARG(d->dropout_p == 0.f, "attention_decode: dropout_p must be 0");
+    DESTA_CHECK_ARG(!d->rope_cos_sin, "attention_decode: rope_cos_sin must be NULL");
+    DESTA_CHECK_ARG(!d->O_f32, "attention_decode: O_f32 must be NULL");
+    DESTA_CHECK_ARG(!d->dO && !d->dQ, "attention_decode: dO and dQ must be NULL (forward only)");
+    AttnArgs a;
+    if (int rc = fill_args(d, a)) return rc;
+    const int G = a.Hq / a.Hkv;
+    DESTA_CHECK_ARG(G <= 8, "attention_decode: group of %d query heads per kv head unsupported (at most 8)", G);
+    DESTA_CHECK_ARG(d->O && ((size_t)d->O & 15) == 0 && d->o_batch_stride % 8 == 0,
+                    "attention_decode: O must be 16-byte aligned with a batch stride that is a multiple of 8 elements");
+    DESTA_CHECK_ARG((((size_t)d->Q | (size_t)d->K | (size_t)d->V) & 15) == 0 && d->q_batch_stride % 8 == 0 &&
+                    d->k_batch_stride % 8 == 0 && d->v_batch_stride % 8 == 0,
+                    "attention_decode: Q, K, V must be 16-byte aligned with batch strides that are multiples of 8 elements");
+    const int nch = (a.Sk + DESTA_ATTN_DECODE_CHUNK - 1) / DESTA_ATTN_DECODE_CHUNK;
+    const size_t need = desta_attention_decode_workspace_bytes(a.B, a.Hq, a.Sk, 128);
+    DESTA_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need && ((size_t)workspace & 15) == 0),
+                    "attention_decode: workspace of %zu bytes is too small or misaligned (%zu needed, 16-byte aligned)", workspace_bytes, need);
+    DESTA_CHECK_ARG((long)a.B * a.Hkv * nch <= 0x7fffffffL, "attention_decode: grid too large");
+    float* ws_ml = (float*)workspace;
+    float* ws_o = ws_ml ? ws_ml + decode_ml_floats((size_t)a.B * a.Hq * nch) : nullptr;
+    const dim3 grid((unsigned)(a.B * a.Hkv * nch));
+    hipStream_t st = (hipStream_t)stream;
+    if (G == 1) hipLaunchKernelGGL((attn_decode_k<1>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
+    else if (G == 2) hipLaunchKernelGGL((attn_decode_k<2>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
+    else if (G <= 4) hipLaunchKernelGGL((attn_decode_k<4>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
+    else hipLaunchKernelGGL((attn_decode_k<8>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
+    DESTA_CHECK_LAUNCH("attention_decode");
+    if (nch > 1) {
+        hipLaunchKernelGGL(attn_decode_combine_k, dim3((unsigned)((a.B * a.Hq + 7) / 8)), dim3(256), 0, st, a, ws_ml, ws_o, nch);
+        DESTA_CHECK_LAUNCH("attention_decode (combine)");
+    }
     return DESTA_OK;
 }
 

@@ -555,6 +555,35 @@ def attention_fwd(d: AttnDesc):
     check(_attn_fwd(C.byref(d), stream()), "desta_attention_fwd")
 
 
+# Split-KV GQA decode attention (seq_q = 1, head_dim 128, at most 8 query heads per KV head): one work item per (row, KV head,
+# chunk of DECODE_ATTN_CHUNK keys), the chunks of a row merged in ascending order by a second launch (include/desta_hip.h).
+lib.desta_attention_decode_chunk.restype = i32
+lib.desta_attention_decode_workspace_bytes.restype = c_size_t
+lib.desta_attention_decode_workspace_bytes.argtypes = [i32, i32, i32, i32]
+_attn_decode = _sig("desta_attention_decode", C.POINTER(AttnDesc), vp, c_size_t, vp)
+DECODE_ATTN_CHUNK = int(lib.desta_attention_decode_chunk())        # keys per work item (DESTA_ATTN_DECODE_CHUNK of the library)
+# decode_step moves from attention_fwd to attention_decode at this many keys (cur + 1).  A multiple of 64, never below 256; set
+# from tools/decode_attn_bench.py (DESIGN.md §3 "Decode attention"): the smallest seq_k from which main + combine launch beat the
+# forward kernel at every batch size of the table (at 320 and 384 keys the second launch still costs batch 1 and 8 more than
+# the split saves; batch 16 and wider would already gain from 256 keys on).
+DECODE_ATTN_MIN_KEYS = 448
+ATTN_DECODE_CALLS = 0              # split-KV decode attention calls issued by this process
+
+
+def attention_decode_workspace_bytes(batch: int, hq: int, sk: int, hd: int = 128) -> int:
+    """Bytes of fp32 workspace `attention_decode` needs for this shape (0 while sk fits one chunk)."""
+    return int(lib.desta_attention_decode_workspace_bytes(int(batch), int(hq), int(sk), int(hd)))
+
+
+@_profiled(lambda d, *a, **k: "attn_decode:" + _attn_tag(d), lambda d, *a, **k: _attn_flops(d, 1.0))
+def attention_decode(d: AttnDesc, ws=None):
+    """The attention of one decode step (d.seq_q == 1) on the split-KV kernel; `ws`: a device buffer of at least
+    `attention_decode_workspace_bytes` bytes (None while d.seq_k <= DECODE_ATTN_CHUNK).  Unsupported descriptors raise."""
+    global ATTN_DECODE_CALLS
+    check(_attn_decode(C.byref(d), p(ws), 0 if ws is None else ws.numel() * ws.element_size(), stream()), "desta_attention_decode")
+    ATTN_DECODE_CALLS += 1
+
+
 @_profiled(lambda d, *a, **k: "attn_bwd:" + _attn_tag(d), lambda d, *a, **k: _attn_flops(d, 2.5))     # dS, dP recompute, dQ, dK, dV
 def attention_bwd(d: AttnDesc, do, dq, dk=None, dv=None, *, do_rs=None, dq_off=0, dk_off=0, dv_off=0, dq_rs=None,
                   dk_rs=None, dv_rs=None, do_bs=None, dq_bs=None, dk_bs=None, dv_bs=None, rope_cos_sin=None, dkv_t=None):

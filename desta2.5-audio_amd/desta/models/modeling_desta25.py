@@ -1770,6 +1770,9 @@ class CausalLMHIP:
         self.g_x, self.g_xm, self.g_hb = b16(B, h), b16(B, h), b16(B, h)
         self.g_qkv, self.g_att = b16(B, self.qkvw), b16(B, self.hq * self.hd)
         self.g_lse = torch.empty(B, self.hq, 1, dtype=F32, device=dev)
+        # fp32 chunk partials of the split-KV decode attention, sized once for the longest cache (0 bytes while it fits one chunk)
+        ws = H.attention_decode_workspace_bytes(B, self.hq, Smax, self.hd) if self.hd == 128 and self.hq // self.hkv <= 8 else 0
+        self.g_attn_ws = torch.empty(ws // 4, dtype=F32, device=dev) if ws else None
         self.g_act = b16(B, self.I)
         self.g_r = torch.empty(B, dtype=F32, device=dev)
         self.g_logits = torch.zeros(B, self.Vp, dtype=BF16, device=dev)
@@ -1802,6 +1805,8 @@ class CausalLMHIP:
             else:
                 H.rmsnorm_fwd(xin, nw, c.rms_norm_eps, self.g_hb, self.g_r)
                 mm(self.g_hb, w, w8, out, N, h, **kw)
+        # long caches: split-KV kernel (K / V once per GQA group, a row's chunks on different CUs); a rule of the shape alone
+        split_kv = self.hd == 128 and self.hq // self.hkv <= 8 and cur + 1 >= H.DECODE_ATTN_MIN_KEYS
         for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
             q8 = ly["q8"] if fp8 else {}
             if self.lora is None:
@@ -1814,7 +1819,10 @@ class CausalLMHIP:
                              hd=self.hd, scale=scale, causal=False, kv_start=kv_start, q_off=0, k_off=0, v_off=self.hkv * self.hd,
                              q_rs=self.qkvw, k_rs=self.kvw, v_rs=self.kvw, o_rs=self.hq * self.hd,
                              q_bs=self.qkvw, k_bs=Smax * self.kvw, v_bs=Smax * self.kvw, o_bs=self.hq * self.hd)
-            H.attention_fwd(ad)
+            if split_kv:
+                H.attention_decode(ad, self.g_attn_ws)
+            else:
+                H.attention_fwd(ad)
             mm(self.g_att, ly["wo"], q8.get("wo"), self.g_xm, h, self.hq * self.hd, residual=x)
             proj(self.g_xm, ly["n2"], ly["wgu"], q8.get("wgu"), self.g_act, self.I, act=4)     # norm + gate|up projection + SwiGLU
             mm(self.g_act, ly["wd"], q8.get("wd"), self.g_x, h, self.I, residual=self.g_xm)

@@ -459,6 +459,25 @@ int desta_attention_set_concurrent_bwd(int on);
  *            SLOWER on the LLM shape, 207 vs 194 us: default 0). */
 int desta_attention_set_option(int which, int value);
 
+/* Split-KV GQA decode attention (additive to ABI 8: no struct changes): the attention of one KV-cached decode step inside
+ * llm_model.generate (modeling_desta25.py:1419; TF:models/llama/modeling_llama.py:230-281 with past_key_values) for long caches
+ * and wide batches.  Takes the descriptor of desta_attention_fwd with seq_q == 1; strides, offsets, kv_start, scale, lse (log2
+ * domain, [batch][n_q_heads][1]) and GQA by n_q_heads / n_kv_heads mean what they mean there, any seq_k >= 1.  A work item is
+ * (batch row, KV head, chunk c of keys [c * CHUNK, min((c + 1) * CHUNK, seq_k))): every K / V byte is read once per GQA group,
+ * a row's chunks run on different CUs, and the chunk boundaries depend on nothing but CHUNK, so a row's result does not depend
+ * on the batch, on kv_start of other rows, on the cache's batch stride or on the device.  Cache rows >= seq_k are never read.
+ * seq_k <= CHUNK: one launch, `workspace` may be NULL.  Otherwise each item leaves an fp32 partial (max, sum, unnormalised O)
+ * in `workspace` and a second launch merges a row's chunks in ascending order (no atomics).
+ * Returns DESTA_EINVAL and launches nothing for: seq_q != 1, head_dim != 128, more than 8 query heads per KV head, causal,
+ * dropout_p != 0, non-NULL rope_cos_sin / O_f32 / dO / dQ, O (or Q, K, V) not 16-byte aligned or with a batch stride that is
+ * no multiple of 8 elements, a workspace smaller than desta_attention_decode_workspace_bytes() or not 16-byte aligned. */
+#ifndef DESTA_ATTN_DECODE_CHUNK
+#define DESTA_ATTN_DECODE_CHUNK 256
+#endif
+int    desta_attention_decode_chunk(void);         /* DESTA_ATTN_DECODE_CHUNK as the library was compiled */
+size_t desta_attention_decode_workspace_bytes(int batch, int n_q_heads, int seq_k, int head_dim);
+int    desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* layer_prompts[j].expand(B,-1,-1) for all taps at once (modeling_desta25.py:589): prompts fp32
  * [taps][n], n = prompt_size*d -> rows [(taps*batch)][n] in fp32 and bf16; prompt_grad sums the
  * gradient back over the batch. */

@@ -1,0 +1,93 @@
+"""Attention of one KV-cached decode step at Llama-3.1-8B geometry (32 / 8 heads, head_dim 128): the split-KV kernel
+(desta_attention_decode: main launch + combine launch) against the forward kernel the decode step used at every length before
+(desta_attention_fwd with seq_q = 1), per batch size and cache length.  Operands as decode_step passes them: Q a slice of the
+[B, 6144] q|k|v buffer, K | V the halves of [B, Smax, 4096] slabs with Smax = the longest cache of the table; --slabs (32) separate
+slabs are visited in rotation, as the 32 layers are, and each line says whether the bytes a rotation touches exceed the 256 MiB
+Infinity Cache (HBM) or not (MALL: the figures are then cache bandwidth, not HBM bandwidth).  Both legs alternate in one process
+(--rounds alternations).  Per leg: median us over the rounds and the spread (max - min); GB/s counts the K + V bytes of the visible
+cache once per KV head; x = forward median / split-KV median.  us = HIP events around a run of back-to-back calls from Python, so it
+is kernel time only while the host enqueues faster than the device runs: `enqueue` is the host time per iteration to issue the
+calls (no synchronise), and a line whose enqueue time reaches 90 % of a leg's us is marked HOST-BOUND (that leg's figure is then an
+upper bound of its kernel time, and the ratio says nothing about the kernels).  `win` = the split-KV leg is faster by more than the
+two spreads added: DECODE_ATTN_MIN_KEYS is the smallest multiple of 64 (>= 256) from which every batch size says win.
+  python tools/decode_attn_bench.py [--batches 1,8,16,32,64] [--keys 128,256,512,1024,2048,4096] [--rounds 3] [--slabs 32]"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "desta2.5-audio_amd"))
+import torch
+from desta import _hip as H
+
+HQ, HKV, HD = 32, 8, 128
+
+
+def timeit(fn, nbuf):
+    reps = max(2 * nbuf, 12)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    t0 = time.perf_counter()
+    for i in range(reps):
+        fn(i % nbuf)
+    enq = (time.perf_counter() - t0) * 1e6 / reps                            # host time to ENQUEUE one iteration
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps, enq
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,8,16,32,64")
+    ap.add_argument("--keys", default="128,256,512,1024,2048,4096")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--slabs", type=int, default=32)
+    a = ap.parse_args()
+    assert a.rounds >= 3, "at least three alternations"
+    keys = [int(k) for k in a.keys.split(",")]
+    Smax, qkvw, kvw = max(keys), (HQ + 2 * HKV) * HD, 2 * HKV * HD
+    print(f"chunk {H.DECODE_ATTN_CHUNK} keys, dispatch threshold {H.DECODE_ATTN_MIN_KEYS} keys, {a.slabs} slabs of [B, {Smax}, {kvw}] bf16")
+    for B in (int(b) for b in a.batches.split(",")):
+        slabs = [torch.empty(B, Smax, kvw, dtype=torch.bfloat16, device="cuda").normal_() for _ in range(a.slabs)]
+        qkv = torch.randn(B, qkvw, device="cuda").to(torch.bfloat16)
+        out = torch.empty(B, HQ * HD, dtype=torch.bfloat16, device="cuda")
+        lse = torch.empty(B, HQ, 1, dtype=torch.float32, device="cuda")
+        kv0 = torch.zeros(B, dtype=torch.int32, device="cuda")
+        nws = H.attention_decode_workspace_bytes(B, HQ, Smax, HD)
+        ws = torch.empty(max(nws // 4, 1), dtype=torch.float32, device="cuda")
+        for sk in keys:
+            descs = [H.attn_desc(qkv, s, s, out, lse, batch=B, hq=HQ, hkv=HKV, sq=1, sk=sk, hd=HD, scale=HD ** -0.5, causal=False, kv_start=kv0,
+                                 q_off=0, k_off=0, v_off=HKV * HD, q_rs=qkvw, k_rs=kvw, v_rs=kvw, o_rs=HQ * HD,
+                                 q_bs=qkvw, k_bs=Smax * kvw, v_bs=Smax * kvw, o_bs=HQ * HD) for s in slabs]
+
+            def new(i):
+                H.attention_decode(descs[i], ws)
+
+            def old(i):
+                H.attention_fwd(descs[i])
+
+            for fn in (new, old):                                            # warm up both legs on every slab
+                for i in range(a.slabs):
+                    fn(i)
+            tn, to, en, eo = [], [], [], []
+            for _ in range(a.rounds):
+                t, e = timeit(new, a.slabs)
+                tn.append(t), en.append(e)
+                t, e = timeit(old, a.slabs)
+                to.append(t), eo.append(e)
+            mn, mo = sorted(tn)[len(tn) // 2], sorted(to)[len(to) // 2]
+            sn, so = max(tn) - min(tn), max(to) - min(to)
+            cache = B * sk * kvw * 2                                         # K + V bytes of one slab's visible cache
+            where = "HBM " if cache * a.slabs > 256 * 2**20 else "MALL"
+            hb = " HOST-BOUND" if min(en) > 0.9 * mn or min(eo) > 0.9 * mo else ""
+            win = "win " if mo - mn > sn + so else "no  "
+            print(f"B={B:2d} keys={sk:4d} {where} {cache * a.slabs / 2**20:8.0f} MiB  split-KV {mn:8.1f}us (spread {sn:5.1f}, enqueue {min(en):5.1f}) "
+                  f"{cache / mn / 1e3:7.1f} GB/s   forward {mo:8.1f}us (spread {so:5.1f}, enqueue {min(eo):5.1f}) {cache / mo / 1e3:7.1f} GB/s   "
+                  f"x{mo / mn:5.2f} {win}{hb}", flush=True)
+        del slabs, descs
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

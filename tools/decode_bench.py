@@ -4,11 +4,14 @@ rate of the decode GEMMs (bytes of frozen LLM weights read per token / token tim
 
   python tools/decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 8] [--ctx 64] [--prompt-tail 16] [--new 64]
                                [--do-sample --temperature T --top-p P --top-k K --min-p M --repetition-penalty R]
-                               [--weights {bf16,fp8}] [--ab [--rounds R]]
+                               [--weights {bf16,fp8}] [--ab [--rounds R]] [--attn-ab [--rounds R]]
 Without --do-sample the decode is greedy (with --repetition-penalty, through the full-chain sampler kernel).
 --weights: what the decode steps stream (`set_decode_weights`; fp8 = weight-only OCP e4m3, half the bytes).  --ab alternates
 bf16 and fp8 in ONE process on one model (R rounds of bf16, fp8) and prints one line per leg and round plus a summary with the
 spread over the rounds: the bf16 leg of the same process is the yardstick, never a number from another box.
+--attn-ab alternates, for the chosen --weights, the decode step's attention dispatch (split-KV kernel from
+H.DECODE_ATTN_MIN_KEYS keys on) with the forward kernel at every length (H.DECODE_ATTN_MIN_KEYS = 1 << 30, the path before the
+split-KV kernel) in ONE process, R rounds, same report.
 """
 import argparse
 import json
@@ -36,7 +39,8 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=None)
     ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16")
     ap.add_argument("--ab", action="store_true", help="alternate bf16 / fp8 decode weights in this process")
-    ap.add_argument("--rounds", type=int, default=3, help="--ab: alternations")
+    ap.add_argument("--attn-ab", action="store_true", help="alternate split-KV / forward-kernel decode attention in this process")
+    ap.add_argument("--rounds", type=int, default=3, help="--ab / --attn-ab: alternations")
     a = ap.parse_args()
     gen = dict(do_sample=a.do_sample, temperature=a.temperature, top_p=a.top_p, top_k=a.top_k, min_p=a.min_p,
                repetition_penalty=a.repetition_penalty)
@@ -83,6 +87,33 @@ def main():
         print(json.dumps(r), flush=True)
         return r
 
+    if a.attn_ab:
+        min_keys = H.DECODE_ATTN_MIN_KEYS
+        legs = {"split_kv": min_keys, "forward": 1 << 30}
+        runs = {k: [] for k in legs}
+        try:
+            H.DECODE_ATTN_MIN_KEYS = min_keys
+            leg(a.weights)                                                   # warm-up
+            for _ in range(a.rounds):
+                for name, thr in legs.items():
+                    H.DECODE_ATTN_MIN_KEYS = thr
+                    n0 = H.ATTN_DECODE_CALLS
+                    runs[name].append(leg(a.weights)["ms_per_token_step"])
+                    assert (H.ATTN_DECODE_CALLS > n0) == (name == "split_kv" and S + a.new >= min_keys)
+        finally:
+            H.DECODE_ATTN_MIN_KEYS = min_keys
+        lo = {k: min(v) for k, v in runs.items()}
+        hi = {k: max(v) for k, v in runs.items()}
+        med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+        print(json.dumps({"attn_ab": f"{a.config} B={B} prompt={S} new={a.new} {mode} weights={a.weights}", "rounds": a.rounds,
+                          "min_keys": min_keys, "chunk": H.DECODE_ATTN_CHUNK,
+                          "split_kv_ms_per_step": runs["split_kv"], "forward_ms_per_step": runs["forward"],
+                          "tokens_per_s": {k: round(B / med[k] * 1e3, 1) for k in runs},
+                          "spread_ms": {k: round(hi[k] - lo[k], 3) for k in runs},
+                          "median_speedup": round(med["forward"] / med["split_kv"], 3),
+                          "margin_ms_worst_case": round(lo["forward"] - hi["split_kv"], 3),
+                          "split_kv_faster_beyond_spread": bool(med["forward"] - med["split_kv"] > sum(hi[k] - lo[k] for k in runs))}))
+        return
     if not a.ab:
         leg(a.weights)
         return
