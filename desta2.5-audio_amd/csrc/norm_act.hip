@@ -794,6 +794,89 @@ extern "C" int desta_rmsnorm_bwd(const void* dy, const void* x, const float* wei
     return DESTA_OK;
 }
 
+namespace {
+// RoPE + QUANTISING KV-cache append (the opt-in FP8 cache of generate()): rope_k<128, NORM, false> with the cache written as
+// OCP e4m3 bytes + one power-of-two fp32 scale per (row, slot, K-or-V head), the rule of desta_quantize_rows_e4m3 with "row"
+// = one head's 128 values.  q and k are rotated in place with the bits rope_k leaves; what is quantised is the bf16 value the
+// bf16 cache would hold.  A head is 8 adjacent lanes, so its amax is three xor shuffles.
+struct RopeKV8 { uint8_t* dst; float* scale; long bs, rs, sbs, srs; int slot0; int n_v; };
+template <int NORM>
+__global__ __launch_bounds__(256) void rope_kv8_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
+                                                  const float* __restrict__ cs, const float* __restrict__ wq,
+                                                  const float* __restrict__ wk, float eps, const int* __restrict__ pos_shift, RopeKV8 kv) {
+    constexpr int HD = 128, G = HD / 16, H2 = HD / 2;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long grp = gid / G;
+    const int j = (int)(gid % G);
+    const int all_heads = n_heads + kv.n_v;
+    const bool active = grp < (long)rows * all_heads;
+    const int row = active ? (int)(grp / all_heads) : 0, head = active ? (int)(grp % all_heads) : 0;
+    bf16_t* p = buf + (long)row * ld + (long)head * HD;
+    u16x8 ca, cb;                                                        // the bf16 bits a bf16 cache would hold
+    if (head >= n_heads) {                                               // V head: as stored
+        ca = *(const u16x8*)(p + 8 * j);
+        cb = *(const u16x8*)(p + H2 + 8 * j);
+    } else {
+        const int spos = row % S, bidx = row / S;
+        const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
+        float a[8], b[8], c[8], s[8];
+        load8(p, 8 * j, 0, a);
+        load8(p, H2 + 8 * j, 0, b);
+        load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
+        load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
+        if (NORM == 1) {
+            const float* w = head < n_q ? wq : wk;
+            float q = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) q += a[e] * a[e] + b[e] * b[e];
+#pragma unroll
+            for (int o = 1; o < G; o <<= 1) q += __shfl_xor(q, o, 64);
+            const float rstd = rsqrtf(q / (float)HD + eps);
+            float wa[8], wb[8];
+            load8(w, 8 * j, 1, wa);
+            load8(w, H2 + 8 * j, 1, wb);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                a[e] = bf2f(f2bf(wa[e] * bf2f(f2bf(a[e] * rstd))));
+                b[e] = bf2f(f2bf(wb[e] * bf2f(f2bf(b[e] * rstd))));
+            }
+        }
+        float oa[8], ob[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { oa[e] = a[e] * c[e] - b[e] * s[e]; ob[e] = b[e] * c[e] + a[e] * s[e]; }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { ca[e] = f2bf(oa[e]); cb[e] = f2bf(ob[e]); }
+        if (active) { *(u16x8*)(p + 8 * j) = ca; *(u16x8*)(p + H2 + 8 * j) = cb; }
+    }
+    unsigned amax = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = max(amax, max((unsigned)(ca[e] & 0x7fff), (unsigned)(cb[e] & 0x7fff)));
+#pragma unroll
+    for (int o = 1; o < G; o <<= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, o, 64));
+    if (!active || head < n_q) return;
+    const int ex = amax ? e4m3_row_exponent(amax) : 0;
+    const long b = row / S, slot = kv.slot0 + row % S;
+    uint8_t* d = kv.dst + b * kv.bs + slot * kv.rs + (long)(head - n_q) * HD;
+    unsigned w[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const u16x8& v = h ? cb : ca;
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = ldexpf(bf2f(v[e]), -ex);
+        int lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+        w[2 * h] = (unsigned)lo; w[2 * h + 1] = (unsigned)hi;
+    }
+    *(uint2*)(d + 8 * j) = make_uint2(w[0], w[1]);
+    *(uint2*)(d + H2 + 8 * j) = make_uint2(w[2], w[3]);
+    if (j == 0) kv.scale[b * kv.sbs + slot * kv.srs + (head - n_q)] = pow2f(ex);
+}
+}  // namespace
+
 static int rope_launch(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                        const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
                        const void* pre_norm, int64_t ld_pre, int backward, const int32_t* pos_shift, RopeKV kv, int sm_batch, void* stream) {
@@ -838,6 +921,31 @@ extern "C" int desta_rope_kv_append(void* qkv, int64_t ld, int rows, int seq, in
     DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0 && (uintptr_t)qkv % 16 == 0, "rope_kv_append: buffers must be 16-byte aligned");
     const RopeKV kv = {(bf16_t*)kv_cache, (long)kv_batch_stride, (long)kv_row_stride, slot0, n_kv_heads};
     return rope_launch(qkv, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, eps, nullptr, 0, 0, pos_shift, kv, 0, stream);
+}
+
+extern "C" int desta_rope_kv_append_e4m3(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                                         const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
+                                         const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                                         float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream) {
+    DESTA_CHECK_ARG(qkv && cos_sin, "rope_kv_append_e4m3: null argument");
+    DESTA_CHECK_ARG(head_dim == 128, "rope_kv_append_e4m3: head_dim %d unsupported (128)", head_dim);
+    DESTA_CHECK_ARG(ld % 8 == 0 && rows > 0 && seq > 0 && rows % seq == 0 && n_q_heads > 0 && n_kv_heads > 0, "rope_kv_append_e4m3: bad shape");
+    DESTA_CHECK_ARG(!q_norm_w == !k_norm_w, "rope_kv_append_e4m3: q_norm and k_norm come together");
+    DESTA_CHECK_ARG(kv_cache && kv_scale && kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0 && slot0 >= 0 &&
+                    kv_row_stride >= 2L * n_kv_heads * 128 && scale_row_stride >= 2L * n_kv_heads && scale_batch_stride >= 0,
+                    "rope_kv_append_e4m3: bad cache argument");
+    DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)kv_scale % 4 == 0,
+                    "rope_kv_append_e4m3: buffers must be 16-byte aligned");
+    const RopeKV8 kv = {kv_cache, kv_scale, (long)kv_batch_stride, (long)kv_row_stride, (long)scale_batch_stride, (long)scale_row_stride,
+                        slot0, n_kv_heads};
+    const int nh = n_q_heads + n_kv_heads;
+    const long nthreads = (long)rows * (nh + n_kv_heads) * 8;
+    const dim3 grid((unsigned)((nthreads + 255) / 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (q_norm_w) hipLaunchKernelGGL((rope_kv8_k<1>), grid, dim3(256), 0, st, (bf16_t*)qkv, (long)ld, rows, seq, nh, n_q_heads, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, kv);
+    else hipLaunchKernelGGL((rope_kv8_k<0>), grid, dim3(256), 0, st, (bf16_t*)qkv, (long)ld, rows, seq, nh, n_q_heads, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, kv);
+    DESTA_CHECK_LAUNCH("rope_kv_append_e4m3");
+    return DESTA_OK;
 }
 
 extern "C" int desta_swiglu_fwd(const void* gate_up, void* act, int64_t rows, int inter, void* stream) {

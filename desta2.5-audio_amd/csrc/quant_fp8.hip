@@ -10,22 +10,6 @@
 
 namespace {
 
-// e for one row from the bits of its largest |w| (bf16, sign cleared; integer order == value order)
-__device__ __forceinline__ int e4m3_row_exponent(unsigned amax_bits) {
-    int ex = (int)(amax_bits >> 7), frac = (int)(amax_bits & 0x7f);
-    if (ex == 0) {                                      // bf16 subnormal: frac * 2^-133, normalise
-        const int top = 31 - __clz(frac);
-        ex = top - 6;                                   // value = 1.f * 2^(top - 133) = 2^(ex - 127)
-        frac = (frac << (7 - top)) & 0x7f;
-    }
-    // amax = (1 + frac/128) * 2^(ex-127);  448 = 1.75 * 2^8:  mantissa <= 1.75 fits under 2^8, a larger one needs one more
-    return ex - 127 - 8 + (frac > 96 ? 1 : 0);
-}
-
-__device__ __forceinline__ float pow2f(int e) {       // 2^e as fp32 bits, subnormal results included (e >= -149)
-    return __uint_as_float(e >= -126 ? (unsigned)(e + 127) << 23 : 1u << (e + 149));
-}
-
 __global__ __launch_bounds__(256) void quantize_rows_e4m3_k(const bf16_t* __restrict__ w, int cols, long ld, uint8_t* __restrict__ q,
                                                             float* __restrict__ scale) {
     __shared__ unsigned sh[4];

@@ -584,6 +584,22 @@ def attention_decode(d: AttnDesc, ws=None):
     ATTN_DECODE_CALLS += 1
 
 
+# The same kernel structure on the opt-in FP8 KV cache: d.K / d.V point at e4m3 bytes (strides in bytes), one power-of-two fp32
+# scale per (row, slot, K-or-V head); bit-identical to attention_decode on the dequantised cache (include/desta_hip.h).
+_attn_kv8 = _sig("desta_attention_decode_kv8", C.POINTER(AttnDesc), vp, vp, i64, i64, vp, c_size_t, vp)
+ATTN_KV8_CALLS = 0                 # FP8-cache decode attention calls issued by this process
+
+
+@_profiled(lambda d, *a, **k: "attn_kv8:" + _attn_tag(d), lambda d, *a, **k: _attn_flops(d, 1.0))
+def attention_decode_kv8(d: AttnDesc, k_scale, v_scale, scale_bs, scale_rs, ws=None):
+    """attention_decode on an FP8 cache; k_scale / v_scale: fp32 tensors (views) whose first element is head 0's scale of
+    row 0, slot 0, sharing the batch / row strides `scale_bs` / `scale_rs` (floats).  `ws` as for attention_decode."""
+    global ATTN_KV8_CALLS
+    check(_attn_kv8(C.byref(d), p(k_scale), p(v_scale), int(scale_bs), int(scale_rs), p(ws),
+                    0 if ws is None else ws.numel() * ws.element_size(), stream()), "desta_attention_decode_kv8")
+    ATTN_KV8_CALLS += 1
+
+
 @_profiled(lambda d, *a, **k: "attn_bwd:" + _attn_tag(d), lambda d, *a, **k: _attn_flops(d, 2.5))     # dS, dP recompute, dQ, dK, dV
 def attention_bwd(d: AttnDesc, do, dq, dk=None, dv=None, *, do_rs=None, dq_off=0, dk_off=0, dv_off=0, dq_rs=None,
                   dk_rs=None, dv_rs=None, do_bs=None, dq_bs=None, dk_bs=None, dv_bs=None, rope_cos_sin=None, dkv_t=None):
@@ -688,6 +704,16 @@ def rope_kv_append(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_
     """Forward rope on a fused q|k|v buffer + append of the rotated K and the V heads to the KV cache slab."""
     check(_rope_kv(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pos_shift), p(cache), kv_bs,
                    kv_rs, slot0, stream()), "desta_rope_kv_append")
+
+
+_rope_kv8 = _sig("desta_rope_kv_append_e4m3", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, f32, vp, vp, i64, i64, vp, i64, i64, i32, vp)
+
+
+def rope_kv_append_e4m3(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, cache, kv_bs, kv_rs,
+                        scale, scale_bs, scale_rs, slot0):
+    """rope_kv_append into the FP8 cache: e4m3 bytes to `cache` (strides in bytes), one fp32 scale per head to `scale`."""
+    check(_rope_kv8(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pos_shift), p(cache), kv_bs,
+                    kv_rs, p(scale), scale_bs, scale_rs, slot0, stream()), "desta_rope_kv_append_e4m3")
 
 
 _sample = _sig("desta_sample_top_p_bf16", vp, i64, i32, i32, f32, f32, C.c_uint64, C.c_uint32, vp, vp, vp)

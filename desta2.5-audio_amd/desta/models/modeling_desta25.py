@@ -1487,6 +1487,8 @@ class CausalLMHIP:
         self.fuse_swiglu = True                     # A/B switch (bench.py --no-swiglu-fusion): silu(gate) * up and its backward inside the gate|up / d(act) GEMM epilogues
         self.decode_weights = "bf16"                # `set_decode_weights`: what the projections of a KV-cached decode step stream
         self.head8 = None
+        self.kv_cache_kind = "bf16"                 # `set_kv_cache`: what generate()'s KV cache holds
+        self.kv_cache = self.kv_scale = None
 
     # -- weight-only FP8 (e4m3) decode: a second, half-size copy of the frozen decode-side weights -------------------------------
     DECODE_WEIGHT_KINDS = ("bf16", "fp8")
@@ -1502,6 +1504,24 @@ class CausalLMHIP:
             self.head8 = None
             for ly in self.layers:
                 ly.pop("q8", None)
+
+    # -- FP8 (e4m3) KV cache: bytes + one power-of-two scale per (row, slot, K-or-V head) (include/desta_hip.h) ------------------
+    KV_CACHE_KINDS = ("bf16", "fp8")
+
+    def set_kv_cache(self, kind: str) -> None:
+        """What generate()'s KV cache holds: "bf16" (default, the reference's arithmetic) or "fp8" = OCP e4m3 bytes, quantised
+        per head where a token is appended and dequantised in registers where the decode attention reads it (0.516 of the bf16
+        bytes).  The prompt pass's own attention reads the bf16 q|k|v projection either way, so prompt logits do not depend on
+        the kind.  "fp8" needs the split-KV decode kernel's geometry: head_dim 128 and at most 8 query heads per KV head."""
+        if kind not in self.KV_CACHE_KINDS:
+            raise ValueError(f"kv_cache must be one of {self.KV_CACHE_KINDS}, got {kind!r}")
+        if kind == "fp8" and (self.hd != 128 or self.hq // self.hkv > 8):
+            raise ValueError(f"kv_cache 'fp8' needs head_dim 128 and at most 8 query heads per KV head, got head_dim {self.hd}, "
+                             f"{self.hq // self.hkv} per KV head")
+        if kind != self.kv_cache_kind:                                       # the other kind's slabs are freed; `_gen_alloc` makes the new ones
+            self.kv_cache = self.kv_scale = self.kv_scale_v = None
+            self._gen_shape = None
+        self.kv_cache_kind = kind
 
     def _fp8_decode_weights(self) -> None:
         """Quantise once: q|k|v, o, gate|up (the concatenated decode copy) and down of every layer, and the lm_head (tied
@@ -1705,6 +1725,10 @@ class CausalLMHIP:
             elif kv_cache is None:
                 H.rope(s["qkv"], self.qkvw, M, S, self.hq, self.hkv, self.hd, cs, ly.get("qn"), ly.get("kn"), c.rms_norm_eps, pos_shift=pos_shift,
                        s_major_batch=smb)
+            elif kv_cache[i].dtype == torch.uint8:                            # FP8 cache: same rotation, the append quantises per head
+                sc = self.kv_scale[i]
+                H.rope_kv_append_e4m3(s["qkv"], self.qkvw, M, S, self.hq, self.hkv, self.hd, cs, ly.get("qn"), ly.get("kn"), c.rms_norm_eps,
+                                      pos_shift, kv_cache[i], kv_cache[i].stride(0), kv_cache[i].stride(1), sc, sc.stride(0), sc.stride(1), 0)
             else:
                 H.rope_kv_append(s["qkv"], self.qkvw, M, S, self.hq, self.hkv, self.hd, cs, ly.get("qn"), ly.get("kn"), c.rms_norm_eps,
                                  pos_shift, kv_cache[i], kv_cache[i].stride(0), kv_cache[i].stride(1), 0)
@@ -1755,16 +1779,22 @@ class CausalLMHIP:
 
     # -- greedy decoding with a KV cache (reference: llm_model.generate, modeling_desta25.py:1419) ------
     def _gen_alloc(self, B: int, Smax: int):
-        if getattr(self, "_gen_shape", None) == (B, Smax):
+        if getattr(self, "_gen_shape", None) == (B, Smax) and self._gen_kind == self.kv_cache_kind:
             return
         dev, h = self.dev, self.h
 
         def b16(*s):
             return torch.empty(*s, dtype=BF16, device=dev)
-        self._gen_shape = (B, Smax)
+        self._gen_shape, self._gen_kind = (B, Smax), self.kv_cache_kind
         self.kvw = 2 * self.hkv * self.hd
         # one [B, Smax, K|V] slab per layer: a decode step reads keys/values with row stride kvw, batch stride Smax*kvw
-        self.kv_cache = [b16(B, Smax, self.kvw) for _ in range(self.L)]
+        self.kv_cache = self.kv_scale = self.kv_scale_v = None              # free the old slabs before the new ones are made
+        if self.kv_cache_kind == "fp8":                                      # e4m3 bytes + fp32 scales [B, Smax, K heads | V heads]
+            self.kv_cache = [torch.empty(B, Smax, self.kvw, dtype=torch.uint8, device=dev) for _ in range(self.L)]
+            self.kv_scale = [torch.empty(B, Smax, 2 * self.hkv, dtype=F32, device=dev) for _ in range(self.L)]
+            self.kv_scale_v = [sc[:, :, self.hkv:] for sc in self.kv_scale]
+        else:
+            self.kv_cache = [b16(B, Smax, self.kvw) for _ in range(self.L)]
         fr = torch.outer(torch.arange(Smax, device=dev, dtype=F32), self.inv_freq)
         self.gen_cos_sin = torch.stack([fr.cos(), fr.sin()], dim=1).contiguous()
         self.g_x, self.g_xm, self.g_hb = b16(B, h), b16(B, h), b16(B, h)
@@ -1807,19 +1837,27 @@ class CausalLMHIP:
                 mm(self.g_hb, w, w8, out, N, h, **kw)
         # long caches: split-KV kernel (K / V once per GQA group, a row's chunks on different CUs); a rule of the shape alone
         split_kv = self.hd == 128 and self.hq // self.hkv <= 8 and cur + 1 >= H.DECODE_ATTN_MIN_KEYS
+        kv8 = self._gen_kind == "fp8"                   # FP8 cache: the kv8 kernel at every cur (the forward kernel cannot read bytes)
         for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
             q8 = ly["q8"] if fp8 else {}
             if self.lora is None:
                 proj(x, ly["n1"], ly["wqkv"], q8.get("wqkv"), self.g_qkv, self.qkvw)
             else:                                                             # the merged weight stays on H.gemm at every B
                 proj(x, ly["n1"], self._lora_merged(li), None, self.g_qkv, self.qkvw, wide=False)
-            H.rope_kv_append(self.g_qkv, self.qkvw, B, 1, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"),
-                             c.rms_norm_eps, pos_shift, cache, Smax * self.kvw, self.kvw, cur)     # rotate q,k + append K|V at slot cur
+            if kv8:
+                sc = self.kv_scale[li]
+                H.rope_kv_append_e4m3(self.g_qkv, self.qkvw, B, 1, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"),
+                                      c.rms_norm_eps, pos_shift, cache, Smax * self.kvw, self.kvw, sc, Smax * 2 * self.hkv, 2 * self.hkv, cur)
+            else:
+                H.rope_kv_append(self.g_qkv, self.qkvw, B, 1, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"),
+                                 c.rms_norm_eps, pos_shift, cache, Smax * self.kvw, self.kvw, cur)     # rotate q,k + append K|V at slot cur
             ad = H.attn_desc(self.g_qkv, cache, cache, self.g_att, self.g_lse, batch=B, hq=self.hq, hkv=self.hkv, sq=1, sk=cur + 1,
                              hd=self.hd, scale=scale, causal=False, kv_start=kv_start, q_off=0, k_off=0, v_off=self.hkv * self.hd,
                              q_rs=self.qkvw, k_rs=self.kvw, v_rs=self.kvw, o_rs=self.hq * self.hd,
                              q_bs=self.qkvw, k_bs=Smax * self.kvw, v_bs=Smax * self.kvw, o_bs=self.hq * self.hd)
-            if split_kv:
+            if kv8:
+                H.attention_decode_kv8(ad, sc, self.kv_scale_v[li], Smax * 2 * self.hkv, 2 * self.hkv, self.g_attn_ws)
+            elif split_kv:
                 H.attention_decode(ad, self.g_attn_ws)
             else:
                 H.attention_fwd(ad)
@@ -2169,6 +2207,14 @@ class DeSTA25AudioModel:
         if kind not in CausalLMHIP.DECODE_WEIGHT_KINDS:
             raise ValueError(f"decode_weights must be one of {CausalLMHIP.DECODE_WEIGHT_KINDS}, got {kind!r}")
         self.llm.set_decode_weights(kind)
+
+    def set_kv_cache(self, kind: str) -> None:
+        """What the LLM's KV cache holds during `generate` / `_generate_step` / the trainer's evaluate: "bf16" (default) or "fp8"
+        (OCP e4m3 bytes + per-head power-of-two scales; `CausalLMHIP.set_kv_cache`).  ORCA's audio K|V and Whisper's ASR decoder
+        keep their own bf16 caches."""
+        if kind not in CausalLMHIP.KV_CACHE_KINDS:
+            raise ValueError(f"kv_cache must be one of {CausalLMHIP.KV_CACHE_KINDS}, got {kind!r}")
+        self.llm.set_kv_cache(kind)
 
     def eval(self):
         return self.train(False)

@@ -173,6 +173,18 @@ def decode_weights_kind(cfg: Cfg) -> str:
     return kind
 
 
+KV_CACHE = ("bf16", "fp8")
+
+
+def kv_cache_kind(cfg: Cfg) -> str:
+    """trainer.kv_cache (this port's key; absent = "bf16"): what the LLM's KV cache holds during evaluate / generate.
+    "fp8" = OCP e4m3 bytes + per-head power-of-two scales (`DeSTA25AudioModel.set_kv_cache`)."""
+    kind = str(cfg.trainer.get("kv_cache", "bf16"))
+    if kind not in KV_CACHE:
+        raise ValueError(f"trainer.kv_cache={kind!r} is not supported (choose one of {', '.join(KV_CACHE)})")
+    return kind
+
+
 def load_pretrained_weights(model, path: str) -> None:
     """Lightning-style {'state_dict': ...} with a 'model.' prefix (reference :73-83); tensors only."""
     import torch
@@ -235,6 +247,7 @@ def main(argv=None):
     if cfg.get("resume_from_checkpoint") and cfg.get("init_from_pretrained_weights"):
         raise AssertionError("Cannot provide both resume_from_checkpoint and init_from_pretrained_weights")
     decode_weights = decode_weights_kind(cfg)                               # a bad value fails here, before any GPU work
+    kv_cache = kv_cache_kind(cfg)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
@@ -242,6 +255,7 @@ def main(argv=None):
     from desta.trainer.desta_trainer import DeSTA25Trainer
     model = create_model(cfg, device=f"cuda:{local}")
     model.set_decode_weights(decode_weights)
+    model.set_kv_cache(kv_cache)
     if cfg.get("init_from_pretrained_weights"):
         load_pretrained_weights(model, cfg.init_from_pretrained_weights)
     train_ds, eval_ds, collate, tok = create_datasets(cfg, model, rank)

@@ -478,6 +478,27 @@ int    desta_attention_decode_chunk(void);         /* DESTA_ATTN_DECODE_CHUNK as
 size_t desta_attention_decode_workspace_bytes(int batch, int n_q_heads, int seq_k, int head_dim);
 int    desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Decode attention on the opt-in FP8 KV cache (additive to ABI 8: no struct changes): desta_attention_decode for a cache that
+ * holds OCP e4m3fn bytes, the quantised `DynamicCache` of llm_model.generate (modeling_desta25.py:1419;
+ * TF:models/llama/modeling_llama.py:230-281 with past_key_values, TF:cache_utils.py QuantizedCache).
+ * Cache format, per layer:
+ *   bytes  [batch][slots][2 * n_kv_heads * 128]  e4m3fn, K heads then V heads, the element order of the bf16 slab;
+ *   scales [batch][slots][2 * n_kv_heads]        fp32, one per (row, slot, K-or-V head).
+ * Scale and bytes follow desta_quantize_rows_e4m3 with "row" = one head's 128 values: scale = 2^e, e the smallest integer with
+ * amax * 2^-e <= 448, an all-zero head gets 1; q = e4m3fn(x * 2^-e), round to nearest even, nothing saturates.  q * scale is
+ * exactly a bf16 value.  2 048 + 64 bytes per cached token and layer at 8 KV heads against 4 096 for bf16.
+ * d->K / d->V point at the bytes and their strides count elements (= bytes, the convention of desta_gemm_w8a16_nt's ldb);
+ * k_scale / v_scale point at the first K / V scale of head 0 (scales and scales + n_kv_heads of the tensor above) and share
+ * scale_batch_stride / scale_row_stride (floats).  Everything else in the descriptor, the workspace
+ * (desta_attention_decode_workspace_bytes) and the rejections are desta_attention_decode's, plus NULL scales.  Neither bytes
+ * nor scales of slots outside [kv_start, seq_k) are read.  O, lse and every workspace partial equal desta_attention_decode's
+ * on the dequantised cache bf16(q * scale), bit for bit, as long as nothing underflows: a power of two commutes with an fp32
+ * rounding only in the normal range, so the identity is promised for scales for which score * k_scale and p * v_scale stay
+ * normal fp32 values and q * scale stays a normal bf16 value (any head whose amax is above ~2^-100; the caches of real models
+ * are many orders of magnitude inside).  Below that the result is still the attention of the dequantised cache to rounding. */
+int    desta_attention_decode_kv8(const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t scale_batch_stride,
+                                  int64_t scale_row_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* layer_prompts[j].expand(B,-1,-1) for all taps at once (modeling_desta25.py:589): prompts fp32
  * [taps][n], n = prompt_size*d -> rows [(taps*batch)][n] in fp32 and bf16; prompt_grad sums the
  * gradient back over the batch. */
@@ -554,6 +575,17 @@ int desta_rope_kv_append(void* qkv, int64_t ld, int rows, int seq, int n_q_heads
                          const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
                          const int32_t* pos_shift, void* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
                          int slot0, void* stream);
+
+/* desta_rope_kv_append for the FP8 KV cache (format: desta_attention_decode_kv8): q and k are rotated in place with the bits
+ * desta_rope_kv_append leaves (q/k-norm included); the rotated K heads and the V heads of row (b, s) are quantised per head
+ * and written as bytes to kv_cache + b*kv_batch_stride + (slot0 + s)*kv_row_stride and as scales to
+ * kv_scale + b*scale_batch_stride + (slot0 + s)*scale_row_stride, K heads then V heads.  One launch; head_dim 128 only.
+ * `DynamicCache.update` of a quantised cache inside `llm_model.generate` (modeling_desta25.py:1419), prompt (seq = prompt
+ * length, slot0 = 0) and decode step (seq = 1, slot0 = cache length). */
+int desta_rope_kv_append_e4m3(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                              const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
+                              const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                              float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: the MEAN over ranks of the flat fp32 gradient arena as one

@@ -10,7 +10,10 @@ is kernel time only while the host enqueues faster than the device runs: `enqueu
 calls (no synchronise), and a line whose enqueue time reaches 90 % of a leg's us is marked HOST-BOUND (that leg's figure is then an
 upper bound of its kernel time, and the ratio says nothing about the kernels).  `win` = the split-KV leg is faster by more than the
 two spreads added: DECODE_ATTN_MIN_KEYS is the smallest multiple of 64 (>= 256) from which every batch size says win.
-  python tools/decode_attn_bench.py [--batches 1,8,16,32,64] [--keys 128,256,512,1024,2048,4096] [--rounds 3] [--slabs 32]"""
+--kv fp8: the kv8 kernel (desta_attention_decode_kv8) on [B, Smax, 4096] e4m3 byte slabs + [B, Smax, 16] fp32 scales against the
+bf16 split-KV kernel (the shipped path from DECODE_ATTN_MIN_KEYS keys on, NOT the forward kernel) at every length; each leg's
+GB/s counts the bytes that leg streams (bytes + scales for kv8), x = bf16 split-KV median / kv8 median.
+  python tools/decode_attn_bench.py [--batches 1,8,16,32,64] [--keys 128,256,512,1024,2048,4096] [--rounds 3] [--slabs 32] [--kv {bf16,fp8}]"""
 import argparse
 import os
 import sys
@@ -43,13 +46,21 @@ def main():
     ap.add_argument("--keys", default="128,256,512,1024,2048,4096")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--slabs", type=int, default=32)
+    ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16", help="fp8: kv8 kernel against the bf16 split-KV kernel")
     a = ap.parse_args()
     assert a.rounds >= 3, "at least three alternations"
     keys = [int(k) for k in a.keys.split(",")]
     Smax, qkvw, kvw = max(keys), (HQ + 2 * HKV) * HD, 2 * HKV * HD
-    print(f"chunk {H.DECODE_ATTN_CHUNK} keys, dispatch threshold {H.DECODE_ATTN_MIN_KEYS} keys, {a.slabs} slabs of [B, {Smax}, {kvw}] bf16")
+    kv8 = a.kv == "fp8"
+    names = ("kv8", "split-KV") if kv8 else ("split-KV", "forward")
+    print(f"chunk {H.DECODE_ATTN_CHUNK} keys, dispatch threshold {H.DECODE_ATTN_MIN_KEYS} keys, {a.slabs} slabs of [B, {Smax}, {kvw}] bf16"
+          + (f" and {a.slabs} of [B, {Smax}, {kvw}] e4m3 bytes + [B, {Smax}, {2 * HKV}] fp32 scales; MiB = both legs' visible bytes" if kv8 else ""))
     for B in (int(b) for b in a.batches.split(",")):
         slabs = [torch.empty(B, Smax, kvw, dtype=torch.bfloat16, device="cuda").normal_() for _ in range(a.slabs)]
+        if kv8:                                                              # finite e4m3 bytes of either sign, scales 2^-7 (a Gaussian head's)
+            slabs8 = [(torch.randint(0, 0x78, (B, Smax, kvw), dtype=torch.uint8, device="cuda") | (torch.randint(0, 2, (B, Smax, kvw), dtype=torch.uint8, device="cuda") << 7))
+                      for _ in range(a.slabs)]
+            scales = [torch.full((B, Smax, 2 * HKV), 2.0 ** -7, dtype=torch.float32, device="cuda") for _ in range(a.slabs)]
         qkv = torch.randn(B, qkvw, device="cuda").to(torch.bfloat16)
         out = torch.empty(B, HQ * HD, dtype=torch.bfloat16, device="cuda")
         lse = torch.empty(B, HQ, 1, dtype=torch.float32, device="cuda")
@@ -61,11 +72,23 @@ def main():
                                  q_off=0, k_off=0, v_off=HKV * HD, q_rs=qkvw, k_rs=kvw, v_rs=kvw, o_rs=HQ * HD,
                                  q_bs=qkvw, k_bs=Smax * kvw, v_bs=Smax * kvw, o_bs=HQ * HD) for s in slabs]
 
-            def new(i):
-                H.attention_decode(descs[i], ws)
+            if kv8:
+                descs8 = [H.attn_desc(qkv, s, s, out, lse, batch=B, hq=HQ, hkv=HKV, sq=1, sk=sk, hd=HD, scale=HD ** -0.5, causal=False, kv_start=kv0,
+                                      q_off=0, k_off=0, v_off=HKV * HD, q_rs=qkvw, k_rs=kvw, v_rs=kvw, o_rs=HQ * HD,
+                                      q_bs=qkvw, k_bs=Smax * kvw, v_bs=Smax * kvw, o_bs=HQ * HD) for s in slabs8]
+                vsc = [sc[:, :, HKV:] for sc in scales]
 
-            def old(i):
-                H.attention_fwd(descs[i])
+                def new(i):
+                    H.attention_decode_kv8(descs8[i], scales[i], vsc[i], Smax * 2 * HKV, 2 * HKV, ws)
+
+                def old(i):
+                    H.attention_decode(descs[i], ws)
+            else:
+                def new(i):
+                    H.attention_decode(descs[i], ws)
+
+                def old(i):
+                    H.attention_fwd(descs[i])
 
             for fn in (new, old):                                            # warm up both legs on every slab
                 for i in range(a.slabs):
@@ -79,13 +102,16 @@ def main():
             mn, mo = sorted(tn)[len(tn) // 2], sorted(to)[len(to) // 2]
             sn, so = max(tn) - min(tn), max(to) - min(to)
             cache = B * sk * kvw * 2                                         # K + V bytes of one slab's visible cache
-            where = "HBM " if cache * a.slabs > 256 * 2**20 else "MALL"
+            cache_new = B * sk * (kvw + 2 * HKV * 4) if kv8 else cache       # kv8: bytes + scales
+            where = "HBM " if (cache + cache_new if kv8 else cache) * a.slabs > 256 * 2**20 else "MALL"
             hb = " HOST-BOUND" if min(en) > 0.9 * mn or min(eo) > 0.9 * mo else ""
             win = "win " if mo - mn > sn + so else "no  "
-            print(f"B={B:2d} keys={sk:4d} {where} {cache * a.slabs / 2**20:8.0f} MiB  split-KV {mn:8.1f}us (spread {sn:5.1f}, enqueue {min(en):5.1f}) "
-                  f"{cache / mn / 1e3:7.1f} GB/s   forward {mo:8.1f}us (spread {so:5.1f}, enqueue {min(eo):5.1f}) {cache / mo / 1e3:7.1f} GB/s   "
+            print(f"B={B:2d} keys={sk:4d} {where} {(cache + cache_new if kv8 else cache) * a.slabs / 2**20:8.0f} MiB  {names[0]} {mn:8.1f}us (spread {sn:5.1f}, enqueue {min(en):5.1f}) "
+                  f"{cache_new / mn / 1e3:7.1f} GB/s   {names[1]} {mo:8.1f}us (spread {so:5.1f}, enqueue {min(eo):5.1f}) {cache / mo / 1e3:7.1f} GB/s   "
                   f"x{mo / mn:5.2f} {win}{hb}", flush=True)
         del slabs, descs
+        if kv8:
+            del slabs8, scales, descs8, vsc
         torch.cuda.empty_cache()
 
 

@@ -4,11 +4,14 @@ rate of the decode GEMMs (bytes of frozen LLM weights read per token / token tim
 
   python tools/decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 8] [--ctx 64] [--prompt-tail 16] [--new 64]
                                [--do-sample --temperature T --top-p P --top-k K --min-p M --repetition-penalty R]
-                               [--weights {bf16,fp8}] [--ab [--rounds R]] [--attn-ab [--rounds R]]
+                               [--weights {bf16,fp8}] [--ab [--rounds R]] [--attn-ab [--rounds R]] [--kv {bf16,fp8}] [--kv-ab [--rounds R]]
 Without --do-sample the decode is greedy (with --repetition-penalty, through the full-chain sampler kernel).
 --weights: what the decode steps stream (`set_decode_weights`; fp8 = weight-only OCP e4m3, half the bytes).  --ab alternates
 bf16 and fp8 in ONE process on one model (R rounds of bf16, fp8) and prints one line per leg and round plus a summary with the
 spread over the rounds: the bf16 leg of the same process is the yardstick, never a number from another box.
+--kv: what the LLM's KV cache holds (`set_kv_cache`; fp8 = e4m3 bytes + per-head scales, 0.516 of the bytes).  --kv-ab alternates
+the two cache kinds for the chosen --weights in ONE process, R rounds, same report, plus the bytes each kind's slabs allocate
+(`torch.cuda.memory_allocated` deltas around the first allocation).
 --attn-ab alternates, for the chosen --weights, the decode step's attention dispatch (split-KV kernel from
 H.DECODE_ATTN_MIN_KEYS keys on) with the forward kernel at every length (H.DECODE_ATTN_MIN_KEYS = 1 << 30, the path before the
 split-KV kernel) in ONE process, R rounds, same report.
@@ -40,7 +43,9 @@ def main():
     ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16")
     ap.add_argument("--ab", action="store_true", help="alternate bf16 / fp8 decode weights in this process")
     ap.add_argument("--attn-ab", action="store_true", help="alternate split-KV / forward-kernel decode attention in this process")
-    ap.add_argument("--rounds", type=int, default=3, help="--ab / --attn-ab: alternations")
+    ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--kv-ab", action="store_true", help="alternate bf16 / fp8 KV cache in this process")
+    ap.add_argument("--rounds", type=int, default=3, help="--ab / --attn-ab / --kv-ab: alternations")
     a = ap.parse_args()
     gen = dict(do_sample=a.do_sample, temperature=a.temperature, top_p=a.top_p, top_k=a.top_k, min_p=a.min_p,
                repetition_penalty=a.repetition_penalty)
@@ -64,6 +69,8 @@ def main():
     mode = "sample " + " ".join(f"{k}={v}" for k, v in gen.items() if k != "do_sample" and v is not None) if a.do_sample else \
         ("greedy" + (f" repetition_penalty={a.repetition_penalty}" if a.repetition_penalty is not None else ""))
 
+    model.set_kv_cache(a.kv)
+
     def leg(kind):
         model.set_decode_weights(kind)
         res = []
@@ -81,7 +88,7 @@ def main():
         prompt_ms = res[0] * 1e3
         tok_ms = (res[1] - res[0]) * 1e3 / (a.new - 1)
         wbytes = welems * (1 if kind == "fp8" else 2)
-        r = {"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "decode_weights": kind, "prompt_ms": round(prompt_ms, 2),
+        r = {"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "decode_weights": kind, "kv_cache": model.llm.kv_cache_kind, "prompt_ms": round(prompt_ms, 2),
              "ms_per_token_step": round(tok_ms, 3), "tokens_per_s": round(B / tok_ms * 1e3, 1),
              "weight_bytes_per_step": wbytes, "weight_stream_GBps": round(wbytes / tok_ms / 1e6, 1), "hbm_peak_GBps": 8000}
         print(json.dumps(r), flush=True)
@@ -113,6 +120,38 @@ def main():
                           "median_speedup": round(med["forward"] / med["split_kv"], 3),
                           "margin_ms_worst_case": round(lo["forward"] - hi["split_kv"], 3),
                           "split_kv_faster_beyond_spread": bool(med["forward"] - med["split_kv"] > sum(hi[k] - lo[k] for k in runs))}))
+        return
+    if a.kv_ab:
+        runs = {"bf16": [], "fp8": []}
+        prompt = {"bf16": [], "fp8": []}
+        alloc = {}
+        for kind in ("bf16", "fp8"):                                         # warm-up; the slabs of a kind are made by its first run
+            model.set_kv_cache(kind)
+            torch.cuda.synchronize()
+            m0 = torch.cuda.memory_allocated()
+            model.llm._gen_alloc(B, S + a.new)
+            nb = sum(x.numel() * x.element_size() for x in model.llm.kv_cache + (model.llm.kv_scale or []))
+            alloc[kind] = {"slab_bytes": nb, "memory_allocated_delta": torch.cuda.memory_allocated() - m0}
+            model.llm._gen_shape = None
+            leg(a.weights)
+        for _ in range(a.rounds):
+            for kind in runs:
+                model.set_kv_cache(kind)
+                n8, n16 = H.ATTN_KV8_CALLS, H.ATTN_DECODE_CALLS
+                r = leg(a.weights)
+                assert (H.ATTN_KV8_CALLS > n8) == (kind == "fp8") and (kind == "bf16" or H.ATTN_DECODE_CALLS == n16)
+                runs[kind].append(r["ms_per_token_step"]), prompt[kind].append(r["prompt_ms"])
+        model.set_kv_cache(a.kv)
+        lo = {k: min(v) for k, v in runs.items()}
+        hi = {k: max(v) for k, v in runs.items()}
+        med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+        print(json.dumps({"kv_ab": f"{a.config} B={B} prompt={S} new={a.new} {mode} weights={a.weights}", "rounds": a.rounds,
+                          "bf16_ms_per_step": runs["bf16"], "fp8_ms_per_step": runs["fp8"], "prompt_ms": prompt,
+                          "spread_ms": {k: round(hi[k] - lo[k], 3) for k in runs},
+                          "median_speedup": round(med["bf16"] / med["fp8"], 3),
+                          "margin_ms_worst_case": round(lo["bf16"] - hi["fp8"], 3),
+                          "fp8_faster_beyond_spread": bool(med["bf16"] - med["fp8"] > sum(hi[k] - lo[k] for k in runs)),
+                          "cache_bytes": alloc, "cache_bytes_ratio": round(alloc["fp8"]["slab_bytes"] / alloc["bf16"]["slab_bytes"], 4)}))
         return
     if not a.ab:
         leg(a.weights)
