@@ -1,0 +1,123 @@
+"""Host (no GPU): the per-element fp64 criterion of tests/attention_reference.py is proved before it is pointed at a kernel.
+
+For a subset of test_gpu_ops.ATTN_CASES (causal GQA head dim 128 with and without padding, head dim 64 causal with padding, the
+flat 64 x 1500 cross-attention, 130 x 700 non-causal) and inputs of this test's own (seed below, not the GPU test's):
+  * the conforming emulation stays inside the bound (worst |err| / bound < 1) on O, dQ, dK and dV, with either forward's rounding;
+  * every seeded mutation (attention_reference.MUTATIONS) is REJECTED by the per-element criterion (`accepted`: within twice
+    the emulation's ratio on the same case and tensor, and within 2).  A mutation it cannot reject at a case is printed by name
+    (run with -s) and counted: at least four of the five must be rejected at every case.  `gqa_short_sum` needs a GQA group
+    and is reported as not applicable where Hq == Hkv (so the other four must all be rejected there);
+  * at the LLM's shape (2, 8, 2, 640, 640, 128) each of the five PASSES the whole-tensor rel-L2 criterion of
+    test_attention_fwd_bwd (8e-3 forward, 1.5e-2 backward).  At the small cases 32 wrong rows are up to an eighth of the tensor
+    and the norm notices some of them (tile_edge_key at 257 x 257 D = 128 and the two non-causal cases, diagonal_key at
+    160 x 160 and 130 x 700, delta_neighbour at 130 x 700); that is printed, and every mutation must pass the old criterion
+    and be rejected by the new one at three cases or more.
+Measured (this seed): emulation ratios O 0.16-0.89, dQ 0.15-0.40, dK 0.42-0.63, dV 0.54-0.84; mutated 1.7-166."""
+import pytest
+import torch
+
+import attention_reference as R
+
+HOST_CASES = [
+    # B, Hq, Hkv, Sq, Sk, D, causal, pad  (entries of test_gpu_ops.ATTN_CASES)
+    (2, 4, 2, 160, 160, 128, True, [0, 37]),
+    (1, 4, 2, 257, 257, 128, True, None),
+    (2, 8, 2, 640, 640, 128, True, [0, 100]),
+    (2, 2, 1, 257, 257, 64, True, [0, 5]),
+    (2, 3, 3, 64, 1500, 64, False, None),
+    (1, 2, 2, 130, 700, 128, False, None),
+]
+SEED = 20240611
+_REF = {}
+
+
+def _reference(case):
+    """(operands, exact, emulation with the 4-wave forward, its ratios, ratios of the emulation with the 8-wave forward)"""
+    key = repr(case)
+    if key not in _REF:
+        ops = R.operands(case, seed=SEED + case[3] + case[4])
+        ref, emu, ratios = R.reference(ops)
+        _REF[key] = (ops, ref, emu[False], ratios[False], ratios[True])
+    return _REF[key]
+
+
+def _args(ops):
+    return ops["q"], ops["k"], ops["v"], ops["do"], ops["scale"], ops["causal"], ops["kv_start"]
+
+
+def test_host_cases_are_attn_cases():
+    from test_gpu_ops import ATTN_CASES
+    for c in HOST_CASES:
+        assert c in ATTN_CASES, c
+
+
+@pytest.mark.parametrize("case", HOST_CASES)
+def test_emulation_is_inside_the_bound(case):
+    ops, ref, emu, ratios, ratios8 = _reference(case)
+    print(case, {n: round(r, 3) for n, r in ratios.items()})
+    print("  with the 8-wave forward's deferred reference:", {n: round(r, 3) for n, r in ratios8.items()})
+    for n in R.TENSORS:
+        assert ratios[n] < 1.0 and ratios8[n] < 1.0, (n, ratios[n], ratios8[n])
+        assert R.rel_l2(emu[n], ref[n]) < R.OLD_LIMIT[n]
+    assert torch.equal(emu["lse"], ref["lse"])                      # the emulation rounds no statistic
+    # exact zeros where nothing is visible: padded query rows (seq_q == seq_k) and keys in front of kv_start
+    if ops["kv_start"] is not None:
+        for b, pl in enumerate(ops["kv_start"].tolist()):
+            assert float(ref["dK"][b, :pl].abs().max() if pl else 0.0) == 0.0 and float(ref["M_dK"][b, :pl].abs().max() if pl else 0.0) == 0.0
+            if pl and case[3] == case[4]:
+                assert float(ref["O"][b, :pl].abs().max()) == 0.0 and bool(torch.isinf(ref["lse"][b, :, :pl]).all())
+                bad = emu["O"].clone()
+                bad[b, 0, 0, 0] = 2.0 ** -100                          # "exactly 0" means exactly
+                assert R.worst_ratio(ref, "O", bad) == float("inf")
+
+
+_OUTCOME = {}
+
+
+def _outcomes(case):
+    """{mutation: (old criterion passes, per-element criterion rejects, report line)}; None where the mutation does not apply."""
+    key = repr(case)
+    if key in _OUTCOME:
+        return _OUTCOME[key]
+    ops, ref, emu, ratios, ratios8 = _reference(case)
+    res = {}
+    for mut in R.MUTATIONS:
+        if mut == "gqa_short_sum" and case[1] == case[2]:
+            res[mut] = None
+            continue
+        out = R.emulate(*_args(ops), mutation=mut)
+        assert any(not torch.equal(out[n], emu[n]) for n in R.TENSORS), f"{mut} changed nothing at {case}"
+        old = {n: R.rel_l2(out[n], ref[n]) for n in R.TENSORS}
+        new = {n: R.worst_ratio(ref, n, out[n]) for n in R.TENSORS}
+        old_pass = all(old[n] < R.OLD_LIMIT[n] for n in R.TENSORS)
+        caught = [n for n in R.TENSORS if not R.accepted(new[n], ratios[n])]
+        if mut == "delta_neighbour":
+            caught = [n for n in caught if n in ("dQ", "dK")]          # this one is looked for where delta goes
+        worst = max(R.TENSORS, key=lambda n: new[n] / ratios[n])
+        line = (f"{mut}: whole-tensor rel-L2 O {old['O']:.1e} dQ {old['dQ']:.1e} dK {old['dK']:.1e} dV {old['dV']:.1e} "
+                f"{'PASSES' if old_pass else 'is rejected there too'}; per-element worst {worst} {new[worst]:.2f} "
+                f"(conforming {ratios[worst]:.2f}) " + (f"REJECTED on {','.join(caught)}" if caught else "NOT REJECTED"))
+        res[mut] = (old_pass, bool(caught), line)
+    _OUTCOME[key] = res
+    return res
+
+
+@pytest.mark.parametrize("case", HOST_CASES)
+def test_mutations_are_rejected_per_element(case):
+    res = _outcomes(case)
+    print(f"\n{case}\n  " + "\n  ".join(f"{m}: not applicable (no GQA group)" if r is None else r[2] for m, r in res.items()))
+    missed = [m for m, r in res.items() if r is None or not r[1]]
+    assert len(missed) <= 1, f"the per-element criterion does not reject {missed} at {case}"
+    if case[:6] == (2, 8, 2, 640, 640, 128):
+        # the LLM's shape: every one of the five is a bug today's whole-tensor criterion lets through
+        for m, r in res.items():
+            assert r[0] and r[1], r[2]
+
+
+def test_every_mutation_passes_the_old_criterion_somewhere_and_is_rejected_there():
+    """At the smaller cases 32 wrong rows are a large share of the tensor and the whole-tensor norm sees some of the mutations
+    too (printed above as 'is rejected there too'); each of the five passes it, and is rejected per element, at these cases:"""
+    for mut in R.MUTATIONS:
+        gaps = [c for c in HOST_CASES if _outcomes(c)[mut] is not None and _outcomes(c)[mut][0] and _outcomes(c)[mut][1]]
+        print(mut, "passes the whole-tensor criterion and is rejected per element at", len(gaps), "of", len(HOST_CASES), "cases")
+        assert len(gaps) >= 3, (mut, gaps)

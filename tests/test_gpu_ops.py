@@ -425,6 +425,19 @@ def test_attention_deferred_rescale_threshold(hip, D, spike):
         assert float((o.view(1, S, H, D) - ref.float()).abs().max()) < 4e-2          # |V| ~ N(0,1): a mis-scaled row is off by O(1)
     assert float((outs[0][0] - outs[1][0]).abs().max()) < 4e-2
     torch.testing.assert_close(outs[0][1], outs[1][1], rtol=1e-4, atol=1e-4)                 # log-sum-exp independent of the reference used
+    # per element against fp64 (tests/attention_reference.py): within twice the conforming emulation's worst |err| / bound, and
+    # within 2; lse against the fp64 value.  Each kernel against its own emulation: P rounded against the running maximum of every tile
+    # (4 waves) or against the deferred reference (8 waves, emulate(fwd8=True)).
+    import attention_reference as R
+    args = (q.view(1, S, H, D), k.view(1, S, H, D), v.view(1, S, H, D), torch.zeros(1, S, H, D), D ** -0.5, False, None)
+    ex = R.exact(*args)
+    for (o, lse), name in zip(outs, ("8-wave", "4-wave")):
+        emu_ratio = R.worst_ratio(ex, "O", R.emulate(*args, fwd8=name == "8-wave")["O"])
+        r = R.worst_ratio(ex, "O", o.view(1, S, H, D).double())
+        lse_err = float(((lse.double() - ex["lse"]).abs() / (1 + ex["lse"].abs())).max())
+        print(f"ATTN_FP64 spike {spike} D {D} {name}: O {r:.3f} ({emu_ratio:.3f}) lse {lse_err:.1e}")
+        assert R.accepted(r, emu_ratio), (name, r, emu_ratio)
+        assert lse_err <= 1e-4, (name, lse_err)
 
 
 def test_attention_fp32_output_copy_feeds_delta(hip):
