@@ -2229,6 +2229,65 @@ extern "C" int desta_attention_decode_kv8(const desta_attn_desc* d, const float*
     return DESTA_OK;
 }
 
+// ------------------------------------------------------------------------- FP8 KV cache -> bf16 staging slab (chunked prompt pass)
+// The forward kernels read bf16: a prompt chunk that attends an FP8 cache first gets the visible slots of ONE layer back as
+// bf16(e4m3(byte) * scale), the value attn_kv8_k forms in registers (the scale is a power of two: the product is exact).
+// One lane takes 16 values of one head: a 16-byte load of cache bytes, the head's scale (the 8 lanes of a head share the
+// address: one request), two 16-byte stores.  Block = KV8_DQ_SLOTS slots of one row; no LDS, no atomics.
+namespace {
+constexpr int KV8_DQ_SLOTS = 16;
+__global__ __launch_bounds__(256) void kv8_dequant_k(const uint8_t* __restrict__ cache, long c_bs, long c_rs, const float* __restrict__ scale,
+                                                     long s_bs, long s_rs, const int* __restrict__ kv_start, int n_heads, int slot1,
+                                                     bf16_t* __restrict__ out, long o_bs, long o_rs) {
+    const int b = blockIdx.y;
+    const int kv_lo = kv_start ? max(0, min(kv_start[b], slot1)) : 0;
+    const int first = max((int)blockIdx.x * KV8_DQ_SLOTS, kv_lo), last = min((int)blockIdx.x * KV8_DQ_SLOTS + KV8_DQ_SLOTS, slot1);
+    if (first >= last) return;                                 // a block in front of kv_start: nothing is read or written
+    const int per = n_heads * 8;                               // 16-value pieces of one slot
+    const int items = (last - first) * per;
+    cache += (long)b * c_bs;
+    scale += (long)b * s_bs;
+    out += (long)b * o_bs;
+    for (int i = threadIdx.x; i < items; i += 256) {
+        const int s = first + i / per, r = i % per;
+        const uint4 q = *(const uint4*)(cache + (long)s * c_rs + 16 * r);
+        const float sc = scale[(long)s * s_rs + (r >> 3)];
+        union { bf16x8 v; u16x8 u; } lo, hi;
+        lo.v = e4m3x8_to_bf16(make_uint2(q.x, q.y));
+        hi.v = e4m3x8_to_bf16(make_uint2(q.z, q.w));
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            lo.u[e] = f2bf(bf2f(lo.u[e]) * sc);
+            hi.u[e] = f2bf(bf2f(hi.u[e]) * sc);
+        }
+        bf16_t* o = out + (long)s * o_rs + 16 * r;
+        *(u16x8*)o = lo.u;
+        *(u16x8*)(o + 8) = hi.u;
+    }
+}
+}  // namespace
+
+extern "C" int desta_kv8_dequant(const uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride, const float* kv_scale,
+                                 int64_t scale_batch_stride, int64_t scale_row_stride, const int32_t* kv_start, int batch, int n_heads,
+                                 int head_dim, int slot1, void* out_bf16, int64_t out_batch_stride, int64_t out_row_stride, void* stream) {
+    DESTA_CHECK_ARG(kv_cache && kv_scale && out_bf16, "kv8_dequant: null cache, scale or output");
+    DESTA_CHECK_ARG(head_dim == 128, "kv8_dequant: head_dim %d unsupported (128)", head_dim);
+    DESTA_CHECK_ARG(batch > 0 && batch <= 65535 && n_heads > 0 && n_heads <= 4096, "kv8_dequant: bad batch %d or n_heads %d", batch, n_heads);
+    DESTA_CHECK_ARG(slot1 > 0, "kv8_dequant: slot1 %d must be positive", slot1);
+    const long w = (long)n_heads * 128;
+    DESTA_CHECK_ARG(((size_t)kv_cache & 15) == 0 && kv_row_stride >= w && kv_row_stride % 16 == 0 && kv_batch_stride >= 0 && kv_batch_stride % 16 == 0,
+                    "kv8_dequant: cache must be 16-byte aligned with row / batch strides that are multiples of 16 bytes, rows of at least %ld", w);
+    DESTA_CHECK_ARG(scale_row_stride >= n_heads && scale_batch_stride >= 0, "kv8_dequant: bad scale stride");
+    DESTA_CHECK_ARG(((size_t)out_bf16 & 15) == 0 && out_row_stride >= w && out_row_stride % 8 == 0 && out_batch_stride >= 0 && out_batch_stride % 8 == 0,
+                    "kv8_dequant: output must be 16-byte aligned with row / batch strides that are multiples of 8 elements, rows of at least %ld", w);
+    const dim3 grid((unsigned)((slot1 + KV8_DQ_SLOTS - 1) / KV8_DQ_SLOTS), (unsigned)batch);
+    hipLaunchKernelGGL(kv8_dequant_k, grid, dim3(256), 0, (hipStream_t)stream, kv_cache, (long)kv_batch_stride, (long)kv_row_stride, kv_scale,
+                       (long)scale_batch_stride, (long)scale_row_stride, (const int*)kv_start, n_heads, slot1, (bf16_t*)out_bf16,
+                       (long)out_batch_stride, (long)out_row_stride);
+    DESTA_CHECK_LAUNCH("kv8_dequant");
+    return DESTA_OK;
+}
+
 // delta [batch][heads][seq_q], then (seq_q <= 64) up to ATTN_Q64_MAX_CHUNKS dQ partials of 64 x 64 floats per (batch, head)
 #define ATTN_Q64_MAX_CHUNKS 4
 extern "C" size_t desta_attention_bwd_workspace_floats(int batch, int n_q_heads, int seq_q) {

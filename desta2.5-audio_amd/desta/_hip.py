@@ -600,6 +600,21 @@ def attention_decode_kv8(d: AttnDesc, k_scale, v_scale, scale_bs, scale_rs, ws=N
     ATTN_KV8_CALLS += 1
 
 
+# One layer of the FP8 cache back as bf16 for the attention of a prompt chunk (`CausalLMHIP.prefill`; include/desta_hip.h).
+_kv8_dequant = _sig("desta_kv8_dequant", vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, i32, vp, i64, i64, vp)
+KV8_DEQUANT_CALLS = 0              # FP8-cache dequantisations issued by this process
+
+
+@_profiled("kv8_dequant", lambda *a, **k: 3.0 * a[7] * a[10] * a[8] * a[9])     # (an upper bound: one byte read, two written per slot of [0, slot1))
+def kv8_dequant(cache, kv_bs, kv_rs, scale, scale_bs, scale_rs, kv_start, batch, n_heads, hd, slot1, out, out_bs, out_rs):
+    """out[b, s, head] = bf16(e4m3(cache[b, s, head]) * scale[b, s, head]) for s in [kv_start[b], slot1); `n_heads` = K heads +
+    V heads of one slot.  Strides: cache in bytes, scale in floats, out in elements.  Nothing else is read or written."""
+    global KV8_DEQUANT_CALLS
+    check(_kv8_dequant(p(cache), int(kv_bs), int(kv_rs), p(scale), int(scale_bs), int(scale_rs), p(kv_start), int(batch), int(n_heads),
+                       int(hd), int(slot1), p(out), int(out_bs), int(out_rs), stream()), "desta_kv8_dequant")
+    KV8_DEQUANT_CALLS += 1
+
+
 @_profiled(lambda d, *a, **k: "attn_bwd:" + _attn_tag(d), lambda d, *a, **k: _attn_flops(d, 2.5))     # dS, dP recompute, dQ, dK, dV
 def attention_bwd(d: AttnDesc, do, dq, dk=None, dv=None, *, do_rs=None, dq_off=0, dk_off=0, dv_off=0, dq_rs=None,
                   dk_rs=None, dv_rs=None, do_bs=None, dq_bs=None, dk_bs=None, dv_bs=None, rope_cos_sin=None, dkv_t=None):

@@ -414,6 +414,22 @@ def check_decode_rows(B: int) -> None:
         raise ValueError(f"generate: a batch of {B} sequences, the KV-cached decode step takes at most {H.DECODE_MAX_ROWS}: split the batch")
 
 
+PREFILL_CHUNK_MIN = 16                              # positions: a 16-row MFMA tile; below it a chunk is launch overhead only
+
+
+def check_prefill_chunk(n) -> None:
+    """`set_prefill_chunk`: None (the training forward as the prompt pass) or an int of at least PREFILL_CHUNK_MIN positions."""
+    if n is None:
+        return
+    if isinstance(n, bool) or not isinstance(n, int) or n < PREFILL_CHUNK_MIN:
+        raise ValueError(f"prefill_chunk must be None or an int >= {PREFILL_CHUNK_MIN}, got {n!r}")
+
+
+def prefill_chunks(S: int, C: int) -> List[Tuple[int, int]]:
+    """Position ranges [c0, c1) of the chunked prompt pass: [0, S) in order, C positions each, a ragged last one."""
+    return [(c0, min(c0 + C, S)) for c0 in range(0, S, C)]
+
+
 @dataclass
 class GenerationOutput:
     """modeling_desta25.py:492-496"""
@@ -1233,17 +1249,34 @@ class OrcaHIP:
             else:
                 self.spans = torch.tensor([(b, 0, S) for b in range(B)], dtype=torch.int32, device=dev)
 
+    def _row_buffers(self, S: int) -> None:
+        """The per-row buffers of `inject` for S rows per sequence."""
+        B, h, dev = self.Bq, self.h, self.dev
+        M = B * S
+        self.M, self.S = M, S
+        self.q16, self.att16 = torch.empty(M, self.hp, dtype=BF16, device=dev), torch.empty(M, self.hp, dtype=BF16, device=dev)
+        self.lse = torch.empty(B, self.heads, S, dtype=F32, device=dev)
+        self.cross32, self.cross16 = torch.empty(M, h, dtype=F32, device=dev), torch.empty(M, h, dtype=BF16, device=dev)
+        self.g1 = torch.empty(M, h // 4, dtype=BF16, device=dev)
+
+    def begin_chunk(self, ci: int, Cc: int) -> None:
+        """generate() with a chunked prompt pass (`begin(..., S = the first chunk's positions, keep_kv=True)`): chunk ci injects into
+        Cc rows per sequence.  The first chunk projects every layer's audio K|V into `kv_layers`; later chunks reuse it, as the
+        decode steps do.  `begin_decode` still follows the last chunk."""
+        if self.audio is None:
+            return
+        self.decoding = ci > 0                                               # (`inject`: take K|V from `kv_layers`)
+        if Cc != self.S:
+            self.q16 = self.att16 = self.lse = self.cross32 = self.cross16 = self.g1 = None     # free before the new ones are made
+            self._row_buffers(Cc)
+
     def begin_decode(self) -> None:
         """generate(): after the prompt pass (`begin(..., keep_kv=True)` + `inject` per layer) every decode step injects into ONE new
         row per sequence; the audio keys / values of each layer do not change between steps and stay in `kv_layers`."""
         if self.audio is None:
             return
-        B, h, dev = self.Bq, self.h, self.dev
-        self.M, self.S, self.decoding = B, 1, True
-        self.q16, self.att16 = torch.empty(B, self.hp, dtype=BF16, device=dev), torch.empty(B, self.hp, dtype=BF16, device=dev)
-        self.lse = torch.empty(B, self.heads, 1, dtype=F32, device=dev)
-        self.cross32, self.cross16 = torch.empty(B, h, dtype=F32, device=dev), torch.empty(B, h, dtype=BF16, device=dev)
-        self.g1 = torch.empty(B, h // 4, dtype=BF16, device=dev)
+        self.decoding = True
+        self._row_buffers(1)
 
     def inject(self, l: int, x: torch.Tensor) -> None:
         """x [B*S, h] bf16 = output of decoder layer l (batch-major rows), updated IN PLACE: x + sigmoid(gate(x)) * LN(cross_attn(x, audio))."""
@@ -1489,6 +1522,20 @@ class CausalLMHIP:
         self.head8 = None
         self.kv_cache_kind = "bf16"                 # `set_kv_cache`: what generate()'s KV cache holds
         self.kv_cache = self.kv_scale = None
+        self.prefill_chunk = None                   # `set_prefill_chunk`: positions per chunk of generate()'s lean prompt pass; None = `forward`
+        self.kv_stage = self._pf = None
+
+    def set_prefill_chunk(self, n: Optional[int]) -> None:
+        """Prompt pass of generate(): None (default) = the training `forward` with its per-layer save set; an int >= 16 = the
+        lean `prefill`, which walks the prompt in chunks of n positions on rolling buffers shared by every layer and chunk, each
+        chunk attending the KV cache the earlier ones filled (n >= the prompt: one chunk).  Memory outside the cache then follows
+        n, not the prompt length or the layer count.  Under the FP8 cache a chunk attends every key, its own included, as the
+        decode steps will see it (dequantised e4m3); `forward` attends the bf16 projection."""
+        check_prefill_chunk(n)
+        if n != self.prefill_chunk:                                          # the chunk buffers (and the FP8 staging slab) go with the setting
+            self._pf = self.kv_stage = None
+            self._gen_shape = None
+        self.prefill_chunk = n
 
     # -- weight-only FP8 (e4m3) decode: a second, half-size copy of the frozen decode-side weights -------------------------------
     DECODE_WEIGHT_KINDS = ("bf16", "fp8")
@@ -1519,7 +1566,7 @@ class CausalLMHIP:
             raise ValueError(f"kv_cache 'fp8' needs head_dim 128 and at most 8 query heads per KV head, got head_dim {self.hd}, "
                              f"{self.hq // self.hkv} per KV head")
         if kind != self.kv_cache_kind:                                       # the other kind's slabs are freed; `_gen_alloc` makes the new ones
-            self.kv_cache = self.kv_scale = self.kv_scale_v = None
+            self.kv_cache = self.kv_scale = self.kv_scale_v = self.kv_stage = None
             self._gen_shape = None
         self.kv_cache_kind = kind
 
@@ -1788,11 +1835,15 @@ class CausalLMHIP:
         self._gen_shape, self._gen_kind = (B, Smax), self.kv_cache_kind
         self.kvw = 2 * self.hkv * self.hd
         # one [B, Smax, K|V] slab per layer: a decode step reads keys/values with row stride kvw, batch stride Smax*kvw
-        self.kv_cache = self.kv_scale = self.kv_scale_v = None              # free the old slabs before the new ones are made
+        self.kv_cache = self.kv_scale = self.kv_scale_v = self.kv_stage = None     # free the old slabs before the new ones are made
         if self.kv_cache_kind == "fp8":                                      # e4m3 bytes + fp32 scales [B, Smax, K heads | V heads]
             self.kv_cache = [torch.empty(B, Smax, self.kvw, dtype=torch.uint8, device=dev) for _ in range(self.L)]
             self.kv_scale = [torch.empty(B, Smax, 2 * self.hkv, dtype=F32, device=dev) for _ in range(self.L)]
             self.kv_scale_v = [sc[:, :, self.hkv:] for sc in self.kv_scale]
+            # chunked prompt pass: ONE layer's slots as bf16 for the forward kernel (`prefill`), 1 / L of a bf16 cache.  Zeroed: the
+            # dequantisation leaves the slots in front of kv_start alone, and the forward kernel multiplies the V rows of a masked
+            # key of the first visible tile by p = 0, so they have to be finite (in the bf16 cache the append writes them)
+            self.kv_stage = torch.zeros(B, Smax, self.kvw, dtype=BF16, device=dev) if self.prefill_chunk is not None else None
         else:
             self.kv_cache = [b16(B, Smax, self.kvw) for _ in range(self.L)]
         fr = torch.outer(torch.arange(Smax, device=dev, dtype=F32), self.inv_freq)
@@ -1807,6 +1858,86 @@ class CausalLMHIP:
         self.g_r = torch.empty(B, dtype=F32, device=dev)
         self.g_logits = torch.zeros(B, self.Vp, dtype=BF16, device=dev)
         self.g_next = torch.zeros(B, dtype=torch.int64, device=dev)
+
+    # -- lean, chunked prompt pass of generate() (`set_prefill_chunk`): nothing is kept for a backward ---------------------------
+    def _prefill_alloc(self, B: int, S: int, Cm: int) -> dict:
+        """Buffers of `prefill`: the prompt's embeddings [B*S, h] (the only one sized by S) and ONE set of per-chunk activations
+        for B * Cm rows, shared by every layer and chunk."""
+        pf = self._pf
+        if pf is not None and pf["key"] == (B, S, Cm):
+            return pf
+        self._pf = pf = None                                                 # free the old set before the new one is made
+        h, dev, M = self.h, self.dev, B * Cm
+
+        def b16(*s):
+            return torch.empty(*s, dtype=BF16, device=dev)
+        self._pf = pf = dict(key=(B, S, Cm), x0=b16(B * S, h), xa=b16(M, h), xb=b16(M, h), hb=b16(M, h), qkv=b16(M, self.qkvw),
+                             att=b16(M, self.hq * self.hd), xm=b16(M, h), gu=b16(M, 2 * self.I), act=b16(M, self.I),
+                             lse=torch.empty(B * self.hq * Cm, dtype=F32, device=dev), r=torch.empty(M, dtype=F32, device=dev))
+        return pf
+
+    def prefill(self, x0_filler, B: int, S: int, kv_start: torch.Tensor, last_logits: torch.Tensor, layer_hook=None, chunk_hook=None) -> torch.Tensor:
+        """The prompt pass of generate() without a save set (needs `_gen_alloc` and a chunk size): `x0_filler(buf)` writes
+        inputs_embeds [B*S, h]; the prompt is walked in the chunks of `prefill_chunks(S, self.prefill_chunk)`.  A chunk [c0, c1) of
+        every sequence runs through all layers with the kernels, weight forms and switches of `forward`'s generate() branch
+        (unfused q|k|v projection, the adapters merged, blocked gate|up + SwiGLU epilogue when `fuse_swiglu`; the copy of the
+        projection in front of the q/k-norm is a backward operand and is not made), appends its rotated K | V at slots [c0, c1)
+        (position = slot - left pad) and attends slots [kv_start, c1) of the layer's cache slab under the causal mask
+        "key <= query + (seq_k - seq_q)".  FP8 cache: the slots up to c1 are dequantised into the one staging slab first, so
+        every key, the chunk's own included, is the value the decode steps will read.  After the last chunk the last row of each
+        sequence is projected into `last_logits` [B, Vp].  `chunk_hook(i, Cc)` runs in front of chunk i (ORCA sizes its row
+        buffers), `layer_hook(l, x)` behind every layer on the chunk's rows [B*Cc, h] (batch-major)."""
+        c, h, hq, hkv, hd = self.c, self.h, self.hq, self.hkv, self.hd
+        chunks = prefill_chunks(S, self.prefill_chunk)
+        pf = self._prefill_alloc(B, S, chunks[0][1])
+        Smax, kvw, aw, eps = self._gen_shape[1], self.kvw, hq * hd, c.rms_norm_eps
+        kv8 = self._gen_kind == "fp8"
+        scale = hd ** -0.5
+        x0_filler(pf["x0"])
+        x0 = pf["x0"].view(B, S, h)
+        if self.lora is not None:
+            self.refresh_lora()
+        blocked = self.fuse_swiglu and "wgu_b" in self.layers[0]
+        for ci, (c0, c1) in enumerate(chunks):
+            Cc = c1 - c0
+            M = B * Cc
+            x, y, hb, qkv, att, xm, gu, act, r = (pf[k][:M] for k in ("xa", "xb", "hb", "qkv", "att", "xm", "gu", "act", "r"))
+            lse = pf["lse"][:B * hq * Cc].view(B, hq, Cc)
+            x.view(B, Cc, h).copy_(x0[:, c0:c1])                              # the chunk's rows, batch-major
+            shift = (c0 - kv_start).to(torch.int32).contiguous()             # position of the chunk's row j: c0 + j - left pad
+            if chunk_hook is not None:
+                chunk_hook(ci, Cc)
+            for i, ly in enumerate(self.layers):
+                H.rmsnorm_fwd(x, ly["n1"], eps, hb, r)
+                H.gemm(hb, ly["wqkv"] if self.lora is None else self._lora_merged(i), qkv, M, self.qkvw, h)
+                cache = self.kv_cache[i]
+                if kv8:
+                    sc = self.kv_scale[i]
+                    H.rope_kv_append_e4m3(qkv, self.qkvw, M, Cc, hq, hkv, hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"), eps, shift,
+                                          cache, Smax * kvw, kvw, sc, Smax * 2 * hkv, 2 * hkv, c0)
+                    H.kv8_dequant(cache, Smax * kvw, kvw, sc, Smax * 2 * hkv, 2 * hkv, kv_start, B, 2 * hkv, hd, c1, self.kv_stage, Smax * kvw, kvw)
+                    kv = self.kv_stage
+                else:
+                    H.rope_kv_append(qkv, self.qkvw, M, Cc, hq, hkv, hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"), eps, shift,
+                                     cache, Smax * kvw, kvw, c0)
+                    kv = cache
+                H.attention_fwd(H.attn_desc(qkv, kv, kv, att, lse, batch=B, hq=hq, hkv=hkv, sq=Cc, sk=c1, hd=hd, scale=scale, causal=True,
+                                            kv_start=kv_start, q_off=0, k_off=0, v_off=hkv * hd, q_rs=self.qkvw, k_rs=kvw, v_rs=kvw, o_rs=aw,
+                                            k_bs=Smax * kvw, v_bs=Smax * kvw))
+                H.gemm(att, ly["wo"], xm, M, h, aw, residual=x)
+                H.rmsnorm_fwd(xm, ly["n2"], eps, hb, r)
+                if blocked:
+                    H.gemm(hb, ly["wgu_b"], gu, M, 2 * self.I, h, act=2, aux=act, ld_aux=self.I)
+                else:
+                    H.gemm(hb, ly["wgu"], gu, M, 2 * self.I, h)
+                    H.swiglu_fwd(gu, act, M, self.I)
+                H.gemm(act, ly["wd"], y, M, h, self.I, residual=xm)
+                if layer_hook is not None:
+                    layer_hook(i, y)
+                x, y = y, x
+        H.rmsnorm_fwd(x, self.norm, eps, hb, r)
+        H.gemm(hb[Cc - 1:], self.head, last_logits, B, self.V, h, lda=Cc * h, ldc=self.Vp)     # row Cc - 1 of each sequence: A is a strided view
+        return last_logits
 
     def decode_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, pos_shift: torch.Tensor, layer_hook=None) -> torch.Tensor:
         """One token per sequence: `tokens` [B] (ids) sit at cache slot `cur`; returns logits [B, Vp] for slot cur+1."""
@@ -1873,12 +2004,13 @@ class CausalLMHIP:
                         eos_token_ids=None, forced_tokens: Optional[torch.Tensor] = None, collect_logits: bool = False,
                         do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0, seed: int = 0, layer_hook=None,
                         after_prompt=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                        repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None):
+                        repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None, chunk_hook=None):
         """Prompt pass + KV-cached decode (greedy, or temperature / top-p sampling with the library's counter RNG).  Returns new token ids [B, n_new] (int64; finished sequences are
         filled with pad_token_id, generation stops early once every sequence has produced an EOS), and, with
         collect_logits, the per-step logits [n_new, B, V] (bf16).  `forced_tokens` [B, T] teacher-forces the
         continuation (parity tests compare per-step logits with the oracle on the same prefix).  `layer_hook(l, x)` runs behind every
-        decoder layer of the prompt pass ([B*S, h]) and of every decode step ([B, h]); `after_prompt()` between the two.
+        decoder layer of the prompt pass ([B*S, h]; with `set_prefill_chunk` on the rows of one chunk, [B*Cc, h], `chunk_hook(i, Cc)` in
+        front of chunk i) and of every decode step ([B, h]); `after_prompt()` between the two.
         top_k / min_p (sampling) and repetition_penalty (both modes) switch to HF's whole processor chain in one kernel
         (`desta_sample_bf16`); None = off.  The penalty's history is what HF's `input_ids` hold: `prompt_ids` [B, S] (text-only
         chats, left padding included) followed by the tokens emitted so far, pad_token_id for finished rows."""
@@ -1891,8 +2023,11 @@ class CausalLMHIP:
         dev = self.dev
         kv_start = kv_start.to(torch.int32).contiguous()
         neg_pad = (-kv_start).contiguous()                                   # prompt: position = index - left_pad
-        logits = self.forward(x0_filler, B, S, kv_start, None, False, pos_shift=neg_pad, cos_sin=self.gen_cos_sin, last_logits=self.g_logits,
-                              kv_cache=self.kv_cache, layer_hook=layer_hook)
+        if self.prefill_chunk is not None:                                   # lean prompt pass: chunks on rolling buffers, no save set
+            logits = self.prefill(x0_filler, B, S, kv_start, self.g_logits, layer_hook=layer_hook, chunk_hook=chunk_hook)
+        else:
+            logits = self.forward(x0_filler, B, S, kv_start, None, False, pos_shift=neg_pad, cos_sin=self.gen_cos_sin, last_logits=self.g_logits,
+                                  kv_cache=self.kv_cache, layer_hook=layer_hook)
         if after_prompt is not None:
             after_prompt()
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
@@ -2216,6 +2351,14 @@ class DeSTA25AudioModel:
             raise ValueError(f"kv_cache must be one of {CausalLMHIP.KV_CACHE_KINDS}, got {kind!r}")
         self.llm.set_kv_cache(kind)
 
+    def set_prefill_chunk(self, n: Optional[int]) -> None:
+        """Prompt pass of `generate` / `_generate_step` / the trainer's evaluate: None (default) = the training forward with its
+        per-layer save set; an int >= 16 = the lean pass in chunks of n positions, whose memory outside the KV cache follows n
+        instead of the prompt length and the layer count (`CausalLMHIP.set_prefill_chunk`).  `score` / `score_batch` need every
+        position's logits and Whisper's ASR decoder has its own loop: both are unaffected."""
+        check_prefill_chunk(n)
+        self.llm.set_prefill_chunk(n)
+
     def eval(self):
         return self.train(False)
 
@@ -2450,16 +2593,18 @@ class DeSTA25AudioModel:
 
                 def fill(buf):
                     H.embed_gather(self.llm.embed, af, src, B * S, h, buf)
-                hook = after = None
+                hook = after = chunk = None
                 if self.orca is not None and N_audio > 0:
                     # ORCA branch (modeling_desta25.py:1375-1408): global tokens spliced above; the audio tokens reach every decoder layer
                     # through the gated cross-attention, at the prompt pass and at every KV-cached step (no alignment loss in eval mode)
                     assert N_audio == B and [int(r) for r, _ in starts] == list(range(B)), "orca_hybrid: one audio per text row, in row order"
                     orca = self.orca
                     local16 = orca.local_forward(self.enc_all, N_audio) if cfg.orca_local_enabled else None
-                    orca.begin(af, local16, B, S, None, False, keep_kv=True)
+                    pc = self.llm.prefill_chunk                               # chunked prompt pass: row buffers for one chunk (`begin_chunk`)
+                    orca.begin(af, local16, B, S if pc is None else min(S, pc), None, False, keep_kv=True)
                     if orca.audio is not None:
                         hook, after = orca.inject, orca.begin_decode
+                        chunk = orca.begin_chunk if pc is not None else None
                 eos = eos_token_id if eos_token_id is not None else cfg.llm_config.eos_token_id
                 if isinstance(eos, int):
                     eos = [eos]
@@ -2469,7 +2614,7 @@ class DeSTA25AudioModel:
                                                 temperature=1.0 if temperature is None else float(temperature),
                                                 top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after,
                                                 top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty,
-                                                prompt_ids=input_ids if prompt_in_history else None)
+                                                prompt_ids=input_ids if prompt_in_history else None, chunk_hook=chunk)
         finally:
             self.training = was_training
 

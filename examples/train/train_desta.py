@@ -185,6 +185,15 @@ def kv_cache_kind(cfg: Cfg) -> str:
     return kind
 
 
+def prefill_chunk(cfg: Cfg):
+    """trainer.prefill_chunk (this port's key; absent = None): positions per chunk of the lean prompt pass of evaluate / generate
+    (`DeSTA25AudioModel.set_prefill_chunk`); None keeps the training forward as the prompt pass."""
+    n = cfg.trainer.get("prefill_chunk", None)
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or n < 16):
+        raise ValueError(f"trainer.prefill_chunk={n!r} is not supported (an integer of at least 16 positions, or absent)")
+    return n
+
+
 def load_pretrained_weights(model, path: str) -> None:
     """Lightning-style {'state_dict': ...} with a 'model.' prefix (reference :73-83); tensors only."""
     import torch
@@ -248,6 +257,7 @@ def main(argv=None):
         raise AssertionError("Cannot provide both resume_from_checkpoint and init_from_pretrained_weights")
     decode_weights = decode_weights_kind(cfg)                               # a bad value fails here, before any GPU work
     kv_cache = kv_cache_kind(cfg)
+    chunk = prefill_chunk(cfg)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
@@ -256,6 +266,7 @@ def main(argv=None):
     model = create_model(cfg, device=f"cuda:{local}")
     model.set_decode_weights(decode_weights)
     model.set_kv_cache(kv_cache)
+    model.set_prefill_chunk(chunk)
     if cfg.get("init_from_pretrained_weights"):
         load_pretrained_weights(model, cfg.init_from_pretrained_weights)
     train_ds, eval_ds, collate, tok = create_datasets(cfg, model, rank)

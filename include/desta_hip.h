@@ -499,6 +499,21 @@ int    desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t 
 int    desta_attention_decode_kv8(const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t scale_batch_stride,
                                   int64_t scale_row_stride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The FP8 KV cache of one layer back as bf16, for the attention of a prompt chunk (additive to ABI 8): the forward kernel
+ * reads bf16, so a chunk that attends cached e4m3 keys gets them through a staging slab.  kv_cache / kv_scale: the bytes and
+ * scales of desta_attention_decode_kv8's format, n_heads = K heads + V heads of one slot (2 * n_kv_heads), head_dim 128;
+ * strides of the bytes in bytes, of the scales in floats, of the output in bf16 elements.  For every row b, slot s in
+ * [kv_start[b], slot1) (kv_start NULL: from 0; values are clamped to [0, slot1]) and head:
+ *   out[b][s][head][0..128) = bf16(e4m3(byte) * scale),
+ * exactly (the scale is a power of two), the value desta_attention_decode_kv8 forms in registers.  Slots below kv_start[b]
+ * and at or above slot1 are neither read (bytes, scales) nor written.  DESTA_EINVAL with nothing launched for head_dim != 128,
+ * batch <= 0, n_heads <= 0, slot1 <= 0, a NULL cache / scale / output, a cache that is not 16-byte aligned with strides that
+ * are multiples of 16 bytes, an output that is not 16-byte aligned with strides that are multiples of 8 elements, or a row
+ * stride narrower than the heads. */
+int    desta_kv8_dequant(const uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride, const float* kv_scale,
+                         int64_t scale_batch_stride, int64_t scale_row_stride, const int32_t* kv_start, int batch, int n_heads,
+                         int head_dim, int slot1, void* out_bf16, int64_t out_batch_stride, int64_t out_row_stride, void* stream);
+
 /* layer_prompts[j].expand(B,-1,-1) for all taps at once (modeling_desta25.py:589): prompts fp32
  * [taps][n], n = prompt_size*d -> rows [(taps*batch)][n] in fp32 and bf16; prompt_grad sums the
  * gradient back over the batch. */

@@ -5,6 +5,7 @@ rate of the decode GEMMs (bytes of frozen LLM weights read per token / token tim
   python tools/decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 8] [--ctx 64] [--prompt-tail 16] [--new 64]
                                [--do-sample --temperature T --top-p P --top-k K --min-p M --repetition-penalty R]
                                [--weights {bf16,fp8}] [--ab [--rounds R]] [--attn-ab [--rounds R]] [--kv {bf16,fp8}] [--kv-ab [--rounds R]]
+                               [--prefill-chunk N[,N...]] [--prefill-ab [--rounds R]]
 Without --do-sample the decode is greedy (with --repetition-penalty, through the full-chain sampler kernel).
 --weights: what the decode steps stream (`set_decode_weights`; fp8 = weight-only OCP e4m3, half the bytes).  --ab alternates
 bf16 and fp8 in ONE process on one model (R rounds of bf16, fp8) and prints one line per leg and round plus a summary with the
@@ -15,6 +16,11 @@ the two cache kinds for the chosen --weights in ONE process, R rounds, same repo
 --attn-ab alternates, for the chosen --weights, the decode step's attention dispatch (split-KV kernel from
 H.DECODE_ATTN_MIN_KEYS keys on) with the forward kernel at every length (H.DECODE_ATTN_MIN_KEYS = 1 << 30, the path before the
 split-KV kernel) in ONE process, R rounds, same report.
+--prefill-chunk N: the prompt pass is the lean chunked one (`set_prefill_chunk(N)`) in every leg above.  --prefill-ab alternates
+today's prompt pass (the training forward) and the chunked pass, one leg per N of a comma-separated --prefill-chunk, in ONE
+process for the chosen --kv: prompt ms (one generated token) and `torch.cuda.max_memory_allocated` of each leg, one leg at a time
+with the other legs' buffers dropped and `reset_peak_memory_stats` in between; a leg that does not fit reports "oom".  Under
+--kv fp8 one more chunked prompt per N runs with the kernel profile open: the share of desta_kv8_dequant in the prompt pass.
 """
 import argparse
 import json
@@ -45,8 +51,15 @@ def main():
     ap.add_argument("--attn-ab", action="store_true", help="alternate split-KV / forward-kernel decode attention in this process")
     ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16")
     ap.add_argument("--kv-ab", action="store_true", help="alternate bf16 / fp8 KV cache in this process")
-    ap.add_argument("--rounds", type=int, default=3, help="--ab / --attn-ab / --kv-ab: alternations")
+    ap.add_argument("--prefill-chunk", default=None, help="positions per chunk of the lean prompt pass (--prefill-ab: a comma-separated list)")
+    ap.add_argument("--prefill-ab", action="store_true", help="alternate today's prompt pass / the chunked pass in this process")
+    ap.add_argument("--rounds", type=int, default=3, help="--ab / --attn-ab / --kv-ab / --prefill-ab: alternations")
     a = ap.parse_args()
+    chunks = [int(x) for x in a.prefill_chunk.split(",")] if a.prefill_chunk else []
+    if a.prefill_ab and not chunks:
+        ap.error("--prefill-ab needs --prefill-chunk N[,N...]")
+    if not a.prefill_ab and len(chunks) > 1:
+        ap.error("several --prefill-chunk values need --prefill-ab")
     gen = dict(do_sample=a.do_sample, temperature=a.temperature, top_p=a.top_p, top_k=a.top_k, min_p=a.min_p,
                repetition_penalty=a.repetition_penalty)
     from desta.models.modeling_desta25 import DeSTA25AudioModel, DeSTA25Config
@@ -70,6 +83,90 @@ def main():
         ("greedy" + (f" repetition_penalty={a.repetition_penalty}" if a.repetition_penalty is not None else ""))
 
     model.set_kv_cache(a.kv)
+    if chunks and not a.prefill_ab:
+        model.set_prefill_chunk(chunks[0])
+
+    if a.prefill_ab:
+        llm = model.llm
+        model.set_decode_weights(a.weights)
+        fwd_bufs = ("cos_sin", "cos_sin_il", "pos_rows", "xs", "sv", "rf", "hb", "hbc", "act", "logits", "dxa", "dxb", "dgu", "dqkv", "datt")
+
+        def drop():                                                          # every leg starts without the other legs' activations
+            for n in fwd_bufs:
+                setattr(llm, n, None)
+            llm.B = llm.S = 0
+            llm._pf = llm.kv_cache = llm.kv_scale = llm.kv_scale_v = llm.kv_stage = None
+            llm._gen_shape = None
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+
+        def forward_bytes():                                                 # what `CausalLMHIP._alloc(B, S)` asks for: the training step's save set
+            M, L, h, I = B * S, llm.L, llm.h, llm.I
+            aw = llm.hq * llm.hd
+            per_layer = 2 * M * (llm.qkvw + aw + h + 2 * I) + 4 * (2 * M + B * llm.hq * S)
+            return 2 * M * ((L + 1) * h + 4 * h + I + llm.Vp + 2 * I + llm.qkvw + aw) + L * per_layer
+
+        def prompt(C):
+            model.set_prefill_chunk(C)
+            drop()
+            if C is None and forward_bytes() > torch.cuda.mem_get_info()[0]:  # do not walk into the allocator's limit on purpose
+                r = {"prompt_ms": "oom", "peak_GiB": "oom", "peak_above_start_GiB": "oom", "needs_GiB": round(forward_bytes() / 2 ** 30, 1)}
+                print(json.dumps({"leg": "forward", "B": B, "prompt": S, "kv_cache": a.kv, **r}), flush=True)
+                return r
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            try:
+                times = []
+                for _ in range(a.repeat + 1):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    model._generate_step(inputs, pad_token_id=0, max_new_tokens=1, eos_token_id=[], **gen)
+                    torch.cuda.synchronize()
+                    times.append(time.perf_counter() - t0)
+                best = min(times[1:])                                        # the first run allocates: not timed
+                r = {"prompt_ms": round(best * 1e3, 2), "peak_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3),
+                     "peak_above_start_GiB": round((torch.cuda.max_memory_allocated() - base) / 2 ** 30, 3)}
+            except torch.cuda.OutOfMemoryError:
+                r = {"prompt_ms": "oom", "peak_GiB": "oom", "peak_above_start_GiB": "oom"}
+            print(json.dumps({"leg": "forward" if C is None else f"chunk{C}", "B": B, "prompt": S, "kv_cache": a.kv, **r}), flush=True)
+            return r
+        legs = [None] + chunks
+        runs = {C: [] for C in legs}
+        for C in legs:                                                       # warm-up: workspaces, merged / transposed weights
+            prompt(C)
+        for _ in range(a.rounds):
+            for C in legs:
+                runs[C].append(prompt(C))
+        summary = {"prefill_ab": f"{a.config} B={B} prompt={S} kv={a.kv}", "rounds": a.rounds, "weights_GiB": None}
+        for C in legs:
+            name = "forward" if C is None else f"chunk{C}"
+            ms = [r["prompt_ms"] for r in runs[C] if r["prompt_ms"] != "oom"]
+            summary[name] = {"prompt_ms": [r["prompt_ms"] for r in runs[C]], "median_ms": sorted(ms)[len(ms) // 2] if ms else "oom",
+                             "spread_ms": round(max(ms) - min(ms), 2) if ms else "oom", "peak_GiB": runs[C][-1]["peak_GiB"],
+                             "peak_above_start_GiB": runs[C][-1]["peak_above_start_GiB"]}
+            if "needs_GiB" in runs[C][-1]:
+                summary[name]["needs_GiB"] = runs[C][-1]["needs_GiB"]
+        if a.kv == "fp8":                                                    # share of the staging-slab dequantisation in the chunked prompt pass
+            for C in chunks:
+                model.set_prefill_chunk(C)
+                drop()
+                model._generate_step(inputs, pad_token_id=0, max_new_tokens=1, eos_token_id=[], **gen)
+                H.kernel_profile_start()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                model._generate_step(inputs, pad_token_id=0, max_new_tokens=1, eos_token_id=[], **gen)
+                torch.cuda.synchronize()
+                wall = (time.perf_counter() - t0) * 1e3
+                prof = H.kernel_profile_stop()
+                dq = prof.get("kv8_dequant", (0, 0.0, 0.0))
+                attn = sum(v[2] for k, v in prof.items() if k.startswith("attn_fwd"))
+                med = summary[f"chunk{C}"]["median_ms"]
+                summary[f"chunk{C}"].update(dequant_calls=dq[0], dequant_ms=round(dq[2], 3), attention_fwd_ms=round(attn, 3), profiled_prompt_ms=round(wall, 2),
+                                            dequant_share_of_prompt=round(dq[2] / med, 4) if med != "oom" else None)
+        drop()
+        summary["weights_GiB"] = round(torch.cuda.memory_allocated() / 2 ** 30, 3)
+        print(json.dumps(summary), flush=True)
+        return
 
     def leg(kind):
         model.set_decode_weights(kind)
@@ -88,7 +185,8 @@ def main():
         prompt_ms = res[0] * 1e3
         tok_ms = (res[1] - res[0]) * 1e3 / (a.new - 1)
         wbytes = welems * (1 if kind == "fp8" else 2)
-        r = {"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "decode_weights": kind, "kv_cache": model.llm.kv_cache_kind, "prompt_ms": round(prompt_ms, 2),
+        r = {"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "decode_weights": kind, "kv_cache": model.llm.kv_cache_kind, "prefill_chunk": model.llm.prefill_chunk,
+             "prompt_ms": round(prompt_ms, 2),
              "ms_per_token_step": round(tok_ms, 3), "tokens_per_s": round(B / tok_ms * 1e3, 1),
              "weight_bytes_per_step": wbytes, "weight_stream_GBps": round(wbytes / tok_ms / 1e6, 1), "hbm_peak_GBps": 8000}
         print(json.dumps(r), flush=True)
