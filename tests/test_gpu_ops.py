@@ -28,6 +28,7 @@ def rel_err(a, b):
 
 @pytest.mark.parametrize("rows,cols,f32in", [(37, 1280, True), (64, 384, False), (5, 128, True), (12, 2048, False), (9, 4096, True), (70, 2560, False)])
 def test_layernorm_fwd_bwd(hip, rows, cols, f32in):
+    """Whole-tensor parity; held per element against float64 at the dispatch edges by tests/test_gpu_rowwise_fp64.py."""
     g = torch.Generator().manual_seed(rows + cols)
     x = torch.randn(rows, cols, generator=g) * 2 + 0.5
     if not f32in:
@@ -60,6 +61,7 @@ def test_layernorm_fwd_bwd(hip, rows, cols, f32in):
 
 @pytest.mark.parametrize("rows,cols", [(33, 4096), (7, 256), (16, 5120)])
 def test_rmsnorm_fwd_bwd(hip, rows, cols):
+    """Whole-tensor parity; held per element against float64 at the dispatch edges by tests/test_gpu_rowwise_fp64.py."""
     g = torch.Generator().manual_seed(cols)
     x = bf(torch.randn(rows, cols, generator=g) * 1.5)
     w = 1 + 0.1 * torch.randn(cols, generator=g)
@@ -133,6 +135,7 @@ def test_mel_to_rows(hip):
 
 @pytest.mark.parametrize("hd,qknorm", [(128, False), (64, False), (128, True), (64, True)])
 def test_rope_fwd_bwd(hip, hd, qknorm):
+    """Whole-tensor parity; held per element against float64 at the dispatch edges by tests/test_gpu_rowwise_fp64.py."""
     g = torch.Generator().manual_seed(hd)
     B, S, hq, hkv = 2, 9, 4, 2
     d = O.tiny_dims(qknorm)
@@ -170,6 +173,7 @@ def test_rope_fwd_bwd(hip, hd, qknorm):
 
 
 def test_swiglu_gelu(hip):
+    """Whole-tensor parity; held per element against float64 at the dispatch edges by tests/test_gpu_rowwise_fp64.py."""
     g = torch.Generator().manual_seed(4)
     rows, I = 19, 512
     gu = bf(torch.randn(rows, 2 * I, generator=g) * 2)
@@ -209,6 +213,7 @@ def test_embed_gather_and_rows(hip):
 
 @pytest.mark.parametrize("V", [512, 1000, 24000, 128256, 151936])
 def test_causal_lm_loss(hip, V):
+    """Whole-tensor parity; held per element against float64 at the dispatch edges by tests/test_gpu_rowwise_fp64.py."""
     g = torch.Generator().manual_seed(V)
     B, S = 2, 7
     logits = bf(torch.randn(B * S, V, generator=g) * 3)
@@ -235,6 +240,7 @@ def test_causal_lm_loss(hip, V):
 
 
 def test_tap_mix(hip):
+    """Whole-tensor parity; held per element against float64 at the dispatch edges by tests/test_gpu_rowwise_fp64.py."""
     g = torch.Generator().manual_seed(6)
     taps, B, K, d = 4, 3, 64, 128
     x = torch.randn(taps, B * K, d, generator=g)
