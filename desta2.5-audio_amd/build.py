@@ -25,7 +25,8 @@ FLAGS += os.environ.get("DESTA_EXTRA_HIPCC_FLAGS", "").split()      # kernel A/B
 # gemm_bf16.hip: accumulators stay in VGPRs for every kernel of the file.  The one-block-per-CU ring kernel would otherwise get
 # AGPR accumulators (512-register budget) and, with two MFMA groups per loop iteration, ~110 v_accvgpr copies per K-tile; the
 # other kernels of the file already compile to the VGPR form (identical code with and without the flag).
-FILE_FLAGS = {"gemm_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
+# embed_ce.hip: the log-sum-exp code two kernels share turns contraction off by pragma, which plain "fast" disregards.
+FILE_FLAGS = {"gemm_bf16.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "embed_ce.hip": ["-ffp-contract=fast-honor-pragmas"]}
 
 
 def _digest(paths):

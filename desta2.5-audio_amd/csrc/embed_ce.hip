@@ -227,34 +227,28 @@ __global__ __launch_bounds__(1024) void ce_row_reg_k(bf16_t* __restrict__ logits
 // (m <= x[lab]) and no entry in FRONT of it reaches x[lab] (`early`; a chunk that lies wholly in front is judged by its maximum).
 constexpr int LPT = 1024;
 
+// From here to lse_logprob the roundings are spelled out and the compiler may not fuse on its own (this file is built with
+// -ffp-contract=fast-honor-pragmas for that): token_logprob_k and topk_logprob_k inline the same source and must write the same
+// bits for the same row, and left free, s * e + s2 * e2 contracts around either product — two inlined copies did differ.
+#pragma clang fp contract(off)
+
 // (m, s) <- (m, s) merged with (m2, s2); -inf maxima (no finite entry yet) carry zero mass and never reach an exponent as inf - inf
 __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
     const float mn = fmaxf(m, m2), ms = mn == -INFINITY ? 0.f : mn;
-    s = s * __expf(m - ms) + s2 * __expf(m2 - ms);
+    const float t2 = s2 * __expf(m2 - ms);
+    s = __builtin_fmaf(s, __expf(m - ms), t2);
     m = mn;
 }
 
-__global__ __launch_bounds__(LPT) void token_logprob_k(const bf16_t* __restrict__ logits, long ld, const long* __restrict__ labels,
-                                                       int V, float* __restrict__ logprob, unsigned char* __restrict__ is_top1) {
-    __shared__ float red_m[LPT / 64], red_s[LPT / 64];
-    __shared__ int red_e[LPT / 64];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    const long tgt = labels[r];
-    if (tgt < 0 || tgt >= V) {                                   // ignored (-100) or out of range: nothing of the row is read
-        if (tid == 0) {
-            logprob[r] = 0.f;
-            if (is_top1) is_top1[r] = 0;
-        }
-        return;
-    }
-    const bf16_t* row = logits + (long)r * ld;
-    const int lab = (int)tgt;
-    const float xl = bf2f(row[lab]);
-    float m = -INFINITY, s = 0.f;
-    int early = 0;
+// One thread's share of a row's (maximum m, sum s of exp(x - m)) pair and of `early` (an entry in front of `lab` reaches xl): the
+// pass that token_logprob_k and topk_logprob_k share, so the two write the same bits for the same row.  EARLY = false drops the
+// top-1 bookkeeping (no label).
+template <bool EARLY>
+__device__ __forceinline__ void lse_thread_pass(const bf16_t* __restrict__ row, int V, int lab, float xl, int tid, float& m, float& s,
+                                                int& early) {
     auto one = [&](int c, bf16_t b) {
         const float x = bf2f(b);
-        early |= (c < lab) & (x >= xl);
+        if (EARLY) early |= (c < lab) & (x >= xl);
         lse_merge(m, s, x, 1.0f);
     };
     auto chunk = [&](int c0, const u16x8& v) {
@@ -262,16 +256,18 @@ __global__ __launch_bounds__(LPT) void token_logprob_k(const bf16_t* __restrict_
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] = bf2f(v[e]);
         const float cm = fmaxf(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])), fmaxf(fmaxf(x[4], x[5]), fmaxf(x[6], x[7])));
-        if (c0 + 8 <= lab) early |= cm >= xl;
-        else if (c0 < lab) {
+        if (EARLY) {
+            if (c0 + 8 <= lab) early |= cm >= xl;
+            else if (c0 < lab) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) early |= (c0 + e < lab) & (x[e] >= xl);
+                for (int e = 0; e < 8; ++e) early |= (c0 + e < lab) & (x[e] >= xl);
+            }
         }
         const float mn = fmaxf(m, cm), ms = mn == -INFINITY ? 0.f : mn;
         float a = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) a += __expf(x[e] - ms);
-        s = s * __expf(m - ms) + a;
+        s = __builtin_fmaf(s, __expf(m - ms), a);
         m = mn;
     };
     const int head = min(V, (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 1));      // elements in front of the first 16-byte boundary
@@ -291,6 +287,9 @@ __global__ __launch_bounds__(LPT) void token_logprob_k(const bf16_t* __restrict_
     }
     for (; g < n8; g += LPT) chunk(head + g * 8, *(const u16x8*)(body + (long)g * 8));
     for (int c = head + n8 * 8 + tid; c < V; c += LPT) one(c, row[c]);
+}
+// The 64 lanes' pairs merged by butterfly; lane 0 of each wave leaves its wave's pair in red_*[wave].
+__device__ __forceinline__ void lse_wave_merge(float& m, float& s, int& early, int tid, float* red_m, float* red_s, int* red_e) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
@@ -298,15 +297,196 @@ __global__ __launch_bounds__(LPT) void token_logprob_k(const bf16_t* __restrict_
         early |= __shfl_xor(early, o, 64);
     }
     if ((tid & 63) == 0) { red_m[tid >> 6] = m; red_s[tid >> 6] = s; red_e[tid >> 6] = early; }
+}
+// Thread 0, after the barrier: the 16 waves' pairs in turn.
+__device__ __forceinline__ void lse_block_merge(float& m, float& s, int& early, const float* red_m, const float* red_s, const int* red_e) {
+    for (int w = 1; w < LPT / 64; ++w) {
+        lse_merge(m, s, red_m[w], red_s[w]);
+        early |= red_e[w];
+    }
+}
+// x[lab] - m is exact in fp32 for bf16 inputs of like magnitude; a -inf entry has probability 0
+__device__ __forceinline__ float lse_logprob(float x, float m, float s) { return x == -INFINITY ? -INFINITY : (x - m) - logf(s); }
+
+#pragma clang fp contract(fast)
+
+__global__ __launch_bounds__(LPT) void token_logprob_k(const bf16_t* __restrict__ logits, long ld, const long* __restrict__ labels,
+                                                       int V, float* __restrict__ logprob, unsigned char* __restrict__ is_top1) {
+    __shared__ float red_m[LPT / 64], red_s[LPT / 64];
+    __shared__ int red_e[LPT / 64];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const long tgt = labels[r];
+    if (tgt < 0 || tgt >= V) {                                   // ignored (-100) or out of range: nothing of the row is read
+        if (tid == 0) {
+            logprob[r] = 0.f;
+            if (is_top1) is_top1[r] = 0;
+        }
+        return;
+    }
+    const bf16_t* row = logits + (long)r * ld;
+    const int lab = (int)tgt;
+    const float xl = bf2f(row[lab]);
+    float m = -INFINITY, s = 0.f;
+    int early = 0;
+    lse_thread_pass<true>(row, V, lab, xl, tid, m, s, early);
+    lse_wave_merge(m, s, early, tid, red_m, red_s, red_e);
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < LPT / 64; ++w) {
-            lse_merge(m, s, red_m[w], red_s[w]);
-            early |= red_e[w];
-        }
-        // x[lab] - m is exact in fp32 for bf16 inputs of like magnitude; a -inf label entry has probability 0
-        logprob[r] = xl == -INFINITY ? -INFINITY : (xl - m) - logf(s);
+        lse_block_merge(m, s, early, red_m, red_s, red_e);
+        logprob[r] = lse_logprob(xl, m, s);
         if (is_top1) is_top1[r] = (xl >= m && !early) ? 1 : 0;
+    }
+}
+
+// Per-token log-probability and the top_n alternatives of a decode step's rows (desta_topk_logprobs): READ ONLY, one 1024-thread
+// block per row.  The (m, s) pair is token_logprob_k's, by the same code.  Selection is exact and by integers only, on the 16-bit
+// monotone key of a bf16 value (-0.0 folded onto +0.0):
+//   1. a floor t0 that at least 32 entries reach: the smallest of the 32 maxima of the block's 32-thread groups (each is a
+//      different entry; a group without entries gives -inf and every entry passes);
+//   2. one sweep appends every entry >= t0 to an LDS list (about a hundred on a model's row).  If more than TK_CAP reach it (ties
+//      in bulk, short rows) the list is rebuilt exactly instead: two 256-bin histograms (high, then low key byte) give the n-th
+//      largest key K and the count above it, a sweep takes every entry above K, and the entries equal to K are taken in index
+//      order (1024-entry tiles, ballot + prefix) until n slots are filled;
+//   3. each listed entry counts the entries that precede it by (key descending, index ascending) — pairs are unique, so the rank
+//      does not depend on the order the atomics filled the list in — and ranks below n are written.
+constexpr int TK_CAP = 1024, TK_MAX = 32;
+
+__device__ __forceinline__ unsigned bf16_key(bf16_t b) {        // value order == unsigned order; +-0 -> 0x8000, -inf -> 0x007f
+    const unsigned u = b == 0x8000 ? 0u : (unsigned)b;
+    return (u & 0x8000) ? (~u & 0xffffu) : (u | 0x8000u);
+}
+__device__ __forceinline__ float key_value(unsigned k) {
+    const unsigned u = (k & 0x8000) ? (k & 0x7fffu) : (~k & 0xffffu);
+    return __uint_as_float(u << 16);
+}
+// f(c, bits) for every entry of the row, whole 16-byte chunks by vector loads (the split of lse_thread_pass)
+template <class F>
+__device__ __forceinline__ void row_sweep(const bf16_t* __restrict__ row, int V, int tid, F f) {
+    const int head = min(V, (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 1));
+    const int n8 = (V - head) >> 3;
+    const bf16_t* body = row + head;
+    if (tid < head) f(tid, row[tid]);
+    int g = tid;
+    for (; g + LPT < n8; g += 2 * LPT) {
+        const u16x8 v0 = *(const u16x8*)(body + (long)g * 8);
+        const u16x8 v1 = *(const u16x8*)(body + (long)(g + LPT) * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f(head + g * 8 + e, v0[e]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f(head + (g + LPT) * 8 + e, v1[e]);
+    }
+    for (; g < n8; g += LPT) {
+        const u16x8 v0 = *(const u16x8*)(body + (long)g * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f(head + g * 8 + e, v0[e]);
+    }
+    for (int c = head + n8 * 8 + tid; c < V; c += LPT) f(c, row[c]);
+}
+// larger == earlier in the output: key descending, then index ascending
+__device__ __forceinline__ unsigned long long tk_pack(unsigned key, int c) { return ((unsigned long long)key << 32) | (0xffffffffu - (unsigned)c); }
+
+__global__ __launch_bounds__(LPT) void topk_logprob_k(const bf16_t* __restrict__ logits, long ld, const long* __restrict__ tokens, int V,
+                                                      int n, float* __restrict__ token_logprob, int* __restrict__ top_ids,
+                                                      float* __restrict__ top_logprobs) {
+    __shared__ float red_m[LPT / 64], red_s[LPT / 64], grp[LPT / 32];
+    __shared__ int red_e[LPT / 64];
+    __shared__ float fin[3];                                     // m, s, t0
+    __shared__ int cnt, sel[3];                                  // list length; high digit / key K, entries above, ties to take
+    __shared__ int hist[256], wcnt[LPT / 64];
+    __shared__ unsigned long long cand[TK_CAP];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const long tgt = tokens ? tokens[r] : 0;
+    if (tgt < 0 || tgt >= V) {                                   // a finished sequence: nothing of the row is read
+        if (tid == 0 && token_logprob) token_logprob[r] = 0.f;
+        if (tid < n) { top_ids[(long)r * n + tid] = -1; top_logprobs[(long)r * n + tid] = 0.f; }
+        return;
+    }
+    const bf16_t* row = logits + (long)r * ld;
+    const int lab = (int)tgt;
+    const float xl = bf2f(row[lab]);
+    float m = -INFINITY, s = 0.f;
+    int early = 0;
+    lse_thread_pass<false>(row, V, lab, xl, tid, m, s, early);
+    float gm = m;                                                // this thread's own maximum, then its 32-thread group's
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) gm = fmaxf(gm, __shfl_xor(gm, o, 64));
+    if ((tid & 31) == 0) grp[tid >> 5] = gm;
+    lse_wave_merge(m, s, early, tid, red_m, red_s, red_e);
+    if (tid == 0) cnt = 0;
+    __syncthreads();
+    if (tid == 0) {
+        lse_block_merge(m, s, early, red_m, red_s, red_e);
+        if (tokens) token_logprob[r] = lse_logprob(xl, m, s);
+        float t0 = grp[0];
+        for (int i = 1; i < LPT / 32; ++i) t0 = fminf(t0, grp[i]);
+        fin[0] = m; fin[1] = s; fin[2] = t0;
+    }
+    if (n == 0) return;
+    __syncthreads();
+    const float t0 = fin[2];
+    // wave-aggregated append: one LDS atomic per wave and call, whatever the number of passing lanes
+    auto append = [&](bool take, unsigned key, int c) {
+        const unsigned long long b = __ballot(take);
+        if (b) {
+            const int lane = tid & 63, leader = __ffsll((long long)b) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&cnt, __popcll(b));
+            base = __shfl(base, leader, 64);
+            const int slot = base + __popcll(b & ((1ull << lane) - 1));
+            if (take && slot < TK_CAP) cand[slot] = tk_pack(key, c);
+        }
+    };
+    row_sweep(row, V, tid, [&](int c, bf16_t b) { append(bf2f(b) >= t0, bf16_key(b), c); });
+    __syncthreads();
+    int total = cnt;
+    if (total > TK_CAP) {                                        // block-uniform: the exact rebuild
+        unsigned hi = 0;
+        int above = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            if (tid < 256) hist[tid] = 0;
+            __syncthreads();
+            if (pass == 0) row_sweep(row, V, tid, [&](int, bf16_t b) { atomicAdd(&hist[bf16_key(b) >> 8], 1); });
+            else row_sweep(row, V, tid, [&](int, bf16_t b) { const unsigned k = bf16_key(b); if ((k >> 8) == hi) atomicAdd(&hist[k & 255], 1); });
+            __syncthreads();
+            if (tid == 0) {                                      // the digit at which the count from the top reaches n
+                int d = 255, acc = above;
+                while (d > 0 && acc + hist[d] < n) acc += hist[d--];
+                sel[0] = d; sel[1] = acc; sel[2] = n - acc;
+                if (pass == 1) cnt = 0;
+            }
+            __syncthreads();
+            hi = (hi << 8) | (unsigned)sel[0];
+            above = sel[1];
+        }
+        const unsigned K = hi;
+        const int need = sel[2];
+        row_sweep(row, V, tid, [&](int c, bf16_t b) { const unsigned k = bf16_key(b); append(k > K, k, c); });      // `above` < n entries
+        int got = 0;
+        for (int c0 = 0; c0 < V && got < need; c0 += LPT) {      // ties with K, lowest indices first
+            const int c = c0 + tid;
+            const bool tie = c < V && bf16_key(row[c]) == K;
+            const unsigned long long b = __ballot(tie);
+            if ((tid & 63) == 0) wcnt[tid >> 6] = __popcll(b);
+            __syncthreads();
+            int before = 0, all = 0;
+#pragma unroll
+            for (int w = 0; w < LPT / 64; ++w) { const int k = wcnt[w]; before += w < (tid >> 6) ? k : 0; all += k; }
+            const int rank = got + before + __popcll(b & ((1ull << (tid & 63)) - 1));
+            if (tie && rank < need) cand[above + rank] = tk_pack(K, c);
+            got += all;
+            __syncthreads();
+        }
+        total = n;
+    }
+    __syncthreads();
+    if (tid < total) {
+        const unsigned long long mine = cand[tid];
+        int rank = 0;
+        for (int j = 0; j < total; ++j) rank += cand[j] > mine;
+        if (rank < n) {
+            top_ids[(long)r * n + rank] = (int)(0xffffffffu - (unsigned)mine);
+            top_logprobs[(long)r * n + rank] = lse_logprob(key_value((unsigned)(mine >> 32)), fin[0], fin[1]);
+        }
     }
 }
 
@@ -484,6 +664,20 @@ extern "C" int desta_token_logprobs(const void* logits_bf16, int64_t ld, const i
     hipLaunchKernelGGL(token_logprob_k, dim3(rows), dim3(LPT), 0, (hipStream_t)stream, (const bf16_t*)logits_bf16, (long)ld,
                        (const long*)labels, vocab, logprob, is_top1);
     DESTA_CHECK_LAUNCH("token_logprobs");
+    return DESTA_OK;
+}
+
+extern "C" int desta_topk_logprobs(const void* logits_bf16, int64_t ld, const int64_t* tokens, int rows, int vocab, int top_n,
+                                   float* token_logprob, int32_t* top_ids, float* top_logprobs, void* stream) {
+    DESTA_CHECK_ARG(logits_bf16, "topk_logprobs: null logits");
+    DESTA_CHECK_ARG(rows > 0 && vocab > 0 && vocab <= 262144 && ld >= vocab, "topk_logprobs: bad shape");
+    DESTA_CHECK_ARG(top_n >= 0 && top_n <= TK_MAX && top_n <= vocab, "topk_logprobs: top_n outside 0..32 (or above vocab)");
+    DESTA_CHECK_ARG((tokens != nullptr) == (token_logprob != nullptr), "topk_logprobs: tokens and token_logprob go together");
+    DESTA_CHECK_ARG(top_n == 0 || (top_ids && top_logprobs), "topk_logprobs: null top_ids / top_logprobs with top_n > 0");
+    DESTA_CHECK_ARG(tokens || top_n > 0, "topk_logprobs: nothing to compute");
+    hipLaunchKernelGGL(topk_logprob_k, dim3(rows), dim3(LPT), 0, (hipStream_t)stream, (const bf16_t*)logits_bf16, (long)ld,
+                       (const long*)tokens, vocab, top_n, token_logprob, top_ids, top_logprobs);
+    DESTA_CHECK_LAUNCH("topk_logprobs");
     return DESTA_OK;
 }
 

@@ -452,6 +452,9 @@ lib.desta_ce_workspace_floats.restype = c_size_t
 lib.desta_ce_workspace_floats.argtypes = [i32, i32]
 _ce = _sig("desta_causal_lm_loss", vp, i64, vp, i32, i32, i32, vp, vp, i32, vp)
 _token_logprobs = _sig("desta_token_logprobs", vp, i64, vp, i32, i32, vp, vp, vp)
+_topk_logprobs = _sig("desta_topk_logprobs", vp, i64, vp, i32, i32, i32, vp, vp, vp, vp)
+TOPK_LOGPROBS_MAX = 32             # largest top_n of desta_topk_logprobs
+TOPK_LOGPROBS_CALLS = 0            # launches issued by this process (tests assert one per decode step, none without logprobs=)
 _mix_fwd = _sig("desta_tap_mix_fwd", vp, vp, i32, i32, i32, i32, vp, vp)
 _mix_bwd = _sig("desta_tap_mix_bwd", vp, vp, vp, i32, i32, i32, i32, vp, vp, vp)
 
@@ -477,6 +480,18 @@ def token_logprobs(logits, ld, labels, rows, vocab, out, is_top1=None):
     labels[r] (int64; negative or >= vocab: ignored, 0).  is_top1 (uint8 [rows], optional): the label is the row's argmax
     (include/desta_hip.h desta_token_logprobs)."""
     check(_token_logprobs(p(logits), ld, p(labels), rows, vocab, p(out), p(is_top1), stream()), "desta_token_logprobs")
+
+
+@_profiled("topk_logprobs", lambda logits, ld, tokens, rows, vocab, top_n, token_logprob=None, top_ids=None, top_logprobs=None: 4 * rows * vocab)
+def topk_logprobs(logits, ld, tokens, rows, vocab, top_n, token_logprob=None, top_ids=None, top_logprobs=None):
+    """Of bf16 rows with stride ld, which stay untouched: token_logprob[r] = log_softmax(logits[r, :vocab])[tokens[r]] (fp32, the bits
+    of `token_logprobs`), top_ids[r, :] (int32) the top_n largest entries in descending order, lower index first among equals, and
+    top_logprobs[r, :] their log-probabilities.  tokens int64, or None with token_logprob None; a negative or >= vocab token marks
+    a finished row: 0 / -1 / 0, not read (include/desta_hip.h desta_topk_logprobs)."""
+    global TOPK_LOGPROBS_CALLS
+    check(_topk_logprobs(p(logits), ld, p(tokens), rows, vocab, top_n, p(token_logprob), p(top_ids), p(top_logprobs), stream()),
+          "desta_topk_logprobs")
+    TOPK_LOGPROBS_CALLS += 1
 
 
 def tap_mix_fwd(x, lw, taps, batch, prompt, d, out):

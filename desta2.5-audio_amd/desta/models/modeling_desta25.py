@@ -408,6 +408,14 @@ def check_sampling_args(top_k=None, min_p=None, repetition_penalty=None) -> None
         raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
 
 
+def check_logprobs_arg(n) -> None:
+    """`logprobs=` of generate(): None (off) or the number of top alternatives per token, an int in 0..H.TOPK_LOGPROBS_MAX."""
+    if n is None:
+        return
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= H.TOPK_LOGPROBS_MAX:
+        raise ValueError(f"`logprobs` has to be None or an integer in [0, {H.TOPK_LOGPROBS_MAX}], but is {n!r}")
+
+
 def check_decode_rows(B: int) -> None:
     """A KV-cached decode step streams the weights once for all its rows; its projections take at most H.DECODE_MAX_ROWS of them."""
     if B > H.DECODE_MAX_ROWS:
@@ -436,6 +444,19 @@ class GenerationOutput:
     audios: list
     generated_ids: list
     text: list
+    # generate(..., logprobs=n) only, under the model's own distribution (log_softmax of the raw logits); None otherwise
+    token_logprobs: Optional[list] = None      # B lists of floats: the row's tokens up to and including its first EOS
+    top_logprobs: Optional[list] = None        # per row and token: n tuples (token_id, token string or None, logprob), most likely first
+    sum_logprob: Optional[list] = None         # B floats: sum of the row's token_logprobs
+
+
+@dataclass
+class TokenLogprobs:
+    """`generate_greedy(logprobs=n)`: the log-probability of every emitted token and the n most likely tokens of its step, under
+    log_softmax of the raw logits.  Columns behind a row's EOS hold 0 / -1 / 0."""
+    token_logprobs: torch.Tensor       # [B, n_new] fp32
+    top_ids: torch.Tensor              # [B, n_new, n] int32, descending probability, lower id first among equals
+    top_logprobs: torch.Tensor         # [B, n_new, n] fp32
 
 
 @dataclass
@@ -2004,7 +2025,8 @@ class CausalLMHIP:
                         eos_token_ids=None, forced_tokens: Optional[torch.Tensor] = None, collect_logits: bool = False,
                         do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0, seed: int = 0, layer_hook=None,
                         after_prompt=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
-                        repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None, chunk_hook=None):
+                        repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None, chunk_hook=None,
+                        logprobs: Optional[int] = None):
         """Prompt pass + KV-cached decode (greedy, or temperature / top-p sampling with the library's counter RNG).  Returns new token ids [B, n_new] (int64; finished sequences are
         filled with pad_token_id, generation stops early once every sequence has produced an EOS), and, with
         collect_logits, the per-step logits [n_new, B, V] (bf16).  `forced_tokens` [B, T] teacher-forces the
@@ -2013,7 +2035,12 @@ class CausalLMHIP:
         front of chunk i) and of every decode step ([B, h]); `after_prompt()` between the two.
         top_k / min_p (sampling) and repetition_penalty (both modes) switch to HF's whole processor chain in one kernel
         (`desta_sample_bf16`); None = off.  The penalty's history is what HF's `input_ids` hold: `prompt_ids` [B, S] (text-only
-        chats, left padding included) followed by the tokens emitted so far, pad_token_id for finished rows."""
+        chats, left padding included) followed by the tokens emitted so far, pad_token_id for finished rows.
+        logprobs = n (0..32): one more launch per step (`desta_topk_logprobs`) scores the step's token once it is fixed (forced /
+        finished substitutions applied) and ranks the row's n most likely tokens; a `TokenLogprobs` is appended to the result.  The
+        distribution is the MODEL'S OWN, log_softmax of the raw logits in front of the repetition penalty, the temperature and the
+        top-k / top-p / min-p filters: HF's log_softmax(output_logits), not its processed output_scores.  The EOS token itself is
+        scored; the padding behind it is not (0 / -1 / 0).  None: no launch, no allocation."""
         assert max_new_tokens >= 1
         check_decode_rows(B)
         use_pen = repetition_penalty is not None and float(repetition_penalty) != 1.0
@@ -2039,6 +2066,13 @@ class CausalLMHIP:
                 hist[:, :P] = prompt_ids.to(dev, torch.int64)
             out = hist[:, P:]
         steps_logits = []
+        if logprobs is not None:
+            lp_tok = torch.zeros(B, max_new_tokens, dtype=F32, device=dev)
+            lp_ids = torch.full((B, max_new_tokens, logprobs), -1, dtype=torch.int32, device=dev)
+            lp_top = torch.zeros(B, max_new_tokens, logprobs, dtype=F32, device=dev)
+            st_tok = torch.empty(B, dtype=F32, device=dev)                   # one step's rows, contiguous for the kernel
+            st_ids = torch.empty(B, logprobs, dtype=torch.int32, device=dev)
+            st_top = torch.empty(B, logprobs, dtype=F32, device=dev)
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
         n_new = 0
@@ -2056,6 +2090,11 @@ class CausalLMHIP:
             nxt = self.g_next if forced_tokens is None else forced_tokens[:, t].to(dev, torch.int64)
             nxt = torch.where(finished, torch.full_like(nxt, int(pad_token_id)), nxt)
             out[:, t] = nxt
+            if logprobs is not None:                                         # rows finished before this step carry -1: not read, 0 / -1 / 0
+                H.topk_logprobs(logits, self.Vp, torch.where(finished, torch.full_like(nxt, -1), nxt), B, self.V, logprobs, st_tok, st_ids, st_top)
+                lp_tok[:, t] = st_tok
+                lp_ids[:, t] = st_ids
+                lp_top[:, t] = st_top
             n_new = t + 1
             if eos is not None:
                 finished |= (nxt.unsqueeze(1) == eos.unsqueeze(0)).any(dim=1)
@@ -2072,7 +2111,10 @@ class CausalLMHIP:
             last = int(torch.where(has, done_at + 1, torch.full_like(done_at, n_new)).max())
             n_new = min(n_new, last)
         out = out[:, :n_new]
-        return (out, torch.stack(steps_logits[:n_new])) if collect_logits else out
+        res = (out, torch.stack(steps_logits[:n_new])) if collect_logits else (out,)
+        if logprobs is not None:
+            res += (TokenLogprobs(token_logprobs=lp_tok[:, :n_new], top_ids=lp_ids[:, :n_new], top_logprobs=lp_top[:, :n_new]),)
+        return res if len(res) > 1 else out
 
     def loss_and_grad(self, labels: torch.Tensor, write_grad: bool) -> torch.Tensor:
         """ForCausalLMLoss on the logits of the last forward; with write_grad the logits buffer becomes dlogits."""
@@ -2552,7 +2594,7 @@ class DeSTA25AudioModel:
     @torch.no_grad()
     def _generate_step(self, inputs, pad_token_id, temperature=0.7, top_p=0.9, max_new_tokens=512, do_sample=True,
                        eos_token_id=None, forced_tokens=None, collect_logits=False, seed=0, top_k=None, min_p=None,
-                       repetition_penalty=None, prompt_in_history=False):
+                       repetition_penalty=None, prompt_in_history=False, logprobs=None):
         """Reference `_generate_step` (modeling_desta25.py:1358-1431): audio features spliced into the prompt
         embeddings, then `llm_model.generate(inputs_embeds=…)` — here the KV-cached decoder on the HIP path.
         Returns ONLY the new tokens, as HF does for inputs_embeds prompts.  do_sample=False: greedy (temperature / top_p
@@ -2561,8 +2603,12 @@ class DeSTA25AudioModel:
         top_k, min_p (sampling only) and repetition_penalty (both modes) add HF's TopK / MinP warpers and its
         RepetitionPenaltyLogitsProcessor; None = off.  HF's history for the penalty is `input_ids`: empty for an
         inputs_embeds prompt (only the generated tokens count, TF:generation/utils.py:1176-1181), the prompt ids for a text
-        prompt passed as input_ids (`prompt_in_history=True`, the text-only leg of `generate`)."""
+        prompt passed as input_ids (`prompt_in_history=True`, the text-only leg of `generate`).
+        logprobs = n: a `TokenLogprobs` becomes the last element of the result, (ids, lp) or (ids, logits, lp): every emitted
+        token's log-probability and the n most likely tokens of its step under the model's own distribution, log_softmax of the
+        raw logits (HF's output_logits, not the processed output_scores; see `CausalLMHIP.generate_greedy`)."""
         check_sampling_args(top_k, min_p, repetition_penalty)
+        check_logprobs_arg(logprobs)
         cfg, dev = self.config, self.device
         input_ids = inputs["context_input_ids"].to(dev)                      # only the context (prompt) part of the batch
         attention_mask = inputs["context_attention_mask"].to(dev)
@@ -2614,7 +2660,7 @@ class DeSTA25AudioModel:
                                                 temperature=1.0 if temperature is None else float(temperature),
                                                 top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after,
                                                 top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty,
-                                                prompt_ids=input_ids if prompt_in_history else None, chunk_hook=chunk)
+                                                prompt_ids=input_ids if prompt_in_history else None, chunk_hook=chunk, logprobs=logprobs)
         finally:
             self.training = was_training
 
@@ -2669,29 +2715,57 @@ class DeSTA25AudioModel:
         if asr is not None or not hasattr(self, "asr"):
             self.asr = asr if asr is not None else (self._asr_whisper if getattr(self, "asr_decoder", None) is not None else None)
 
+    check_logprobs_arg = staticmethod(check_logprobs_arg)
+
+    def _logprob_fields(self, tok, ids, lp: TokenLogprobs, eos_ids) -> dict:
+        """`GenerationOutput`'s log-prob fields from a `TokenLogprobs`: every row cut behind its first EOS (one host copy)."""
+        tl, ti, tp = lp.token_logprobs.tolist(), lp.top_ids.tolist(), lp.top_logprobs.tolist()
+        to_str = getattr(tok, "convert_ids_to_tokens", None)
+        token_logprobs, top = [], []
+        for b, row in enumerate(ids.tolist() if torch.is_tensor(ids) else ids):
+            n = next((i + 1 for i, t in enumerate(row) if t in eos_ids), len(row))
+            token_logprobs.append(tl[b][:n])
+            top.append([[(i, to_str(i) if to_str is not None else None, v) for i, v in zip(ti[b][t], tp[b][t])] for t in range(n)])
+        return dict(token_logprobs=token_logprobs, top_logprobs=top, sum_logprob=[float(sum(r)) for r in token_logprobs])
+
     def generate(self, messages, temperature=0.7, top_p=0.9, do_sample=True, max_new_tokens=512, seed=0, top_k=None, min_p=None,
-                 repetition_penalty=None):
+                 repetition_penalty=None, logprobs=None):
         """The reference's chat-level `generate` (modeling_desta25.py:1491-1721): messages -> audio decode -> log-mel -> placeholder
         expansion of every `<|AUDIO|>` -> left-padded tokenisation, pad-shifted start positions, transcription ids ->
         `_generate_step` -> `GenerationOutput(text, audios, generated_ids)`.  Same messages schema, same errors; the front-end
         models (tokenizer / VAD / ASR) are injected through `_setup_generation`.  top_k / min_p / repetition_penalty: HF's
         processors of the same names, None = off (see `_generate_step`).  To sample exactly as the reference's
         `llm_model.generate` does, with the checkpoint's generation_config.json and HF's defaults (top_k = 50) filled in:
-        `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))`."""
+        `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))`.
+        logprobs = n (0..32): the output also carries `token_logprobs`, `top_logprobs` (n alternatives per token) and `sum_logprob`,
+        each row cut behind its first EOS — the model's own distribution, log_softmax of the raw logits in front of the penalty,
+        the temperature and the filters (HF's output_logits, not output_scores)."""
         check_sampling_args(top_k, min_p, repetition_penalty)
+        check_logprobs_arg(logprobs)
         extra = dict(top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty)
+        if logprobs is not None:
+            extra["logprobs"] = logprobs
         tok, inputs, audios, texts = self._chat_inputs(messages)
         if not audios:
             # no audio: plain LLM generation on the chat template; stops on eos or <|eot_id|>
+            eos = [tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")]
             ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
-                                      do_sample=do_sample, eos_token_id=[tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")], seed=seed,
-                                      prompt_in_history=True, **extra)
+                                      do_sample=do_sample, eos_token_id=eos, seed=seed, prompt_in_history=True, **extra)
+            lp = {}
+            if logprobs is not None:
+                ids, tlp = ids
+                lp = self._logprob_fields(tok, ids, tlp, eos)
             rows = [r.tolist() for r in ids]
-            return GenerationOutput(text=tok.batch_decode(rows, skip_special_tokens=True), audios=[], generated_ids=rows)
+            return GenerationOutput(text=tok.batch_decode(rows, skip_special_tokens=True), audios=[], generated_ids=rows, **lp)
         self._last_generate_inputs = inputs
         ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,
                                   do_sample=do_sample, seed=seed, **extra)
-        return GenerationOutput(text=tok.batch_decode(ids, skip_special_tokens=True), audios=list(zip(audios, texts)), generated_ids=ids.tolist())
+        lp = {}
+        if logprobs is not None:
+            ids, tlp = ids
+            eos = self.config.llm_config.eos_token_id
+            lp = self._logprob_fields(tok, ids, tlp, [eos] if isinstance(eos, int) else list(eos or []))
+        return GenerationOutput(text=tok.batch_decode(ids, skip_special_tokens=True), audios=list(zip(audios, texts)), generated_ids=ids.tolist(), **lp)
 
     def _chat_inputs(self, messages):
         """The front half of the reference's chat-level `generate` (modeling_desta25.py:1491-1700), shared by `generate` and

@@ -606,8 +606,11 @@ class DeSTA25Trainer:
         return report
 
     def _predict_step(self, batch: Dict[str, Any], generation_kwargs: Optional[Dict[str, Any]] = None) -> torch.Tensor:
-        """desta_trainer.py:160-189: generate from the context part of the batch; decode when a tokenizer is attached."""
-        gk = dict(temperature=0.7, top_p=0.9, max_new_tokens=128, do_sample=False, top_k=None, min_p=None, repetition_penalty=None)
+        """desta_trainer.py:160-189: generate from the context part of the batch; decode when a tokenizer is attached.
+        generation_kwargs `logprobs` = n: every prediction row also carries `token_logprobs` (its tokens up to and including the
+        first EOS, under the model's own distribution) and `avg_logprob`, their mean."""
+        gk = dict(temperature=0.7, top_p=0.9, max_new_tokens=128, do_sample=False, top_k=None, min_p=None, repetition_penalty=None,
+                  logprobs=None)
         cfg_gk = getattr(getattr(self.cfg, "model", None), "generation_kwargs", None) if self.cfg is not None else None
         for src in (cfg_gk, generation_kwargs):
             if src:
@@ -618,8 +621,20 @@ class DeSTA25Trainer:
         ids = self.model._generate_step(batch, pad_token_id=pad_id, temperature=gk["temperature"], top_p=gk["top_p"],
                                         max_new_tokens=gk["max_new_tokens"], do_sample=gk["do_sample"],
                                         seed=self.global_step, top_k=gk["top_k"], min_p=gk["min_p"],
-                                        repetition_penalty=gk["repetition_penalty"])
+                                        repetition_penalty=gk["repetition_penalty"],
+                                        **({} if gk["logprobs"] is None else {"logprobs": gk["logprobs"]}))
+        extras = None
+        if gk["logprobs"] is not None:
+            ids, lp = ids
+            eos = getattr(getattr(getattr(self.model, "config", None), "llm_config", None), "eos_token_id", eos_id)     # what `_generate_step` stopped on
+            eos = [eos] if isinstance(eos, int) else list(eos or [])
+            extras = []
+            for row, vals in zip(ids.tolist(), lp.token_logprobs.tolist()):
+                n = next((i + 1 for i, t in enumerate(row) if t in eos), len(row))
+                extras.append({"avg_logprob": sum(vals[:n]) / max(n, 1), "token_logprobs": vals[:n]})
         metas = batch.get("metadata") or [{} for _ in range(ids.shape[0])]
+        if extras is not None:
+            metas = [{**m, **e} for m, e in zip(metas, extras)]
         if tok is not None:
             ctx = batch["context_input_ids"].clone()
             ctx[ctx == -100] = pad_id

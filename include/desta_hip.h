@@ -343,6 +343,24 @@ int desta_causal_lm_loss(void* logits, int64_t ld, const int64_t* labels, int ba
 int desta_token_logprobs(const void* logits_bf16, int64_t ld, const int64_t* labels, int rows, int vocab,
                          float* logprob, uint8_t* is_top1 /* may be NULL */, void* stream);
 
+/* Log-probability of each decode step's chosen token and the top_n alternatives of its row: what `llm_model.generate`
+ * (modeling_desta25.py:1419-1427) yields with output_logits=True followed by log_softmax — the raw distribution, the one
+ * compute_transition_scores(normalize_logits=True) reports for greedy search (TF:generation/utils.py: `raw_logits += (next_token_logits,)`
+ * and compute_transition_scores) — not the processed output_scores.  Additive to ABI 8.
+ * logits bf16 [rows, ld] (ld >= vocab, any alignment), READ ONLY; vocab <= 262144; 0 <= top_n <= 32 (and <= vocab).
+ *   logprob(c) = x[r, c] - logsumexp(x[r, :vocab]) in fp32, maximum subtracted first; -inf entries carry no mass.
+ *   token_logprob[r]  for 0 <= tokens[r] < vocab: bit-identical to desta_token_logprobs on the same row and label (shared code).
+ *   top_ids[r, :]     the top_n largest entries, descending; among equal values (-0.0 == +0.0) the lower index first; a -inf
+ *                     entry appears only when fewer than top_n entries are finite, with logprob -inf.
+ *   top_logprobs[r,j] logprob(top_ids[r, j]).
+ *   tokens[r] < 0 or >= vocab: the row is ignored (a finished sequence) and not read: token_logprob 0, top_ids -1, top_logprobs 0.
+ * tokens and token_logprob are both NULL or both set; without tokens every row is ranked.  With top_n == 0 the top pointers may
+ * be NULL.  NaN logits and rows without a finite entry are out of contract.  One 1024-thread block per row; integer selection
+ * and a fixed reduction order: bitwise reproducible, independent of rows. */
+int desta_topk_logprobs(const void* logits_bf16, int64_t ld, const int64_t* tokens /* may be NULL */, int rows, int vocab,
+                        int top_n, float* token_logprob /* [rows], NULL iff tokens NULL */,
+                        int32_t* top_ids /* [rows, top_n] */, float* top_logprobs /* [rows, top_n] */, void* stream);
+
 /* Connector tap mix (modeling_desta25.py:600-604): x fp32 [taps][batch*prompt][d], layer_weights
  * fp32 [prompt][taps]; out[b,k,:] = sum_j softmax(layer_weights[k,:])_j x[j,b,k,:]; and its backward. */
 int desta_tap_mix_fwd(const float* x, const float* layer_weights, int taps, int batch, int prompt, int d,
