@@ -87,8 +87,8 @@ typedef struct desta_gemm_desc {
                                        /*   saved blocked gate|up, C[M,2N] (bf16, ldc = row length) = d(gate|up), blocked.    */
                                        /*   Replaces TF:models/llama/modeling_llama.py:163-176 (LlamaMLP act_fn(gate) * up)   */
                                        /*   and its autograd; same rounding points as desta_swiglu_fwd / _bwd.                */
-    float dropout_p;                   /* > 0: inverted dropout of act(acc+bias) BEFORE the residual add, mask */
-    uint64_t dropout_seed;             /*   = desta_dropout_mask(seed, m*N + n) (BertSelfOutput/BertOutput, p=0.1) */
+    float dropout_p;                   /* > 0: inverted dropout of act(acc+bias) BEFORE the residual add, mask = desta_dropout_mask(seed, */
+    uint64_t dropout_seed;             /*   (z*M + m)*N + n), z = batch item (BertSelfOutput/BertOutput, p=0.1) */
     void* workspace;                   /* optional fp32 scratch for the split-K tail (NULL = never split);   */
     size_t workspace_bytes;            /* 64 MiB + 4 KiB covers every shape (<= 256 slabs of 256x256 fp32);   */
                                        /* its LAST 4 KiB hold the arrival tickets of the in-kernel K-slice    */

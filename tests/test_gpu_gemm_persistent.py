@@ -1,7 +1,8 @@
 """The persistent tile-queue form of the 256x256 GEMM (`gemm_bf16_nt_256p_kernel`) against the one-tile-per-block kernel of the
 same call: every epilogue instance, split-K tails, the self-resetting queue counters, and a run beside a concurrent load.  No
 tolerances: each item is computed by one block in the same K order with the same epilogue arithmetic, so every output is
-bit-identical (`torch.equal`).  Option 0 of desta_gemm_set_option: 0 = never persistent, 2 = persistent for every multi-round grid."""
+bit-identical (`torch.equal`).  Option 0 of desta_gemm_set_option: 0 = never persistent, 2 = persistent for every multi-round grid.
+Both kernels run the same epilogue code: what that code computes is checked against float64 in tests/test_gpu_gemm_fp64.py."""
 import pytest
 import torch
 

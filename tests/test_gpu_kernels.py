@@ -1,5 +1,7 @@
 """GPU parity tests of the individual HIP kernels against the CPU oracle / plain torch fp32.
-All calls go through the C ABI (desta._hip ctypes binding)."""
+All calls go through the C ABI (desta._hip ctypes binding).
+The GEMM tests here compare paths with each other bit for bit and with fp32 torch by whole-tensor limits; every path and epilogue
+is held per element to a float64 reference of the operation in tests/test_gpu_gemm_fp64.py (reference: tests/gemm_reference.py)."""
 import math
 
 import pytest
