@@ -1625,8 +1625,65 @@ __global__ __launch_bounds__(256) void attn_dq_sum_k(AttnArgs p, const float* __
 // A row with one chunk is finished here (O, lse).  Otherwise each item writes (max, sum, unnormalised O) in fp32 and
 // attn_decode_combine_k merges a row's chunks in ascending order: no atomics, no tickets, a second launch.
 // Empty chunk (all keys masked): max = -inf, sum = 0, O = 0; the combine skips it.
-template <int GP>                                          // G rounded up to 1, 2, 4, 8
-__global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
+//
+// FP8 (e4m3) KV cache: the same body on a cache of OCP e4m3 bytes + one power-of-two fp32 scale per (row, slot, K-or-V head) (the
+// format of desta_rope_kv_append_e4m3).  Work items, chunk boundaries, lane slots, MFMA calls and summation order are shared, so
+// O, lse and every workspace partial equal the bf16 kernel's on the dequantised cache bf16(q * s) bit for bit (while score * s_k
+// and p * s_v stay normal fp32 values: a power of two commutes with a rounding only where nothing underflows).  KV8 differs in:
+//   1. fragments: a lane's K fragment is 8 contiguous bytes at the element offsets of the bf16 kernel, its V piece the 8 bytes
+//      of its 8 columns (DecodeKV);
+//   2. the K and V scales of the keys of this lane's st[t][r] are loaded, rows clamped to [kv_start, seq_k) like the data rows;
+//   3. K bytes become the bf16 MFMA operand exactly (3 mantissa bits) (k_operand);
+//   4. the fp32 score is multiplied by the key's K scale in front of scale_log2;
+//   5. the key's V scale is folded into the probability that goes to s_p (pv * s_v, exact), so the fma rounds the product the
+//      bf16 kernel rounds; the row sum keeps pv;
+//   6. V bytes become fp32 by the packed conversion instead of a shift (v_unpack).
+// and, arithmetic aside, in where decode_load_q is called (see there): a scheduling matter, measured.
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+__device__ __forceinline__ bf16x8 e4m3x8_to_bf16(const uint2& q) {
+    union { unsigned u[4]; bf16x8 v; } o;
+    const unsigned w[2] = {q.x, q.y};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+        o.u[2 * i] = __builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u);
+        o.u[2 * i + 1] = __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u);
+    }
+    return o.v;
+}
+template <bool KV8> struct DecodeKV { typedef bf16_t elem; typedef bf16x8 kfrag; typedef uint4 vfrag; };
+template <> struct DecodeKV<true> { typedef uint8_t elem; typedef uint2 kfrag; typedef uint2 vfrag; };
+__device__ __forceinline__ bf16x8 k_operand(const bf16x8& k) { return k; }
+__device__ __forceinline__ bf16x8 k_operand(const uint2& k) { return e4m3x8_to_bf16(k); }
+__device__ __forceinline__ void v_unpack(const uint4& v, float (&f)[8]) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2) { f[2 * j2] = __builtin_bit_cast(float, w[j2] << 16); f[2 * j2 + 1] = __builtin_bit_cast(float, w[j2] & 0xffff0000u); }
+}
+__device__ __forceinline__ void v_unpack(const uint2& v, float (&f)[8]) {
+    const f32x2 vv[4] = {__builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, false), __builtin_amdgcn_cvt_pk_f32_fp8((int)v.x, true),
+                         __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, false), __builtin_amdgcn_cvt_pk_f32_fp8((int)v.y, true)};
+#pragma unroll
+    for (int j2 = 0; j2 < 4; ++j2) { f[2 * j2] = vv[j2][0]; f[2 * j2 + 1] = vv[j2][1]; }
+}
+
+// the B operand: this lane's 4 x 8 elements of its query row, zero for the columns past the group
+__device__ __forceinline__ void decode_load_q(const AttnArgs& p, int b, int hk, int G, int c16, int q4, bf16x8 (&qf)[4]) {
+    const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)(hk * G + min(c16, G - 1)) * 128 + 8 * q4;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        qf[ks] = *(const bf16x8*)(qptr + 32 * ks);
+        if (c16 >= G)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qf[ks][j] = (__bf16)0.f;
+    }
+}
+template <int GP, bool KV8>                                // G rounded up to 1, 2, 4, 8; KV8: k_scale, v_scale, sc_bs, sc_rs are read
+__device__ __forceinline__ void attn_decode_body(const AttnArgs& p, const float* __restrict__ k_scale, const float* __restrict__ v_scale, long sc_bs,
+                                                 long sc_rs, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
+    typedef typename DecodeKV<KV8>::elem E;
+    typedef typename DecodeKV<KV8>::kfrag KF;
+    typedef typename DecodeKV<KV8>::vfrag VF;
     constexpr int CH = DESTA_ATTN_DECODE_CHUNK, KW = CH / 4, NT16 = KW / 16, NV = KW / 4;
     __shared__ __attribute__((aligned(16))) float s_p[4][KW][8];
     __shared__ __attribute__((aligned(16))) float s_red[4][GP][128];
@@ -1641,43 +1698,53 @@ __global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restri
     const bool live = k0 < p.Sk && k0 + KW > kv_lo;        // wave-uniform: some key of this wave is visible
     const int row_lo = min(kv_lo, p.Sk - 1), row_hi = p.Sk - 1;
 
-    bf16x8 kf[NT16][4];
-    uint4 vf[NV];
+    KF kf[NT16][4];
+    VF vf[NV];
+    float ksc[NT16][4], vsc[NT16][4];                      // KV8: scales of keys k0 + 16 t + 4 q4 + r, the keys of this lane's st[t][r]
     bf16x8 qf[4];
+    // The group's query rows.  WHERE the four loads are issued is a scheduling matter only, and the one place where the twins
+    // want different things from hipcc (measured, B = 64 x 4 096 keys): behind the byte loads of KV8 it issues them one by one,
+    // each after a full drain of the loads in flight (153.9 us against 136.2); in front of the bf16 loads it keeps fewer K / V
+    // loads in flight (208 us against 199).
+    if constexpr (KV8) decode_load_q(p, b, hk, G, c16, q4, qf);
     if (live) {
-        const bf16_t* kbase = p.K + (long)b * p.k_bs + (long)hk * 128 + 8 * q4;
-        const bf16_t* vbase = p.V + (long)b * p.v_bs + (long)hk * 128 + 8 * c16;
+        const E* kbase = (const E*)p.K + (long)b * p.k_bs + (long)hk * 128 + 8 * q4;
+        const E* vbase = (const E*)p.V + (long)b * p.v_bs + (long)hk * 128 + 8 * c16;
 #pragma unroll
         for (int t = 0; t < NT16; ++t) {
             const int row = min(max(k0 + 16 * t + c16, row_lo), row_hi);
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) kf[t][ks] = *(const bf16x8*)(kbase + (long)row * p.k_rs + 32 * ks);
+            for (int ks = 0; ks < 4; ++ks) kf[t][ks] = *(const KF*)(kbase + (long)row * p.k_rs + 32 * ks);
         }
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int row = min(max(k0 + 4 * i + q4, row_lo), row_hi);
-            vf[i] = *(const uint4*)(vbase + (long)row * p.v_rs);
+            vf[i] = *(const VF*)(vbase + (long)row * p.v_rs);
+        }
+        if constexpr (KV8) {
+            const float* ksb = k_scale + (long)b * sc_bs + hk;
+            const float* vsb = v_scale + (long)b * sc_bs + hk;
+#pragma unroll
+            for (int t = 0; t < NT16; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = min(max(k0 + 16 * t + 4 * q4 + r, row_lo), row_hi);
+                    ksc[t][r] = ksb[(long)row * sc_rs];
+                    vsc[t][r] = vsb[(long)row * sc_rs];
+                }
         }
     } else {
 #pragma unroll
         for (int t = 0; t < NT16; ++t)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
+            for (int ks = 0; ks < 4; ++ks) {
+                kf[t][ks] = KF{};
+                if constexpr (KV8) { ksc[t][ks] = 1.f; vsc[t][ks] = 1.f; }
+            }
 #pragma unroll
-                for (int j = 0; j < 8; ++j) kf[t][ks][j] = (__bf16)0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) vf[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (int i = 0; i < NV; ++i) vf[i] = VF{};
     }
-    {
-        const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)(hk * G + min(c16, G - 1)) * 128 + 8 * q4;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[ks] = *(const bf16x8*)(qptr + 32 * ks);
-            if (c16 >= G)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) qf[ks][j] = (__bf16)0.f;
-        }
-    }
+    if constexpr (!KV8) decode_load_q(p, b, hk, G, c16, q4, qf);
 
     // scores of the wave's KW keys, masked and scaled; st[t][r]: key k0 + 16 t + 4 q4 + r, query row c16
     f32x4 st[NT16];
@@ -1686,11 +1753,12 @@ __global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restri
     for (int t = 0; t < NT16; ++t) {
         st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[t][ks], qf[ks], st[t], 0, 0, 0);
+        for (int ks = 0; ks < 4; ++ks) st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k_operand(kf[t][ks]), qf[ks], st[t], 0, 0, 0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int key = k0 + 16 * t + 4 * q4 + r;
-            st[t][r] = (key >= kv_lo && key < p.Sk) ? st[t][r] * p.scale_log2 : -INFINITY;
+            const float sk = KV8 ? st[t][r] * ksc[t][r] : st[t][r];         // 2^e commutes with every fp32 rounding
+            st[t][r] = (key >= kv_lo && key < p.Sk) ? sk * p.scale_log2 : -INFINITY;
             mx = fmaxf(mx, st[t][r]);
         }
     }
@@ -1708,7 +1776,7 @@ __global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restri
         for (int r = 0; r < 4; ++r) {
             const float pv = __builtin_amdgcn_exp2f(st[t][r] - muse);
             ls += pv;
-            if (c16 < 8) s_p[wave][16 * t + 4 * q4 + r][c16] = pv;
+            if (c16 < 8) s_p[wave][16 * t + 4 * q4 + r][c16] = KV8 ? pv * vsc[t][r] : pv;      // exact; the row sum keeps pv
         }
     ls += __shfl_xor(ls, 16, 64);
     ls += __shfl_xor(ls, 32, 64);
@@ -1735,10 +1803,11 @@ __global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restri
 #pragma unroll
             for (int g = 0; g < GP; ++g) pg[g] = pr[g];
         }
-        const unsigned w[4] = {vf[i].x, vf[i].y, vf[i].z, vf[i].w};
+        float v8[8];
+        v_unpack(vf[i], v8);
 #pragma unroll
         for (int j2 = 0; j2 < 4; ++j2) {
-            const float v0 = __builtin_bit_cast(float, w[j2] << 16), v1 = __builtin_bit_cast(float, w[j2] & 0xffff0000u);
+            const float v0 = v8[2 * j2], v1 = v8[2 * j2 + 1];
 #pragma unroll
             for (int g = 0; g < GP; ++g) {
                 acc[g][2 * j2] = fmaf(pg[g], v0, acc[g][2 * j2]);
@@ -1808,6 +1877,15 @@ __global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restri
             if (d4 == 0) { ws_ml[2 * r] = m; ws_ml[2 * r + 1] = l; }
         }
     }
+}
+template <int GP>
+__global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
+    attn_decode_body<GP, false>(p, nullptr, nullptr, 0, 0, ws_ml, ws_o, nch);
+}
+template <int GP>
+__global__ __launch_bounds__(256) void attn_kv8_k(AttnArgs p, const float* __restrict__ k_scale, const float* __restrict__ v_scale, long sc_bs, long sc_rs,
+                                                  float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
+    attn_decode_body<GP, true>(p, k_scale, v_scale, sc_bs, sc_rs, ws_ml, ws_o, nch);
 }
 
 // Merge of a row's chunk partials, chunks in ascending order, fp32.  32 threads per (batch, query head), 8 heads per block.
@@ -1836,223 +1914,6 @@ __global__ __launch_bounds__(256) void attn_decode_combine_k(AttnArgs p, const f
     for (int e = 0; e < 4; ++e) ob[e] = f2bf(l > 0.f ? o[e] / l : 0.f);
     *(u16x4*)(p.O + (long)b * p.o_bs + (long)h * 128 + 4 * d4) = ob;
     if (p.lse && d4 == 0) p.lse[bh] = l > 0.f ? m + log2f(l) : INFINITY;
-}
-
-// ------------------------------------------------------------------------------------------ decode on the FP8 (e4m3) KV cache
-// attn_decode_k on a cache of OCP e4m3 bytes + one power-of-two fp32 scale per (row, slot, K-or-V head) (the format of
-// desta_rope_kv_append_e4m3): the same work items, chunk boundaries, lane slots, MFMA calls and summation order, so O, lse and
-// every workspace partial equal attn_decode_k's on the dequantised cache bf16(q * s) bit for bit (while score * s_k and p * s_v
-// stay normal fp32 values: a power of two commutes with a rounding only where nothing underflows).
-//   * K and V stream as bytes: a lane's K fragment is 8 contiguous bytes at the element offsets of the bf16 kernel, its V piece
-//     the 8 bytes of its 8 columns; rows and scale rows are clamped to [kv_start, seq_k).
-//   * K bytes become the bf16 fragment exactly (3 mantissa bits); the fp32 score is multiplied by the key's K scale.
-//   * V bytes become fp32; the key's V scale is folded into the probability that goes to s_p (pv * s_v, exact), so the fma
-//     rounds the product the bf16 kernel rounds.  The row sum keeps pv.
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-__device__ __forceinline__ bf16x8 e4m3x8_to_bf16(const uint2& q) {
-    union { unsigned u[4]; bf16x8 v; } o;
-    const unsigned w[2] = {q.x, q.y};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
-        o.u[2 * i] = __builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u);
-        o.u[2 * i + 1] = __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u);
-    }
-    return o.v;
-}
-template <int GP>                                          // G rounded up to 1, 2, 4, 8
-__global__ __launch_bounds__(256) void attn_kv8_k(AttnArgs p, const float* __restrict__ k_scale, const float* __restrict__ v_scale, long sc_bs, long sc_rs,
-                                                  float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
-    constexpr int CH = DESTA_ATTN_DECODE_CHUNK, KW = CH / 4, NT16 = KW / 16, NV = KW / 4;
-    __shared__ __attribute__((aligned(16))) float s_p[4][KW][8];
-    __shared__ __attribute__((aligned(16))) float s_red[4][GP][128];
-    __shared__ float s_m[4][8], s_l[4][8];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c16 = lane & 15, q4 = lane >> 4;
-    const int G = p.Hq / p.Hkv;
-    int id = blockIdx.x;
-    const int c = id % nch; id /= nch;
-    const int hk = id % p.Hkv, b = id / p.Hkv;
-    const int kv_lo = p.kv_start ? max(0, min(p.kv_start[b], p.Sk)) : 0;
-    const int k0 = c * CH + wave * KW;
-    const bool live = k0 < p.Sk && k0 + KW > kv_lo;        // wave-uniform: some key of this wave is visible
-    const int row_lo = min(kv_lo, p.Sk - 1), row_hi = p.Sk - 1;
-
-    uint2 kq[NT16][4], vq[NV];
-    float ksc[NT16][4], vsc[NT16][4];                      // scales of keys k0 + 16 t + 4 q4 + r: the keys of this lane's st[t][r]
-    bf16x8 qf[4];
-    if (live) {
-        const uint8_t* kbase = (const uint8_t*)p.K + (long)b * p.k_bs + (long)hk * 128 + 8 * q4;
-        const uint8_t* vbase = (const uint8_t*)p.V + (long)b * p.v_bs + (long)hk * 128 + 8 * c16;
-        const float* ksb = k_scale + (long)b * sc_bs + hk;
-        const float* vsb = v_scale + (long)b * sc_bs + hk;
-#pragma unroll
-        for (int t = 0; t < NT16; ++t) {
-            const int row = min(max(k0 + 16 * t + c16, row_lo), row_hi);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) kq[t][ks] = *(const uint2*)(kbase + (long)row * p.k_rs + 32 * ks);
-        }
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int row = min(max(k0 + 4 * i + q4, row_lo), row_hi);
-            vq[i] = *(const uint2*)(vbase + (long)row * p.v_rs);
-        }
-#pragma unroll
-        for (int t = 0; t < NT16; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = min(max(k0 + 16 * t + 4 * q4 + r, row_lo), row_hi);
-                ksc[t][r] = ksb[(long)row * sc_rs];
-                vsc[t][r] = vsb[(long)row * sc_rs];
-            }
-    } else {
-#pragma unroll
-        for (int t = 0; t < NT16; ++t)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) { kq[t][ks] = make_uint2(0u, 0u); ksc[t][ks] = 1.f; vsc[t][ks] = 1.f; }
-#pragma unroll
-        for (int i = 0; i < NV; ++i) vq[i] = make_uint2(0u, 0u);
-    }
-    {
-        const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)(hk * G + min(c16, G - 1)) * 128 + 8 * q4;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[ks] = *(const bf16x8*)(qptr + 32 * ks);
-            if (c16 >= G)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) qf[ks][j] = (__bf16)0.f;
-        }
-    }
-
-    // scores of the wave's KW keys, masked and scaled; st[t][r]: key k0 + 16 t + 4 q4 + r, query row c16
-    f32x4 st[NT16];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < NT16; ++t) {
-        st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(e4m3x8_to_bf16(kq[t][ks]), qf[ks], st[t], 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int key = k0 + 16 * t + 4 * q4 + r;
-            st[t][r] = (key >= kv_lo && key < p.Sk) ? (st[t][r] * ksc[t][r]) * p.scale_log2 : -INFINITY;   // 2^e commutes with every fp32 rounding
-            mx = fmaxf(mx, st[t][r]);
-        }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (lane < 8) s_m[wave][lane] = mx;
-    __syncthreads();
-    const int g8 = c16 & 7;
-    const float mblk = fmaxf(fmaxf(s_m[0][g8], s_m[1][g8]), fmaxf(s_m[2][g8], s_m[3][g8]));
-    const float muse = (mblk == -INFINITY) ? 0.f : mblk;
-    float ls = 0.f;
-#pragma unroll
-    for (int t = 0; t < NT16; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float pv = __builtin_amdgcn_exp2f(st[t][r] - muse);
-            ls += pv;
-            if (c16 < 8) s_p[wave][16 * t + 4 * q4 + r][c16] = pv * vsc[t][r];     // exact; the row sum keeps pv
-        }
-    ls += __shfl_xor(ls, 16, 64);
-    ls += __shfl_xor(ls, 32, 64);
-    if (lane < 8) s_l[wave][lane] = ls;
-    __syncthreads();
-
-    // P . V: acc[g][j] = sum over this lane's keys of P[g][key] * V[key][8 c16 + j]
-    float acc[GP][8];
-#pragma unroll
-    for (int g = 0; g < GP; ++g)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float* pr = &s_p[wave][4 * i + q4][0];
-        float pg[GP];
-        if constexpr (GP >= 4) {
-#pragma unroll
-            for (int g = 0; g < GP; g += 4) {
-                const f32x4 t4 = *(const f32x4*)(pr + g);
-                pg[g] = t4[0]; pg[g + 1] = t4[1]; pg[g + 2] = t4[2]; pg[g + 3] = t4[3];
-            }
-        } else {
-#pragma unroll
-            for (int g = 0; g < GP; ++g) pg[g] = pr[g];
-        }
-        const f32x2 vv[4] = {__builtin_amdgcn_cvt_pk_f32_fp8((int)vq[i].x, false), __builtin_amdgcn_cvt_pk_f32_fp8((int)vq[i].x, true),
-                             __builtin_amdgcn_cvt_pk_f32_fp8((int)vq[i].y, false), __builtin_amdgcn_cvt_pk_f32_fp8((int)vq[i].y, true)};
-#pragma unroll
-        for (int j2 = 0; j2 < 4; ++j2) {
-            const float v0 = vv[j2][0], v1 = vv[j2][1];
-#pragma unroll
-            for (int g = 0; g < GP; ++g) {
-                acc[g][2 * j2] = fmaf(pg[g], v0, acc[g][2 * j2]);
-                acc[g][2 * j2 + 1] = fmaf(pg[g], v1, acc[g][2 * j2 + 1]);
-            }
-        }
-    }
-    // fold the four key classes (lanes l, l ^ 16, l ^ 32, l ^ 48): each exchange halves the query rows a lane keeps
-    const bool hi32 = (lane & 32) != 0, hi16 = (lane & 16) != 0;
-    constexpr int G1 = GP >= 2 ? GP / 2 : GP, G2 = GP >= 4 ? GP / 4 : G1;
-    float a1[G1][8], a2[G2][8];
-#pragma unroll
-    for (int g = 0; g < G1; ++g)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if constexpr (GP >= 2) {
-                const float keep = hi32 ? acc[g + G1][j] : acc[g][j], send = hi32 ? acc[g][j] : acc[g + G1][j];
-                a1[g][j] = keep + __shfl_xor(send, 32, 64);
-            } else {
-                a1[g][j] = acc[g][j] + __shfl_xor(acc[g][j], 32, 64);
-            }
-        }
-#pragma unroll
-    for (int g = 0; g < G2; ++g)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if constexpr (GP >= 4) {
-                const float keep = hi16 ? a1[g + G2][j] : a1[g][j], send = hi16 ? a1[g][j] : a1[g + G2][j];
-                a2[g][j] = keep + __shfl_xor(send, 16, 64);
-            } else {
-                a2[g][j] = a1[g][j] + __shfl_xor(a1[g][j], 16, 64);
-            }
-        }
-    {
-        // query rows this lane now holds: GP >= 4: (hi32 ? G1 : 0) + (hi16 ? G2 : 0) + g;  GP == 2: hi32 (both lanes of an
-        // xor-16 pair hold the same sums: one writes);  GP == 1: row 0 on every lane (lanes 0..15 write)
-        const int gbase = (GP >= 2 && hi32 ? G1 : 0) + (GP >= 4 && hi16 ? G2 : 0);
-        const bool writer = GP >= 4 ? true : (GP == 2 ? !hi16 : lane < 16);
-        if (writer)
-#pragma unroll
-            for (int g = 0; g < G2; ++g) {
-                float* dst = &s_red[wave][gbase + g][8 * c16];
-                *(f32x4*)dst = f32x4{a2[g][0], a2[g][1], a2[g][2], a2[g][3]};
-                *(f32x4*)(dst + 4) = f32x4{a2[g][4], a2[g][5], a2[g][6], a2[g][7]};
-            }
-    }
-    __syncthreads();
-
-    // the block's result: thread t < 32 GP sums the four waves for query row t / 32, columns 4 (t % 32) .. + 3
-    const int tg = threadIdx.x >> 5, d4 = threadIdx.x & 31;
-    if (tg < G) {
-        f32x4 o = *(const f32x4*)&s_red[0][tg][4 * d4];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) o += *(const f32x4*)&s_red[w][tg][4 * d4];
-        const float m = fmaxf(fmaxf(s_m[0][tg], s_m[1][tg]), fmaxf(s_m[2][tg], s_m[3][tg]));
-        const float l = ((s_l[0][tg] + s_l[1][tg]) + s_l[2][tg]) + s_l[3][tg];
-        const int h = hk * G + tg;
-        if (nch == 1) {
-            u16x4 ob;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ob[e] = f2bf(l > 0.f ? o[e] / l : 0.f);
-            *(u16x4*)(p.O + (long)b * p.o_bs + (long)h * 128 + 4 * d4) = ob;
-            if (p.lse && d4 == 0) p.lse[(long)b * p.Hq + h] = l > 0.f ? m + log2f(l) : INFINITY;
-        } else {
-            const long r = ((long)b * p.Hq + h) * nch + c;
-            *(f32x4*)(ws_o + r * 128 + 4 * d4) = o;
-            if (d4 == 0) { ws_ml[2 * r] = m; ws_ml[2 * r + 1] = l; }
-        }
-    }
 }
 
 int fill_args(const desta_attn_desc* d, AttnArgs& a) {
@@ -2148,85 +2009,62 @@ extern "C" size_t desta_attention_decode_workspace_bytes(int batch, int n_q_head
     return (decode_ml_floats(items) + items * (size_t)head_dim) * sizeof(float);
 }
 
-extern "C" int desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-    DESTA_CHECK_ARG(d, "attention_decode: null descriptor");
-    DESTA_CHECK_ARG(d->seq_q == 1, "attention_decode: seq_q %d unsupported (one query row per sequence)", d->seq_q);
-    DESTA_CHECK_ARG(d->head_dim == 128, "attention_decode: head_dim %d unsupported (128)", d->head_dim);
-    DESTA_CHECK_ARG(!d->causal, "attention_decode: causal must be 0 (the one query row sees every key of [kv_start, seq_k))");
-    DESTA_CHECK_ARG(d->dropout_p == 0.f, "attention_decode: dropout_p must be 0");
-    DESTA_CHECK_ARG(!d->rope_cos_sin, "attention_decode: rope_cos_sin must be NULL");
-    DESTA_CHECK_ARG(!d->O_f32, "attention_decode: O_f32 must be NULL");
-    DESTA_CHECK_ARG(!d->dO && !d->dQ, "attention_decode: dO and dQ must be NULL (forward only)");
+// Both decode entry points: `who` prefixes every message; k_scale != NULL selects the FP8-cache kernel.
+static int decode_launch(const char* who, const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t sbs, int64_t srs,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    DESTA_CHECK_ARG(d, "%s: null descriptor", who);
+    DESTA_CHECK_ARG(d->seq_q == 1, "%s: seq_q %d unsupported (one query row per sequence)", who, d->seq_q);
+    DESTA_CHECK_ARG(d->head_dim == 128, "%s: head_dim %d unsupported (128)", who, d->head_dim);
+    DESTA_CHECK_ARG(!d->causal, "%s: causal must be 0 (the one query row sees every key of [kv_start, seq_k))", who);
+    DESTA_CHECK_ARG(d->dropout_p == 0.f, "%s: dropout_p must be 0", who);
+    DESTA_CHECK_ARG(!d->rope_cos_sin, "%s: rope_cos_sin must be NULL", who);
+    DESTA_CHECK_ARG(!d->O_f32, "%s: O_f32 must be NULL", who);
+    DESTA_CHECK_ARG(!d->dO && !d->dQ, "%s: dO and dQ must be NULL (forward only)", who);
     AttnArgs a;
     if (int rc = fill_args(d, a)) return rc;
     const int G = a.Hq / a.Hkv;
-    DESTA_CHECK_ARG(G <= 8, "attention_decode: group of %d query heads per kv head unsupported (at most 8)", G);
+    DESTA_CHECK_ARG(G <= 8, "%s: group of %d query heads per kv head unsupported (at most 8)", who, G);
     DESTA_CHECK_ARG(d->O && ((size_t)d->O & 15) == 0 && d->o_batch_stride % 8 == 0,
-                    "attention_decode: O must be 16-byte aligned with a batch stride that is a multiple of 8 elements");
+                    "%s: O must be 16-byte aligned with a batch stride that is a multiple of 8 elements", who);
     DESTA_CHECK_ARG((((size_t)d->Q | (size_t)d->K | (size_t)d->V) & 15) == 0 && d->q_batch_stride % 8 == 0 &&
                     d->k_batch_stride % 8 == 0 && d->v_batch_stride % 8 == 0,
-                    "attention_decode: Q, K, V must be 16-byte aligned with batch strides that are multiples of 8 elements");
+                    "%s: Q, K, V must be 16-byte aligned with batch strides that are multiples of 8 elements", who);
     const int nch = (a.Sk + DESTA_ATTN_DECODE_CHUNK - 1) / DESTA_ATTN_DECODE_CHUNK;
     const size_t need = desta_attention_decode_workspace_bytes(a.B, a.Hq, a.Sk, 128);
     DESTA_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need && ((size_t)workspace & 15) == 0),
-                    "attention_decode: workspace of %zu bytes is too small or misaligned (%zu needed, 16-byte aligned)", workspace_bytes, need);
-    DESTA_CHECK_ARG((long)a.B * a.Hkv * nch <= 0x7fffffffL, "attention_decode: grid too large");
+                    "%s: workspace of %zu bytes is too small or misaligned (%zu needed, 16-byte aligned)", who, workspace_bytes, need);
+    DESTA_CHECK_ARG((long)a.B * a.Hkv * nch <= 0x7fffffffL, "%s: grid too large", who);
     float* ws_ml = (float*)workspace;
     float* ws_o = ws_ml ? ws_ml + decode_ml_floats((size_t)a.B * a.Hq * nch) : nullptr;
     const dim3 grid((unsigned)(a.B * a.Hkv * nch));
     hipStream_t st = (hipStream_t)stream;
-    if (G == 1) hipLaunchKernelGGL((attn_decode_k<1>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
-    else if (G == 2) hipLaunchKernelGGL((attn_decode_k<2>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
-    else if (G <= 4) hipLaunchKernelGGL((attn_decode_k<4>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
-    else hipLaunchKernelGGL((attn_decode_k<8>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
-    DESTA_CHECK_LAUNCH("attention_decode");
+#define DECODE_LAUNCH(GP)                                                                                                               \
+    do {                                                                                                                                \
+        if (k_scale) hipLaunchKernelGGL((attn_kv8_k<GP>), grid, dim3(256), 0, st, a, k_scale, v_scale, (long)sbs, (long)srs, ws_ml, ws_o, nch); \
+        else hipLaunchKernelGGL((attn_decode_k<GP>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);                                      \
+    } while (0)
+    if (G == 1) DECODE_LAUNCH(1);
+    else if (G == 2) DECODE_LAUNCH(2);
+    else if (G <= 4) DECODE_LAUNCH(4);
+    else DECODE_LAUNCH(8);
+#undef DECODE_LAUNCH
+    DESTA_CHECK_LAUNCH(who);
     if (nch > 1) {
         hipLaunchKernelGGL(attn_decode_combine_k, dim3((unsigned)((a.B * a.Hq + 7) / 8)), dim3(256), 0, st, a, ws_ml, ws_o, nch);
-        DESTA_CHECK_LAUNCH("attention_decode (combine)");
+        DESTA_CHECK_LAUNCH(k_scale ? "attention_decode_kv8 (combine)" : "attention_decode (combine)");
     }
     return DESTA_OK;
+}
+
+extern "C" int desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    return decode_launch("attention_decode", d, nullptr, nullptr, 0, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int desta_attention_decode_kv8(const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t scale_batch_stride,
                                           int64_t scale_row_stride, void* workspace, size_t workspace_bytes, void* stream) {
     DESTA_CHECK_ARG(d, "attention_decode_kv8: null descriptor");
     DESTA_CHECK_ARG(k_scale && v_scale && scale_batch_stride >= 0 && scale_row_stride > 0, "attention_decode_kv8: null scale or bad scale stride");
-    DESTA_CHECK_ARG(d->seq_q == 1, "attention_decode_kv8: seq_q %d unsupported (one query row per sequence)", d->seq_q);
-    DESTA_CHECK_ARG(d->head_dim == 128, "attention_decode_kv8: head_dim %d unsupported (128)", d->head_dim);
-    DESTA_CHECK_ARG(!d->causal, "attention_decode_kv8: causal must be 0 (the one query row sees every key of [kv_start, seq_k))");
-    DESTA_CHECK_ARG(d->dropout_p == 0.f, "attention_decode_kv8: dropout_p must be 0");
-    DESTA_CHECK_ARG(!d->rope_cos_sin, "attention_decode_kv8: rope_cos_sin must be NULL");
-    DESTA_CHECK_ARG(!d->O_f32, "attention_decode_kv8: O_f32 must be NULL");
-    DESTA_CHECK_ARG(!d->dO && !d->dQ, "attention_decode_kv8: dO and dQ must be NULL (forward only)");
-    AttnArgs a;
-    if (int rc = fill_args(d, a)) return rc;
-    const int G = a.Hq / a.Hkv;
-    DESTA_CHECK_ARG(G <= 8, "attention_decode_kv8: group of %d query heads per kv head unsupported (at most 8)", G);
-    DESTA_CHECK_ARG(d->O && ((size_t)d->O & 15) == 0 && d->o_batch_stride % 8 == 0,
-                    "attention_decode_kv8: O must be 16-byte aligned with a batch stride that is a multiple of 8 elements");
-    DESTA_CHECK_ARG((((size_t)d->Q | (size_t)d->K | (size_t)d->V) & 15) == 0 && d->q_batch_stride % 8 == 0 &&
-                    d->k_batch_stride % 8 == 0 && d->v_batch_stride % 8 == 0,
-                    "attention_decode_kv8: Q, K, V must be 16-byte aligned with batch strides that are multiples of 8 elements");
-    const int nch = (a.Sk + DESTA_ATTN_DECODE_CHUNK - 1) / DESTA_ATTN_DECODE_CHUNK;
-    const size_t need = desta_attention_decode_workspace_bytes(a.B, a.Hq, a.Sk, 128);
-    DESTA_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need && ((size_t)workspace & 15) == 0),
-                    "attention_decode_kv8: workspace of %zu bytes is too small or misaligned (%zu needed, 16-byte aligned)", workspace_bytes, need);
-    DESTA_CHECK_ARG((long)a.B * a.Hkv * nch <= 0x7fffffffL, "attention_decode_kv8: grid too large");
-    float* ws_ml = (float*)workspace;
-    float* ws_o = ws_ml ? ws_ml + decode_ml_floats((size_t)a.B * a.Hq * nch) : nullptr;
-    const dim3 grid((unsigned)(a.B * a.Hkv * nch));
-    hipStream_t st = (hipStream_t)stream;
-    const long sbs = (long)scale_batch_stride, srs = (long)scale_row_stride;
-    if (G == 1) hipLaunchKernelGGL((attn_kv8_k<1>), grid, dim3(256), 0, st, a, k_scale, v_scale, sbs, srs, ws_ml, ws_o, nch);
-    else if (G == 2) hipLaunchKernelGGL((attn_kv8_k<2>), grid, dim3(256), 0, st, a, k_scale, v_scale, sbs, srs, ws_ml, ws_o, nch);
-    else if (G <= 4) hipLaunchKernelGGL((attn_kv8_k<4>), grid, dim3(256), 0, st, a, k_scale, v_scale, sbs, srs, ws_ml, ws_o, nch);
-    else hipLaunchKernelGGL((attn_kv8_k<8>), grid, dim3(256), 0, st, a, k_scale, v_scale, sbs, srs, ws_ml, ws_o, nch);
-    DESTA_CHECK_LAUNCH("attention_decode_kv8");
-    if (nch > 1) {
-        hipLaunchKernelGGL(attn_decode_combine_k, dim3((unsigned)((a.B * a.Hq + 7) / 8)), dim3(256), 0, st, a, ws_ml, ws_o, nch);
-        DESTA_CHECK_LAUNCH("attention_decode_kv8 (combine)");
-    }
-    return DESTA_OK;
+    return decode_launch("attention_decode_kv8", d, k_scale, v_scale, scale_batch_stride, scale_row_stride, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------- FP8 KV cache -> bf16 staging slab (chunked prompt pass)

@@ -310,6 +310,39 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_k(const bf16_t* __restrict__ 
 // KV-cache append (generate()): with kv.dst the grid also covers the V heads that follow K in `buf`; rotated K heads and
 // plain V heads of row (b, s) are ALSO written to kv.dst + b*bs + (slot0 + s)*rs + (head - n_q)*HD (the K|V slab).
 struct RopeKV { bf16_t* dst; long bs, rs; int slot0; int n_v; };
+// Forward rotation of lane j's 2 x 8 elements of the head at p, position pos (NORM == 1: RMSNorm with weight w first, rounded to
+// bf16 twice as HF does).  Every lane of a head group has to get here: the norm's sum is a shuffle over the group.
+template <int HD, int NORM>
+__device__ __forceinline__ void rope_fwd_rotate(const bf16_t* p, int j, int pos, const float* __restrict__ cs, const float* __restrict__ w,
+                                                float eps, float (&oa)[8], float (&ob)[8]) {
+    constexpr int G = HD / 16, H2 = HD / 2;
+    float a[8], b[8], c[8], s[8];
+    load8(p, 8 * j, 0, a);
+    load8(p, H2 + 8 * j, 0, b);
+    load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
+    load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
+    // The sums of two products are spelled as fmaf(x, y, u * v): under -ffp-contract=fast the compiler is free to fuse either
+    // product of "x * y + u * v", and which one it takes varies with the code around it, so the two kernels that inline this
+    // would not round alike.  These are the forms both kernels were compiled to before the rotation became one function.
+    if (NORM == 1) {
+        float q = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q += fmaf(a[e], a[e], b[e] * b[e]);
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) q += __shfl_xor(q, o, 64);
+        const float rstd = rsqrtf(q / (float)HD + eps);
+        float wa[8], wb[8];
+        load8(w, 8 * j, 1, wa);
+        load8(w, H2 + 8 * j, 1, wb);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            a[e] = bf2f(f2bf(wa[e] * bf2f(f2bf(a[e] * rstd))));
+            b[e] = bf2f(f2bf(wb[e] * bf2f(f2bf(b[e] * rstd))));
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { oa[e] = fmaf(a[e], c[e], -(b[e] * s[e])); ob[e] = fmaf(b[e], c[e], a[e] * s[e]); }
+}
 template <int HD, int NORM, bool BWD>
 __global__ __launch_bounds__(256) void rope_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
                                               const float* __restrict__ cs, const float* __restrict__ wq,
@@ -335,32 +368,9 @@ __global__ __launch_bounds__(256) void rope_k(bf16_t* __restrict__ buf, long ld,
     const int spos = sm_batch ? row / sm_batch : row % S, bidx = sm_batch ? row % sm_batch : row / S;
     const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
     bf16_t* p = buf + (long)row * ld + (long)head * HD;
-    float a[8], b[8], c[8], s[8];
-    load8(p, 8 * j, 0, a);
-    load8(p, H2 + 8 * j, 0, b);
-    load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
-    load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
     if (!BWD) {
-        if (NORM == 1) {
-            const float* w = head < n_q ? wq : wk;
-            float q = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) q += a[e] * a[e] + b[e] * b[e];
-#pragma unroll
-            for (int o = 1; o < G; o <<= 1) q += __shfl_xor(q, o, 64);
-            const float rstd = rsqrtf(q / (float)HD + eps);
-            float wa[8], wb[8];
-            load8(w, 8 * j, 1, wa);
-            load8(w, H2 + 8 * j, 1, wb);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                a[e] = bf2f(f2bf(wa[e] * bf2f(f2bf(a[e] * rstd))));
-                b[e] = bf2f(f2bf(wb[e] * bf2f(f2bf(b[e] * rstd))));
-            }
-        }
         float oa[8], ob[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { oa[e] = a[e] * c[e] - b[e] * s[e]; ob[e] = b[e] * c[e] + a[e] * s[e]; }
+        rope_fwd_rotate<HD, NORM>(p, j, pos, cs, head < n_q ? wq : wk, eps, oa, ob);
         if (active) {
             store8_bf16(p, 8 * j, oa); store8_bf16(p, H2 + 8 * j, ob);
             if (kv.dst && head >= n_q) {
@@ -369,6 +379,11 @@ __global__ __launch_bounds__(256) void rope_k(bf16_t* __restrict__ buf, long ld,
             }
         }
     } else {
+        float a[8], b[8], c[8], s[8];
+        load8(p, 8 * j, 0, a);
+        load8(p, H2 + 8 * j, 0, b);
+        load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
+        load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
         float ga[8], gb[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) { ga[e] = a[e] * c[e] + b[e] * s[e]; gb[e] = b[e] * c[e] - a[e] * s[e]; }
@@ -819,31 +834,8 @@ __global__ __launch_bounds__(256) void rope_kv8_k(bf16_t* __restrict__ buf, long
     } else {
         const int spos = row % S, bidx = row / S;
         const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
-        float a[8], b[8], c[8], s[8];
-        load8(p, 8 * j, 0, a);
-        load8(p, H2 + 8 * j, 0, b);
-        load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
-        load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
-        if (NORM == 1) {
-            const float* w = head < n_q ? wq : wk;
-            float q = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) q += a[e] * a[e] + b[e] * b[e];
-#pragma unroll
-            for (int o = 1; o < G; o <<= 1) q += __shfl_xor(q, o, 64);
-            const float rstd = rsqrtf(q / (float)HD + eps);
-            float wa[8], wb[8];
-            load8(w, 8 * j, 1, wa);
-            load8(w, H2 + 8 * j, 1, wb);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                a[e] = bf2f(f2bf(wa[e] * bf2f(f2bf(a[e] * rstd))));
-                b[e] = bf2f(f2bf(wb[e] * bf2f(f2bf(b[e] * rstd))));
-            }
-        }
         float oa[8], ob[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { oa[e] = a[e] * c[e] - b[e] * s[e]; ob[e] = b[e] * c[e] + a[e] * s[e]; }
+        rope_fwd_rotate<HD, NORM>(p, j, pos, cs, head < n_q ? wq : wk, eps, oa, ob);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { ca[e] = f2bf(oa[e]); cb[e] = f2bf(ob[e]); }
         if (active) { *(u16x8*)(p + 8 * j) = ca; *(u16x8*)(p + H2 + 8 * j) = cb; }

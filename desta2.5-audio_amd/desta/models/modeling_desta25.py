@@ -1793,13 +1793,8 @@ class CausalLMHIP:
             elif kv_cache is None:
                 H.rope(s["qkv"], self.qkvw, M, S, self.hq, self.hkv, self.hd, cs, ly.get("qn"), ly.get("kn"), c.rms_norm_eps, pos_shift=pos_shift,
                        s_major_batch=smb)
-            elif kv_cache[i].dtype == torch.uint8:                            # FP8 cache: same rotation, the append quantises per head
-                sc = self.kv_scale[i]
-                H.rope_kv_append_e4m3(s["qkv"], self.qkvw, M, S, self.hq, self.hkv, self.hd, cs, ly.get("qn"), ly.get("kn"), c.rms_norm_eps,
-                                      pos_shift, kv_cache[i], kv_cache[i].stride(0), kv_cache[i].stride(1), sc, sc.stride(0), sc.stride(1), 0)
-            else:
-                H.rope_kv_append(s["qkv"], self.qkvw, M, S, self.hq, self.hkv, self.hd, cs, ly.get("qn"), ly.get("kn"), c.rms_norm_eps,
-                                 pos_shift, kv_cache[i], kv_cache[i].stride(0), kv_cache[i].stride(1), 0)
+            else:                                                             # generate(): `kv_cache` is self.kv_cache, `cos_sin` its table
+                self._kv_append(i, ly, s["qkv"], M, S, pos_shift, 0)
             aw = self.hq * self.hd
             ad = H.attn_desc(s["qkv"], s["qkv"], s["qkv"], s["att"], s["lse"], batch=B, hq=self.hq, hkv=self.hkv, sq=S, sk=S, hd=self.hd,
                              scale=scale, causal=True, kv_start=kv_start, q_off=0, k_off=self.hq * self.hd, v_off=(self.hq + self.hkv) * self.hd,
@@ -1880,6 +1875,19 @@ class CausalLMHIP:
         self.g_logits = torch.zeros(B, self.Vp, dtype=BF16, device=dev)
         self.g_next = torch.zeros(B, dtype=torch.int64, device=dev)
 
+    def _kv_append(self, li: int, ly: dict, qkv: torch.Tensor, rows: int, seq: int, shift: torch.Tensor, slot0: int) -> None:
+        """Rotate q, k of `qkv` [rows, qkvw] (batch-major, `seq` rows per sequence, position = row's index + shift[b]) in place and
+        append the rotated K | V of layer `li` at slots [slot0, slot0 + seq) of its cache slab.  The slab's dtype picks the kernel:
+        bf16 as it is, uint8 (FP8 cache) quantised per head with the scales into `kv_scale[li]`.  Every stride is the tensor's."""
+        cache = self.kv_cache[li]
+        args = (qkv, self.qkvw, rows, seq, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"), self.c.rms_norm_eps, shift,
+                cache, cache.stride(0), cache.stride(1))
+        if cache.dtype == torch.uint8:
+            sc = self.kv_scale[li]
+            H.rope_kv_append_e4m3(*args, sc, sc.stride(0), sc.stride(1), slot0)
+        else:
+            H.rope_kv_append(*args, slot0)
+
     # -- lean, chunked prompt pass of generate() (`set_prefill_chunk`): nothing is kept for a backward ---------------------------
     def _prefill_alloc(self, B: int, S: int, Cm: int) -> dict:
         """Buffers of `prefill`: the prompt's embeddings [B*S, h] (the only one sized by S) and ONE set of per-chunk activations
@@ -1932,15 +1940,12 @@ class CausalLMHIP:
                 H.rmsnorm_fwd(x, ly["n1"], eps, hb, r)
                 H.gemm(hb, ly["wqkv"] if self.lora is None else self._lora_merged(i), qkv, M, self.qkvw, h)
                 cache = self.kv_cache[i]
+                self._kv_append(i, ly, qkv, M, Cc, shift, c0)
                 if kv8:
                     sc = self.kv_scale[i]
-                    H.rope_kv_append_e4m3(qkv, self.qkvw, M, Cc, hq, hkv, hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"), eps, shift,
-                                          cache, Smax * kvw, kvw, sc, Smax * 2 * hkv, 2 * hkv, c0)
                     H.kv8_dequant(cache, Smax * kvw, kvw, sc, Smax * 2 * hkv, 2 * hkv, kv_start, B, 2 * hkv, hd, c1, self.kv_stage, Smax * kvw, kvw)
                     kv = self.kv_stage
                 else:
-                    H.rope_kv_append(qkv, self.qkvw, M, Cc, hq, hkv, hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"), eps, shift,
-                                     cache, Smax * kvw, kvw, c0)
                     kv = cache
                 H.attention_fwd(H.attn_desc(qkv, kv, kv, att, lse, batch=B, hq=hq, hkv=hkv, sq=Cc, sk=c1, hd=hd, scale=scale, causal=True,
                                             kv_start=kv_start, q_off=0, k_off=0, v_off=hkv * hd, q_rs=self.qkvw, k_rs=kvw, v_rs=kvw, o_rs=aw,
@@ -1996,19 +2001,13 @@ class CausalLMHIP:
                 proj(x, ly["n1"], ly["wqkv"], q8.get("wqkv"), self.g_qkv, self.qkvw)
             else:                                                             # the merged weight stays on H.gemm at every B
                 proj(x, ly["n1"], self._lora_merged(li), None, self.g_qkv, self.qkvw, wide=False)
-            if kv8:
-                sc = self.kv_scale[li]
-                H.rope_kv_append_e4m3(self.g_qkv, self.qkvw, B, 1, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"),
-                                      c.rms_norm_eps, pos_shift, cache, Smax * self.kvw, self.kvw, sc, Smax * 2 * self.hkv, 2 * self.hkv, cur)
-            else:
-                H.rope_kv_append(self.g_qkv, self.qkvw, B, 1, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"),
-                                 c.rms_norm_eps, pos_shift, cache, Smax * self.kvw, self.kvw, cur)     # rotate q,k + append K|V at slot cur
+            self._kv_append(li, ly, self.g_qkv, B, 1, pos_shift, cur)        # rotate q,k + append K|V at slot cur
             ad = H.attn_desc(self.g_qkv, cache, cache, self.g_att, self.g_lse, batch=B, hq=self.hq, hkv=self.hkv, sq=1, sk=cur + 1,
                              hd=self.hd, scale=scale, causal=False, kv_start=kv_start, q_off=0, k_off=0, v_off=self.hkv * self.hd,
                              q_rs=self.qkvw, k_rs=self.kvw, v_rs=self.kvw, o_rs=self.hq * self.hd,
                              q_bs=self.qkvw, k_bs=Smax * self.kvw, v_bs=Smax * self.kvw, o_bs=self.hq * self.hd)
             if kv8:
-                H.attention_decode_kv8(ad, sc, self.kv_scale_v[li], Smax * 2 * self.hkv, 2 * self.hkv, self.g_attn_ws)
+                H.attention_decode_kv8(ad, self.kv_scale[li], self.kv_scale_v[li], Smax * 2 * self.hkv, 2 * self.hkv, self.g_attn_ws)
             elif split_kv:
                 H.attention_decode(ad, self.g_attn_ws)
             else:

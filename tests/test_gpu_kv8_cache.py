@@ -148,10 +148,11 @@ def _cos_sin(n):
     return torch.stack([fr.cos(), fr.sin()], dim=1).contiguous()
 
 
-@pytest.mark.parametrize("Hq,Hkv", [(4, 2), (8, 1)])
-@pytest.mark.parametrize("norm", [False, True])
-@pytest.mark.parametrize("form", ["prompt", "decode"])
-def test_append_is_exact(hip, Hq, Hkv, norm, form):
+APPEND_CONFIGS = [(Hq, Hkv, norm, form) for form in ("prompt", "decode") for norm in (False, True) for Hq, Hkv in ((4, 2), (8, 1))]
+
+
+def append_inputs(Hq, Hkv, norm, form):
+    """-> (B, S, slot0, Smax, ld, qkv on the CPU, cos_sin, q-norm weight, k-norm weight, pos_shift on the device)"""
     B, S, slot0, Smax = (2, 5, 0, 9) if form == "prompt" else (3, 1, 7, 12)
     g = torch.Generator().manual_seed(Hq * 10 + Hkv + 2 * norm + S)
     nh, kvw = Hq + 2 * Hkv, 2 * Hkv * HD
@@ -173,6 +174,15 @@ def test_append_is_exact(hip, Hq, Hkv, norm, form):
     qn = (1 + 0.1 * torch.randn(HD, generator=g)).cuda() if norm else None
     kn = (1 + 0.1 * torch.randn(HD, generator=g)).cuda() if norm else None
     shift = torch.tensor([3, 0, 6][:B], dtype=torch.int32).cuda()            # non-zero pos_shift
+    return B, S, slot0, Smax, ld, qkv, cs, qn, kn, shift
+
+
+@pytest.mark.parametrize("Hq,Hkv", [(4, 2), (8, 1)])
+@pytest.mark.parametrize("norm", [False, True])
+@pytest.mark.parametrize("form", ["prompt", "decode"])
+def test_append_is_exact(hip, Hq, Hkv, norm, form):
+    B, S, slot0, Smax, ld, qkv, cs, qn, kn, shift = append_inputs(Hq, Hkv, norm, form)
+    kvw = 2 * Hkv * HD
     a, b = qkv.cuda(), qkv.cuda()
     c16 = torch.full((B, Smax, kvw), -3.0, dtype=torch.bfloat16, device="cuda")
     c8 = torch.full((B, Smax, kvw), 0xAB, dtype=torch.uint8, device="cuda")
