@@ -469,7 +469,7 @@ def test_adafactor_connector_shapes(hip):
     """Shapes of the real connector tensors (largest: 1280x3072, 4096x1280) incl. the 3-D prompts."""
     shapes = [(64, 4), (1, 64, 1280), (3072, 1280), (3072,), (1280, 3072), (1280,), (4096, 1280), (4096,)]
     _, opt = _run_adafactor_case(hip, shapes, steps=2, gscale=[0.02, 3.0])
-    assert opt.plan.n_groups >= 1 and opt.plan.max_chunks_per_tensor == 320
+    assert opt.plan.n_groups == 1 and opt.plan.max_chunks_per_tensor == 320      # 13.1 M floats: below GROUP_FLOATS, one group
 
 
 def _assert_chunk_table(opt):
@@ -509,10 +509,11 @@ def test_adafactor_ragged_rows_carry_no_chunks_and_take_the_unit_kernels(hip):
 
 
 def test_adafactor_many_chunk_tensor_and_descending_chunk_order(hip):
-    """A tensor of 321 chunks between small ones, several launch groups in the reverse arena order; 2 steps against the
-    exact-reduction oracle."""
+    """A tensor of 321 chunks between small ones, the chunks in the reverse arena order; 2 steps against the exact-reduction
+    oracle.  The plan is 5.4 M floats, below GROUP_FLOATS: ONE launch group (a plan cut into several groups is run by
+    test_gpu_adafactor_fp64.py::test_group_cut_changes_launches_not_arithmetic)."""
     _, opt = _run_adafactor_case(hip, [(8, 64), (4100, 1280), (1280,), (2, 16, 1280), (257, 516)], steps=2, gscale=[0.03, 2.0])
-    assert opt.plan.max_chunks_per_tensor == 321
+    assert opt.plan.max_chunks_per_tensor == 321 and opt.plan.n_groups == 1
     _assert_chunk_table(opt)
 
 
