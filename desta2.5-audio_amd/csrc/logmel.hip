@@ -124,7 +124,7 @@ __global__ __launch_bounds__(NT) void logmel_k1(const float* __restrict__ wave, 
         float acc = 0.f;
         const int klo = (int)krange[2 * m], khi = (int)krange[2 * m + 1];
         for (int kk = klo; kk < khi; ++kk) acc = fmaf(fb[kk * n_mels + m], pf[kk], acc);
-        const float lv = log10f(fmaxf(acc, 1e-10f));
+        const float lv = fmaxf(log10f(acc), -10.0f);   // log10(max(acc, 1e-10)) with the floor after the log: log10f(1e-10f) is 1 ulp off -10, silence must give -10
         const int t = t0 + f;
         if (t < N_FRAMES) {
             out[((long)b * n_mels + m) * N_FRAMES + t] = lv;

@@ -404,6 +404,7 @@ def test_gemm_rejects_bad_shapes(hip):
 
 @pytest.mark.parametrize("n_mels", [80, 128])
 def test_logmel_matches_oracle(hip, n_mels):
+    """Whole-tensor parity with the oracle; held per element against float64 on tones, impulses and quiet clips by tests/test_gpu_logmel_fp64.py."""
     g = torch.Generator().manual_seed(1234)
     wave = (0.1 * torch.randn(3, 480000, generator=g)).clamp(-1, 1)
     wave[1, 200000:] = 0.0                         # long silence: exercises the max-8 clamp
@@ -415,6 +416,7 @@ def test_logmel_matches_oracle(hip, n_mels):
 
 
 def test_logmel_short_and_long_clips(hip):
+    """Whole-tensor parity; lengths 1 .. 485000 are held per element against float64 by tests/test_gpu_logmel_fp64.py."""
     g = torch.Generator().manual_seed(7)
     short = 0.1 * torch.randn(2, 16000 * 3 + 17, generator=g)
     torch.testing.assert_close(hip.logmel(short.cuda(), 128).cpu(), O.logmel(short, 128), rtol=0, atol=2e-4)

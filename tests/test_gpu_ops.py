@@ -124,6 +124,7 @@ def test_colsum_transpose_cast_add(hip):
 
 
 def test_mel_to_rows(hip):
+    """One shape into a zeroed buffer; pad rows, pad channels and guards at four shapes: tests/test_gpu_logmel_fp64.py."""
     g = torch.Generator().manual_seed(3)
     mel = torch.randn(2, 80, 200, generator=g)
     out = torch.zeros(2, 202, 128, dtype=torch.bfloat16, device="cuda")
