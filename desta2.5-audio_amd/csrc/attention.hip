@@ -128,7 +128,15 @@ __device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8
 // Q, K, V).  Here XCD x walks the (batch, kv head) groups g = x, x + 8, ... and, inside a group, the query heads of the GQA
 // group and their q-blocks back to back, so the K / V tiles of a group are re-read from that XCD's L2.  Speed only: any
 // placement is correct.  Causal: q-blocks in descending order (most keys first).
-__device__ __forceinline__ void attn_work_item(const AttnArgs& p, int nq, int& qblk, int& h, int& b) {
+// What a wave of a query-block kernel works on: batch, kv head, query head, first row of the block and of the wave, this
+// lane's row.  wave_on (8-wave blocks): false for a wave past the ragged end, which only helps staging.
+struct QWork { int b, hk, h, qb0, q0, qcol; bool wave_on; };
+
+// four-wave (two-wave) blocks: NW * 32 rows of one head
+template <int NW>
+__device__ __forceinline__ QWork attn_work_item(const AttnArgs& p, int wave, int lane) {
+    constexpr int QB = 32 * NW;
+    const int nq = (p.Sq + QB - 1) / QB;
     const int id = blockIdx.x, per = nq * (p.Hq / p.Hkv), ngrp = p.B * p.Hkv;       // per = blocks of one (batch, kv head) group
     int g, r;
     if ((ngrp & 7) == 0) {
@@ -139,10 +147,176 @@ __device__ __forceinline__ void attn_work_item(const AttnArgs& p, int nq, int& q
         g = id / per;
         r = id % per;
     }
-    b = g / p.Hkv;
-    h = (g % p.Hkv) * (p.Hq / p.Hkv) + r / nq;
-    qblk = r % nq;
+    QWork w;
+    w.b = g / p.Hkv;
+    w.h = (g % p.Hkv) * (p.Hq / p.Hkv) + r / nq;
+    int qblk = r % nq;
     if (p.causal) qblk = nq - 1 - qblk;
+    w.qb0 = qblk * QB; w.q0 = w.qb0 + wave * 32;
+    w.hk = w.h / (p.Hq / p.Hkv);
+    w.qcol = w.q0 + (lane & 31);
+    w.wave_on = true;
+    return w;
+}
+
+// eight-wave blocks: HPB heads of one GQA group x 256 / HPB rows.  Causal launches the heaviest q-blocks of all groups first
+// (the K / V of an XCD's groups fit its L2 together), non-causal keeps the q-blocks of a group back to back.
+template <bool CAUSAL, int HPB>
+__device__ __forceinline__ QWork attn_work_item8(const AttnArgs& p, int wave, int lane) {
+    constexpr int RB = 256 / HPB, WPH = RB / 32;                   // query rows of a block (per head), waves per head
+    const int G = p.Hq / p.Hkv, nq = (p.Sq + RB - 1) / RB, hgroups = G / HPB, ngrp = p.B * p.Hkv;
+    int g, qblk, hg;
+    const int id = blockIdx.x, per = nq * hgroups;
+    if ((ngrp & 7) == 0) {
+        const int xcd = id & 7, slot = id >> 3, gpx = ngrp >> 3;
+        if (CAUSAL) {
+            const int r = slot % (hgroups * gpx);
+            qblk = nq - 1 - slot / (hgroups * gpx); hg = r / gpx; g = (r % gpx) * 8 + xcd;
+        } else {
+            const int r = slot % per;
+            g = (slot / per) * 8 + xcd; hg = r / nq; qblk = r % nq;
+        }
+    } else if (CAUSAL) {
+        const int r = id % (hgroups * ngrp);
+        qblk = nq - 1 - id / (hgroups * ngrp); hg = r / ngrp; g = r % ngrp;
+    } else {
+        const int r = id % per;
+        g = id / per; hg = r / nq; qblk = r % nq;
+    }
+    QWork w;
+    w.b = g / p.Hkv; w.hk = g % p.Hkv;
+    w.h = w.hk * G + hg * HPB + wave / WPH;
+    w.qb0 = qblk * RB; w.q0 = w.qb0 + (wave % WPH) * 32;
+    w.qcol = w.q0 + (lane & 31);
+    w.wave_on = w.q0 < p.Sq;                                       // scalar
+    return w;
+}
+
+// Keys a query block of QB rows walks, and what one of its waves and lanes may see.  `causal` is a compile-time constant in the
+// 8-wave kernels and p.causal in the others.
+struct KeyRange {
+    int coff, kv_lo;          // query row q sits on key q + coff; first valid key (left padding)
+    int t_lo, t_hi;           // 64-key tiles [t_lo, t_hi) of the block
+    int q0, q_abs;            // the wave's first row; last key this lane's row sees under the causal mask
+    int wave_kmax;            // last key any row of this wave may see
+};
+__device__ __forceinline__ KeyRange attn_key_range(const AttnArgs& p, int causal, const QWork& w, int QB) {
+    KeyRange k;
+    k.coff = p.Sk - p.Sq;
+    k.kv_lo = p.kv_start ? max(0, min(p.kv_start[w.b], p.Sk)) : 0;
+    int kv_hi = p.Sk;
+    if (causal) kv_hi = min(p.Sk, min(w.qb0 + QB - 1, p.Sq - 1) + k.coff + 1);
+    k.t_lo = k.kv_lo / 64; k.t_hi = (kv_hi + 63) / 64;
+    k.q0 = w.q0; k.q_abs = w.qcol + k.coff;
+    k.wave_kmax = causal ? min(w.q0 + 31, p.Sq - 1) + k.coff : p.Sk - 1;
+    return k;
+}
+
+// Key visibility (ragged Sk, left padding, causal diagonal) of NH 32-key accumulators that start at key0: masked scores become
+// -inf (exp2(-inf) = 0).  Boundary tiles only: the guard is wave-uniform and stays a BRANCH through the asm (hipcc otherwise
+// if-converts the compares + selects into every tile's straight-line code).
+template <int NH>
+__device__ __forceinline__ void mask_keys(f32x16* st, const AttnArgs& p, int causal, const KeyRange& k, int key0, int lane) {
+    const bool need_mask = (key0 + 32 * NH - 1 >= p.Sk) || (key0 < k.kv_lo) || (causal && key0 + 32 * NH - 1 > k.q0 + k.coff);
+    if (need_mask) {
+        asm volatile("; boundary tile" ::: "memory");
+#pragma unroll
+        for (int kb = 0; kb < NH; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = key0 + kb * 32 + acc_row(r, lane);
+                const bool ok = key < p.Sk && key >= k.kv_lo && (!causal || key <= k.q_abs);
+                st[kb][r] = ok ? st[kb][r] : -INFINITY;
+            }
+    }
+}
+
+// K / V tile walk of the four-wave kernels: both tiles register-staged PF tiles ahead (PF = 2: two register sets), one LDS
+// image each, two barriers per tile, the loop unrolled by two.  compute(kt) runs between a tile's store and the next one's.
+// ABL: the forward's timing ablations (ATTN_ABL); 0 everywhere else.
+template <int D, int NW, int PF, int ABL, class Compute>
+__device__ __forceinline__ void kv_tile_walk(const AttnArgs& p, const QWork& w, const KeyRange& k, char* kimg, char* vimg, Compute compute) {
+    constexpr int NT = 64 * NW;
+    const bf16_t* kbase = p.K + (long)w.b * p.k_bs + (long)w.hk * D;
+    const bf16_t* vbase = p.V + (long)w.b * p.v_bs + (long)w.hk * D;
+    const int t_lo = k.t_lo, t_hi = k.t_hi;
+    stage_t<D, 64, NT> kr0 = {}, vr0 = {}, kr1 = {}, vr1 = {};
+    if (t_lo < t_hi) {
+        kr0 = tile_load<D, 64, NT>(kbase, p.k_rs, t_lo * 64, p.Sk - 1);
+        vr0 = tile_load<D, 64, NT>(vbase, p.v_rs, t_lo * 64, p.Sk - 1);
+    }
+    if (PF == 2 && t_lo + 1 < t_hi) {
+        kr1 = tile_load<D, 64, NT>(kbase, p.k_rs, (t_lo + 1) * 64, p.Sk - 1);
+        vr1 = tile_load<D, 64, NT>(vbase, p.v_rs, (t_lo + 1) * 64, p.Sk - 1);
+    }
+#define DESTA_KV_STAGE(KT, KR, VR)                                                   \
+    __syncthreads(); /* previous tile's LDS reads are done */                        \
+    asm volatile("; stage " #KR ::: "memory"); /* distinct text: keeps the two halves from being tail-merged */ \
+    if (ABL != 1 || (KT) == t_lo) {                                                  \
+        tile_store<D, 64, NT>(kimg, KR);                                             \
+        tile_store<D, 64, NT>(vimg, VR);                                             \
+    }                                                                                \
+    __syncthreads();                                                                 \
+    if (ABL != 2 && (KT) + PF < t_hi) {                                              \
+        KR = tile_load<D, 64, NT>(kbase, p.k_rs, ((KT) + PF) * 64, p.Sk - 1);        \
+        VR = tile_load<D, 64, NT>(vbase, p.v_rs, ((KT) + PF) * 64, p.Sk - 1);        \
+    }
+    for (int kt = t_lo; kt < t_hi; kt += 2) {
+        DESTA_KV_STAGE(kt, kr0, vr0)
+        compute(kt);
+        if (kt + 1 < t_hi) {
+            if constexpr (PF == 2) {
+                DESTA_KV_STAGE(kt + 1, kr1, vr1)
+            } else {
+                DESTA_KV_STAGE(kt + 1, kr0, vr0)
+            }
+            compute(kt + 1);
+        }
+    }
+#undef DESTA_KV_STAGE
+}
+
+// this lane's row of a [d][query] fp32 accumulator -> bf16, as 8-byte pieces (registers 4 rq .. 4 rq + 3: d = 32 i + 8 rq + 4 h2 + e)
+template <int D>
+__device__ __forceinline__ void store_row_bf16(bf16_t* row, const f32x16* acc, int h2) {
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+            u16x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[i][4 * rq + e]);
+            *(u16x4*)(row + i * 32 + 8 * rq + 4 * h2) = o;
+        }
+}
+// the same row as 16-byte pieces (guide T21).  Registers 8j..8j+3: d = 32i + 16j + 4*h2 + e; 8j+4..8j+7: d = 32i + 16j + 8 + 4*h2 + e.
+// After a permlane32 exchange of the packed halves a lane of the lower half holds d = 32i + 16j + 0..7, its partner in the upper
+// half 32i + 16j + 8..15: one 16-byte store each
+template <int D>
+__device__ __forceinline__ void store_row_bf16_16B(bf16_t* row, const f32x16* acc, int h2) {
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            unsigned a[2], c[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                a[e] = (unsigned)f2bf(acc[i][8 * j + 2 * e]) | ((unsigned)f2bf(acc[i][8 * j + 2 * e + 1]) << 16);
+                c[e] = (unsigned)f2bf(acc[i][8 * j + 4 + 2 * e]) | ((unsigned)f2bf(acc[i][8 * j + 4 + 2 * e + 1]) << 16);
+            }
+            const auto r0 = __builtin_amdgcn_permlane32_swap(a[0], c[0], false, false);
+            const auto r1 = __builtin_amdgcn_permlane32_swap(a[1], c[1], false, false);
+            *(uint4*)(row + i * 32 + 16 * j + 8 * h2) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
+        }
+}
+// and as fp32 (desta_attn_desc.O_f32)
+template <int D>
+__device__ __forceinline__ void store_row_f32(float* row, const f32x16* acc, int h2) {
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq)
+            *(f32x4*)(row + i * 32 + 8 * rq + 4 * h2) = f32x4{acc[i][4 * rq], acc[i][4 * rq + 1], acc[i][4 * rq + 2], acc[i][4 * rq + 3]};
 }
 
 // ------------------------------------------------------------------------------------------ forward
@@ -159,32 +333,20 @@ __device__ __forceinline__ void attn_work_item(const AttnArgs& p, int nq, int& q
 #endif
 template <int D, bool DROP, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? (D == 64 ? ATTN_FWD64_WAVES : 2) : 2) void attn_fwd_k(AttnArgs p) {
-    constexpr int NT = 64 * NW, QB = 32 * NW;
+    constexpr int QB = 32 * NW;
     __shared__ __attribute__((aligned(16))) char lds[2 * 64 * D * 2];
     char* kimg = lds;
     char* vimg = lds + 64 * D * 2;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h2 = lane >> 5;    // wave index in an SGPR: everything derived from it (q0, mask tests) is scalar -> real branches
-    int qblk, h, b;
-    attn_work_item(p, (p.Sq + QB - 1) / QB, qblk, h, b);
-    const int qb0 = qblk * QB, q0 = qb0 + wave * 32;
-    const int hk = h / (p.Hq / p.Hkv);
-    const int qcol = q0 + (lane & 31);
+    const QWork w = attn_work_item<NW>(p, wave, lane);
+    const int b = w.b, h = w.h, qcol = w.qcol;
 
     const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)min(qcol, p.Sq - 1) * p.q_rs + (long)h * D;
     bf16x8 qf[D / 16];
 #pragma unroll
     for (int ds = 0; ds < D / 16; ++ds) qf[ds] = *(const bf16x8*)(qptr + 16 * ds + 8 * h2);
 
-    const int coff = p.Sk - p.Sq;
-    const int kv_lo = p.kv_start ? max(0, min(p.kv_start[b], p.Sk)) : 0;
-    int kv_hi = p.Sk;
-    if (p.causal) kv_hi = min(p.Sk, min(qb0 + QB - 1, p.Sq - 1) + coff + 1);
-    const int t_lo = kv_lo / 64, t_hi = (kv_hi + 63) / 64;
-    const int q_abs = qcol + coff;
-    const int wave_kmax = p.causal ? min(q0 + 31, p.Sq - 1) + coff : p.Sk - 1;   // last key any row of this wave may see
-
-    const bf16_t* kbase = p.K + (long)b * p.k_bs + (long)hk * D;
-    const bf16_t* vbase = p.V + (long)b * p.v_bs + (long)hk * D;
+    const KeyRange rng = attn_key_range(p, p.causal, w, QB);
 
     f32x16 oacc[D / 32];
 #pragma unroll
@@ -193,19 +355,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (D == 64 ? ATTN_FWD64_WAVES : 2)
         for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
     float m = -INFINITY, l = 0.f;
 
-    // K/V tiles are register-staged PF tiles ahead (PF = 2: two register sets, loop unrolled by two)
-    constexpr int PF = ATTN_FWD_PF;                        // prefetch distance in tiles (1 or 2)
-    stage_t<D, 64, NT> kr0 = {}, vr0 = {}, kr1 = {}, vr1 = {};
-    if (t_lo < t_hi) {
-        kr0 = tile_load<D, 64, NT>(kbase, p.k_rs, t_lo * 64, p.Sk - 1);
-        vr0 = tile_load<D, 64, NT>(vbase, p.v_rs, t_lo * 64, p.Sk - 1);
-    }
-    if (PF == 2 && t_lo + 1 < t_hi) {
-        kr1 = tile_load<D, 64, NT>(kbase, p.k_rs, (t_lo + 1) * 64, p.Sk - 1);
-        vr1 = tile_load<D, 64, NT>(vbase, p.v_rs, (t_lo + 1) * 64, p.Sk - 1);
-    }
     auto compute = [&](const int kt) __attribute__((always_inline)) {
-        if (kt * 64 > wave_kmax) return;                   // wave-uniform: nothing visible in this tile
+        if (kt * 64 > rng.wave_kmax) return;               // wave-uniform: nothing visible in this tile
         f32x16 st[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -228,19 +379,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (D == 64 ? ATTN_FWD64_WAVES : 2)
 #pragma unroll
             for (int ds = 0; ds < NS; ++ds) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kbf[ds], qf[ds], st[1], 0, 0, 0);
         }
-        // masks only on boundary tiles (wave-uniform): ragged Sk, left padding, causal diagonal
-        const bool need_mask = (kt * 64 + 63 >= p.Sk) || (kt * 64 < kv_lo) || (p.causal && kt * 64 + 63 > q0 + coff);
-        if (need_mask) {
-            asm volatile("; boundary tile" ::: "memory");          // keeps this a BRANCH: hipcc otherwise if-converts the 128 compares
-#pragma unroll                                                      // + selects into every tile's straight-line code
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * 64 + kb * 32 + acc_row(r, lane);
-                    const bool ok = key < p.Sk && key >= kv_lo && (!p.causal || key <= q_abs);
-                    st[kb][r] = ok ? st[kb][r] : -INFINITY;
-                }
-        }
+        mask_keys<2>(st, p, p.causal, rng, kt * 64, lane);
         float tmax = -INFINITY;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -302,52 +441,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (D == 64 ? ATTN_FWD64_WAVES : 2)
                     oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr<D>(vimg, kb * 32 + 16 * s, i * 32, lane), pb, oacc[i], 0, 0, 0);
             }
     };
-#define DESTA_KV_STAGE(KT, KR, VR)                                                   \
-    __syncthreads(); /* previous tile's LDS reads are done */                        \
-    asm volatile("; stage " #KR ::: "memory"); /* distinct text: keeps the two halves from being tail-merged */ \
-    if (ATTN_ABL != 1 || (KT) == t_lo) {                                             \
-    tile_store<D, 64, NT>(kimg, KR);                                                     \
-    tile_store<D, 64, NT>(vimg, VR);                                                     \
-    }                                                                                \
-    __syncthreads();                                                                 \
-    if (ATTN_ABL != 2 && (KT) + PF < t_hi) {                                         \
-        KR = tile_load<D, 64, NT>(kbase, p.k_rs, ((KT) + PF) * 64, p.Sk - 1);            \
-        VR = tile_load<D, 64, NT>(vbase, p.v_rs, ((KT) + PF) * 64, p.Sk - 1);            \
-    }
-    for (int kt = t_lo; kt < t_hi; kt += 2) {
-        DESTA_KV_STAGE(kt, kr0, vr0)
-        compute(kt);
-        if (kt + 1 < t_hi) {
-            if constexpr (PF == 2) {
-                DESTA_KV_STAGE(kt + 1, kr1, vr1)
-            } else {
-                DESTA_KV_STAGE(kt + 1, kr0, vr0)
-            }
-            compute(kt + 1);
-        }
-    }
-#undef DESTA_KV_STAGE
+    kv_tile_walk<D, NW, ATTN_FWD_PF, ATTN_ABL>(p, w, rng, kimg, vimg, compute);
 
     if (qcol < p.Sq) {
         const float inv = l > 0.f ? 1.0f / l : 0.f;
-        bf16_t* optr = p.O + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D;
 #pragma unroll
         for (int i = 0; i < D / 32; ++i)
 #pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                u16x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = f2bf(oacc[i][4 * rq + e] * inv);
-                *(u16x4*)(optr + i * 32 + 8 * rq + 4 * h2) = o;
-            }
-        if (p.O32) {
-            float* o32 = p.O32 + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D;
-#pragma unroll
-            for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-                for (int rq = 0; rq < 4; ++rq)
-                    *(f32x4*)(o32 + i * 32 + 8 * rq + 4 * h2) = f32x4{oacc[i][4 * rq] * inv, oacc[i][4 * rq + 1] * inv, oacc[i][4 * rq + 2] * inv, oacc[i][4 * rq + 3] * inv};
-        }
+            for (int r = 0; r < 16; ++r) oacc[i][r] *= inv;
+        store_row_bf16<D>(p.O + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D, oacc, h2);
+        if (p.O32) store_row_f32<D>(p.O32 + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D, oacc, h2);
         if (p.lse && h2 == 0) p.lse[((long)b * p.Hq + h) * p.Sq + qcol] = l > 0.f ? m + log2f(l) : INFINITY;
     }
 }
@@ -406,69 +509,35 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* lo, const char* hi) {
     return __builtin_shufflevector(a, c, 0, 1, 2, 3, 4, 5, 6, 7);            // one register tuple: no element-wise moves
 }
 
-// MINW = 4 (D = 64 only): two 8-wave blocks per CU (<= 128 registers)
-template <int D, bool CAUSAL, int HPB, int MINW = 2, bool STAGGER = false>
-__global__ __launch_bounds__(512, MINW) void attn_fwd8_k(AttnArgs p) {
-    constexpr int NT = 512, RB = 256 / HPB, WPH = RB / 32;         // query rows of a block (per head), waves per head
-    constexpr int TILE = 64 * D * 2;                               // bytes of one 64-key K (or V) image
-    constexpr int SLOT = 2 * TILE, NSLOT = STAGGER ? 3 : 2;        // lockstep: double buffer; staggered: tile t-1's V is still read while t+1 is written
-    constexpr int NCH = 64 * (D / 8) / NT;                         // 16-byte chunks per thread, tile and tensor (2 / 1)
-    __shared__ __attribute__((aligned(16))) char lds[NSLOT * SLOT];   // ring of [K image, V image]
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h2 = lane >> 5;
-    const int G = p.Hq / p.Hkv, nq = (p.Sq + RB - 1) / RB, hgroups = G / HPB, ngrp = p.B * p.Hkv;
-    int g, qblk, hg;
-    {
-        const int id = blockIdx.x, per = nq * hgroups;
-        if ((ngrp & 7) == 0) {
-            const int xcd = id & 7, slot = id >> 3, gpx = ngrp >> 3;
-            if (CAUSAL) {
-                const int r = slot % (hgroups * gpx);
-                qblk = nq - 1 - slot / (hgroups * gpx); hg = r / gpx; g = (r % gpx) * 8 + xcd;
-            } else {
-                const int r = slot % per;
-                g = (slot / per) * 8 + xcd; hg = r / nq; qblk = r % nq;
-            }
-        } else if (CAUSAL) {
-            const int r = id % (hgroups * ngrp);
-            qblk = nq - 1 - id / (hgroups * ngrp); hg = r / ngrp; g = r % ngrp;
-        } else {
-            const int r = id % per;
-            g = id / per; hg = r / nq; qblk = r % nq;
-        }
-    }
-    const int b = g / p.Hkv, hk = g % p.Hkv;
-    const int h = hk * G + hg * HPB + wave / WPH;
-    const int qb0 = qblk * RB, q0 = qb0 + (wave % WPH) * 32;
-    const int qcol = q0 + (lane & 31);
-    const bool wave_on = q0 < p.Sq;                                 // scalar: a wave past the ragged end only helps staging
-
-    const int coff = p.Sk - p.Sq;
-    const int kv_lo = p.kv_start ? max(0, min(p.kv_start[b], p.Sk)) : 0;
-    int kv_hi = p.Sk;
-    if (CAUSAL) kv_hi = min(p.Sk, min(qb0 + RB - 1, p.Sq - 1) + coff + 1);
-    const int t_lo = kv_lo / 64, t_hi = (kv_hi + 63) / 64;
-    const int q_abs = qcol + coff;
-    const int wave_kmax = CAUSAL ? min(q0 + 31, p.Sq - 1) + coff : p.Sk - 1;
-
-    const char* kbase = (const char*)(p.K + (long)b * p.k_bs + (long)hk * D);
-    const char* vbase = (const char*)(p.V + (long)b * p.v_bs + (long)hk * D);
-    // staging: this thread's NCH chunks of a tile: (row r, chunk c) -> byte offset from the tile's first row (32-bit; the tile
-    // base is wave-uniform: scalar base + vector offset loads) and its place in the swizzled LDS image
+// K | V staging stream of the 8-wave kernels: 512 threads move one 64-key tile of both tensors, global -> registers ->
+// a ring slot [K image, V image] of the block's LDS.
+template <int D>
+struct KVStream8 {
+    static constexpr int NT = 512, TILE = 64 * D * 2;              // bytes of one 64-key K (or V) image
+    static constexpr int NCH = 64 * (D / 8) / NT;                  // 16-byte chunks per thread, tile and tensor (2 / 1)
+    const char* kbase; const char* vbase;
+    // this thread's NCH chunks of a tile: (row r, chunk c) -> byte offset from the tile's first row (32-bit; the tile base is
+    // wave-uniform: scalar base + vector offset loads) and its place in the swizzled LDS image
     int srow[NCH], sdst[NCH];
     unsigned ksrc[NCH], vsrc[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int id = i * NT + threadIdx.x, r = id / (D / 8), c = id % (D / 8);
-        srow[i] = r;
-        sdst[i] = img_off<D>(r, c);
-        ksrc[i] = (unsigned)(r * (int)p.k_rs + c * 8) * 2u;
-        vsrc[i] = (unsigned)(r * (int)p.v_rs + c * 8) * 2u;
-    }
     // ONE first-class vector value per tensor (an array that is conditionally re-loaded inside the loop is kept in memory by
     // hipcc — promoted to LDS here: every load was waited for and parked in LDS right behind its issue)
-    typedef typename stage_vec<NCH>::type stage8_t;
-    stage8_t kr = {}, vr = {};
-    auto load_tile = [&](const int kt) __attribute__((always_inline)) {
+    typename stage_vec<NCH>::type kr, vr;
+
+    __device__ __forceinline__ KVStream8(const AttnArgs& p, const QWork& w) : kr{}, vr{} {
+        kbase = (const char*)(p.K + (long)w.b * p.k_bs + (long)w.hk * D);
+        vbase = (const char*)(p.V + (long)w.b * p.v_bs + (long)w.hk * D);
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int id = i * NT + threadIdx.x, r = id / (D / 8), c = id % (D / 8);
+            srow[i] = r;
+            sdst[i] = img_off<D>(r, c);
+            ksrc[i] = (unsigned)(r * (int)p.k_rs + c * 8) * 2u;
+            vsrc[i] = (unsigned)(r * (int)p.v_rs + c * 8) * 2u;
+        }
+    }
+    // global -> registers.  Rows are clamped: the loads are legal even when the block has no tile at all
+    __device__ __forceinline__ void load_tile(const AttnArgs& p, const int kt) {
         const char* kb_ = kbase + (long)kt * 64 * p.k_rs * 2;
         const char* vb_ = vbase + (long)kt * 64 * p.v_rs * 2;
         const bool ragged = kt * 64 + 64 > p.Sk;                    // last tile (or a block without tiles): clamp the rows
@@ -484,47 +553,79 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd8_k(AttnArgs p) {
             kr[4 * i + 0] = a.x; kr[4 * i + 1] = a.y; kr[4 * i + 2] = a.z; kr[4 * i + 3] = a.w;
             vr[4 * i + 0] = c4.x; vr[4 * i + 1] = c4.y; vr[4 * i + 2] = c4.z; vr[4 * i + 3] = c4.w;
         }
-    };
-    auto store_tile = [&](char* slot) __attribute__((always_inline)) {
+    }
+    __device__ __forceinline__ void store_tile(char* slot) const {
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             *(uint4*)(slot + sdst[i]) = make_uint4(kr[4 * i + 0], kr[4 * i + 1], kr[4 * i + 2], kr[4 * i + 3]);
             *(uint4*)(slot + TILE + sdst[i]) = make_uint4(vr[4 * i + 0], vr[4 * i + 1], vr[4 * i + 2], vr[4 * i + 3]);
         }
-    };
+    }
+    // tile kt+1: registers -> its ring slot (last read two barriers ago); then the global loads of tile kt+2
+    __device__ __forceinline__ void advance(const AttnArgs& p, const int kt, const int t_hi, char* slot_next) {
+        if (kt + 1 < t_hi) {
+            store_tile(slot_next);
+            if (kt + 2 < t_hi) load_tile(p, kt + 2);
+        }
+    }
+};
+
+// LDS read addresses inside a ring slot (lane constants; "+v": keep them in registers instead of re-deriving them per tile):
+// kofs: rows 0..31 of an image as the A operand (rows 32..63: + 32 rows, same swizzle); tofs: the transposed operand from the image
+// at byte `tbase` of the slot, rows r0 + 4 h2 + q and + 8 (r0 = multiples of 16: same swizzle)
+template <int D>
+__device__ __forceinline__ void lds_read_offsets(int lane, int tbase, int (&kofs)[D / 16], int (&tofs)[D / 32][2]) {
+    const int h2 = lane >> 5;
+#pragma unroll
+    for (int ds = 0; ds < D / 16; ++ds) {
+        kofs[ds] = img_off<D>(lane & 31, 2 * ds + h2);
+        asm volatile("" : "+v"(kofs[ds]));
+    }
+    const int i16 = lane & 15, gq = (lane >> 4) & 1, qq = i16 >> 2, pp = i16 & 3;
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+        const int c = i * 32 + 16 * gq + 4 * pp;
+        tofs[i][0] = tbase + img_off<D>(4 * h2 + qq, c >> 3) + ((c & 4) << 1);
+        tofs[i][1] = tbase + img_off<D>(4 * h2 + qq + 8, c >> 3) + ((c & 4) << 1);
+        asm volatile("" : "+v"(tofs[i][0]), "+v"(tofs[i][1]));
+    }
+}
+
+// one barrier per tile: LDS traffic of this wave is done; global loads stay in flight (no vmcnt drain)
+__device__ __forceinline__ void attn_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// MINW = 4 (D = 64 only): two 8-wave blocks per CU (<= 128 registers)
+template <int D, bool CAUSAL, int HPB, int MINW = 2, bool STAGGER = false>
+__global__ __launch_bounds__(512, MINW) void attn_fwd8_k(AttnArgs p) {
+    constexpr int RB = 256 / HPB;                                  // query rows of a block (per head)
+    constexpr int TILE = KVStream8<D>::TILE;
+    constexpr int SLOT = 2 * TILE, NSLOT = STAGGER ? 3 : 2;        // lockstep: double buffer; staggered: tile t-1's V is still read while t+1 is written
+    __shared__ __attribute__((aligned(16))) char lds[NSLOT * SLOT];   // ring of [K image, V image]
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h2 = lane >> 5;
+    const QWork w = attn_work_item8<CAUSAL, HPB>(p, wave, lane);
+    const int b = w.b, h = w.h, qcol = w.qcol;
+    const bool wave_on = w.wave_on;
+    const KeyRange rng = attn_key_range(p, CAUSAL, w, RB);
+    const int t_lo = rng.t_lo, t_hi = rng.t_hi;
+    KVStream8<D> kv(p, w);
 
     // prologue, straight-line on purpose: first K / V tile, then the Q fragments; loads return in order, so once the Q
     // fragments are in (the empty asm makes the compiler wait for them HERE) nothing of the prologue is still in flight and
     // the loop's vmcnt bookkeeping covers only the K / V stream (with the Q loads pending at the loop head hipcc makes every
     // tile's S MFMAs wait for vmcnt(3..0), i.e. for the loads of tile t+2 issued half a tile earlier).  Rows are clamped:
     // the loads are legal even when the block has no tile at all.
-    load_tile(t_lo);
+    kv.load_tile(p, t_lo);
     const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)min(qcol, p.Sq - 1) * p.q_rs + (long)h * D;
     bf16x8 qf[D / 16];
 #pragma unroll
     for (int ds = 0; ds < D / 16; ++ds) qf[ds] = *(const bf16x8*)(qptr + 16 * ds + 8 * h2);
 #pragma unroll
     for (int ds = 0; ds < D / 16; ++ds) asm volatile("" :: "v"(qf[ds]));
-    store_tile(lds);
-    load_tile(t_lo + 1);
+    kv.store_tile(lds);
+    kv.load_tile(p, t_lo + 1);
 
-    // LDS read addresses inside a slot (lane constants; "+v": keep them in registers instead of re-deriving them per tile)
-    int kofs[D / 16], vofs[D / 32][2];
-#pragma unroll
-    for (int ds = 0; ds < D / 16; ++ds) {
-        kofs[ds] = img_off<D>(lane & 31, 2 * ds + h2);             // K rows 0..31 (rows 32..63: + 32 rows, same swizzle)
-        asm volatile("" : "+v"(kofs[ds]));
-    }
-    {
-        const int i16 = lane & 15, gq = (lane >> 4) & 1, qq = i16 >> 2, pp = i16 & 3;
-#pragma unroll
-        for (int i = 0; i < D / 32; ++i) {
-            const int c = i * 32 + 16 * gq + 4 * pp;
-            vofs[i][0] = TILE + img_off<D>(4 * h2 + qq, c >> 3) + ((c & 4) << 1);          // V rows r0 + 4 h2 + q (r0 = multiples of 16: same swizzle)
-            vofs[i][1] = TILE + img_off<D>(4 * h2 + qq + 8, c >> 3) + ((c & 4) << 1);
-            asm volatile("" : "+v"(vofs[i][0]), "+v"(vofs[i][1]));
-        }
-    }
+    int kofs[D / 16], vofs[D / 32][2];                              // K rows as the A operand; V^T from the V image
+    lds_read_offsets<D>(lane, TILE, kofs, vofs);
 
     f32x16 oacc[D / 32];
 #pragma unroll
@@ -533,12 +634,11 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd8_k(AttnArgs p) {
         for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
     float m = -INFINITY, l = 0.f;                                   // m: reference in scaled log2 units (may lag the true maximum by <= 2^DEFER); l: this lane's partial sum
     f32x16 st[2];                                                   // S^T of the current tile, then its probabilities (waves 4-7 carry them across the barrier)
-#define ATTN_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")   /* LDS traffic of this wave is done; global loads stay in flight */
-    ATTN_BARRIER();
+    attn_barrier();
 
     // S^T = K Q^T of tile kt (slot base `sb`), boundary masks, deferred-rescale online softmax: st := probabilities
     auto scores = [&](const int kt, const int sb) __attribute__((always_inline)) {
-        if (!(wave_on && kt * 64 <= wave_kmax)) return;             // scalar
+        if (!(wave_on && kt * 64 <= rng.wave_kmax)) return;         // scalar
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -558,18 +658,7 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd8_k(AttnArgs p) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ds = 0; ds < D / 16; ++ds) st[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kbf[ds], qf[ds], st[1], 0, 0, 0);
-        const bool need_mask = (kt * 64 + 63 >= p.Sk) || (kt * 64 < kv_lo) || (CAUSAL && kt * 64 + 63 > q0 + coff);
-        if (need_mask) {
-            asm volatile("; boundary tile" ::: "memory");
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * 64 + kb * 32 + acc_row(r, lane);
-                    const bool ok = key < p.Sk && key >= kv_lo && (!CAUSAL || key <= q_abs);
-                    st[kb][r] = ok ? st[kb][r] : -INFINITY;
-                }
-        }
+        mask_keys<2>(st, p, CAUSAL, rng, kt * 64, lane);
         float tmax = vmax3(st[0][0], st[1][0], st[0][1]);
         tmax = vmax3(tmax, st[1][1], st[0][2]);
 #pragma unroll
@@ -597,7 +686,7 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd8_k(AttnArgs p) {
     };
     // O^T += V^T P^T of tile kt
     auto pv = [&](const int kt, const int sb) __attribute__((always_inline)) {
-        if (!(wave_on && kt * 64 <= wave_kmax)) return;
+        if (!(wave_on && kt * 64 <= rng.wave_kmax)) return;
         int vad[D / 32][2];
 #pragma unroll
         for (int i = 0; i < D / 32; ++i)
@@ -614,69 +703,42 @@ __global__ __launch_bounds__(512, MINW) void attn_fwd8_k(AttnArgs p) {
                         tr_pair(lds + vad[i][0] + (kb * 32 + 16 * s) * D * 2, lds + vad[i][1] + (kb * 32 + 16 * s) * D * 2), pb, oacc[i], 0, 0, 0);
             }
     };
-    // tile kt+1: registers -> its ring slot (last read two barriers ago); then the global loads of tile kt+2
-    auto stage = [&](const int kt, const int sb_next) __attribute__((always_inline)) {
-        if (kt + 1 < t_hi) {
-            store_tile(lds + sb_next);
-            if (kt + 2 < t_hi) load_tile(kt + 2);
-        }
-    };
     auto next_slot = [](int sb) { return sb == (NSLOT - 1) * SLOT ? 0 : sb + SLOT; };
     int sb = 0;                                                     // slot of tile kt (scalar)
     if (!STAGGER || wave < 4) {
         for (int kt = t_lo; kt < t_hi; ++kt) {
             const int sn = next_slot(sb);
             scores(kt, sb);
-            stage(kt, sn);
+            kv.advance(p, kt, t_hi, lds + sn);
             pv(kt, sb);
-            ATTN_BARRIER();
+            attn_barrier();
             sb = sn;
         }
     } else if (t_lo < t_hi) {
         // half a tile behind: the same number of barriers as waves 0-3 (one per tile), P.V of tile kt after the barrier that ends it
         scores(t_lo, sb);
-        stage(t_lo, next_slot(sb));
-        ATTN_BARRIER();
+        kv.advance(p, t_lo, t_hi, lds + next_slot(sb));
+        attn_barrier();
         for (int kt = t_lo; kt + 1 < t_hi; ++kt) {
             const int sn = next_slot(sb);
             pv(kt, sb);
-            stage(kt + 1, next_slot(sn));
+            kv.advance(p, kt + 1, t_hi, lds + next_slot(sn));
             scores(kt + 1, sn);
-            ATTN_BARRIER();
+            attn_barrier();
             sb = sn;
         }
         pv(t_hi - 1, sb);
     }
-#undef ATTN_BARRIER
 
     if (wave_on && qcol < p.Sq) {
         const float lt = swap_halves_sum(l);
         const float inv = lt > 0.f ? 1.0f / lt : 0.f;
-        bf16_t* optr = p.O + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D;
 #pragma unroll
         for (int i = 0; i < D / 32; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                // registers 8j..8j+3: d = 32i + 16j + 4*h2 + e; 8j+4..8j+7: d = 32i + 16j + 8 + 4*h2 + e.  After the exchange a lane
-                // of the lower half holds d = 32i + 16j + 0..7, its partner in the upper half 32i + 16j + 8..15: one 16-byte store each
-                unsigned a[2], c[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    a[e] = (unsigned)f2bf(oacc[i][8 * j + 2 * e] * inv) | ((unsigned)f2bf(oacc[i][8 * j + 2 * e + 1] * inv) << 16);
-                    c[e] = (unsigned)f2bf(oacc[i][8 * j + 4 + 2 * e] * inv) | ((unsigned)f2bf(oacc[i][8 * j + 4 + 2 * e + 1] * inv) << 16);
-                }
-                const auto r0 = __builtin_amdgcn_permlane32_swap(a[0], c[0], false, false);
-                const auto r1 = __builtin_amdgcn_permlane32_swap(a[1], c[1], false, false);
-                *(uint4*)(optr + i * 32 + 16 * j + 8 * h2) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-            }
-        if (p.O32) {
-            float* o32 = p.O32 + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D;
-#pragma unroll
-            for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-                for (int rq = 0; rq < 4; ++rq)
-                    *(f32x4*)(o32 + i * 32 + 8 * rq + 4 * h2) = f32x4{oacc[i][4 * rq] * inv, oacc[i][4 * rq + 1] * inv, oacc[i][4 * rq + 2] * inv, oacc[i][4 * rq + 3] * inv};
-        }
+            for (int r = 0; r < 16; ++r) oacc[i][r] *= inv;
+        store_row_bf16_16B<D>(p.O + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D, oacc, h2);
+        if (p.O32) store_row_f32<D>(p.O32 + (long)b * p.o_bs + (long)qcol * p.o_rs + (long)h * D, oacc, h2);
         if (p.lse && h2 == 0) p.lse[((long)b * p.Hq + h) * p.Sq + qcol] = lt > 0.f ? m + log2f(lt) : INFINITY;
     }
 }
@@ -720,16 +782,13 @@ __global__ __launch_bounds__(256) void attn_delta_k(AttnArgs p, float* __restric
 #endif
 template <int D, bool DROP, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_DQ_BLOCKS : 2) void attn_bwd_dq_k(AttnArgs p) {
-    constexpr int NT = 64 * NW, QB = 32 * NW;
+    constexpr int QB = 32 * NW;
     __shared__ __attribute__((aligned(16))) char lds[2 * 64 * D * 2];
     char* kimg = lds;
     char* vimg = lds + 64 * D * 2;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h2 = lane >> 5;    // wave index in an SGPR: everything derived from it (q0, mask tests) is scalar -> real branches
-    int qblk, h, b;
-    attn_work_item(p, (p.Sq + QB - 1) / QB, qblk, h, b);
-    const int qb0 = qblk * QB, q0 = qb0 + wave * 32;
-    const int hk = h / (p.Hq / p.Hkv);
-    const int qcol = q0 + (lane & 31), qc = min(qcol, p.Sq - 1);
+    const QWork w = attn_work_item<NW>(p, wave, lane);
+    const int b = w.b, h = w.h, qcol = w.qcol, qc = min(qcol, p.Sq - 1);
 
     const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)qc * p.q_rs + (long)h * D;
     const bf16_t* gptr = p.dO + (long)b * p.do_bs + (long)qc * p.do_rs + (long)h * D;
@@ -742,16 +801,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_DQ_BLOCKS : 2) void attn_bw
     const long stat = ((long)b * p.Hq + h) * p.Sq + qc;
     const float lse = p.lse[stat], dlt = p.delta[stat];
 
-    const int coff = p.Sk - p.Sq;
-    const int kv_lo = p.kv_start ? max(0, min(p.kv_start[b], p.Sk)) : 0;
-    int kv_hi = p.Sk;
-    if (p.causal) kv_hi = min(p.Sk, min(qb0 + QB - 1, p.Sq - 1) + coff + 1);
-    const int t_lo = kv_lo / 64, t_hi = (kv_hi + 63) / 64;
-    const int q_abs = qcol + coff;
-    const int wave_kmax = p.causal ? min(q0 + 31, p.Sq - 1) + coff : p.Sk - 1;
-
-    const bf16_t* kbase = p.K + (long)b * p.k_bs + (long)hk * D;
-    const bf16_t* vbase = p.V + (long)b * p.v_bs + (long)hk * D;
+    const KeyRange rng = attn_key_range(p, p.causal, w, QB);
 
     f32x16 dq[D / 32];
 #pragma unroll
@@ -759,19 +809,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_DQ_BLOCKS : 2) void attn_bw
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[i][r] = 0.f;
 
-    // K/V tiles are register-staged PF tiles ahead (PF = 2: two register sets, loop unrolled by two)
-    constexpr int PF = ATTN_DQ_PF;                         // prefetch distance in tiles (1 or 2)
-    stage_t<D, 64, NT> kr0 = {}, vr0 = {}, kr1 = {}, vr1 = {};
-    if (t_lo < t_hi) {
-        kr0 = tile_load<D, 64, NT>(kbase, p.k_rs, t_lo * 64, p.Sk - 1);
-        vr0 = tile_load<D, 64, NT>(vbase, p.v_rs, t_lo * 64, p.Sk - 1);
-    }
-    if (PF == 2 && t_lo + 1 < t_hi) {
-        kr1 = tile_load<D, 64, NT>(kbase, p.k_rs, (t_lo + 1) * 64, p.Sk - 1);
-        vr1 = tile_load<D, 64, NT>(vbase, p.v_rs, (t_lo + 1) * 64, p.Sk - 1);
-    }
     auto compute = [&](const int kt) __attribute__((always_inline)) {
-        if (kt * 64 > wave_kmax) return;
+        if (kt * 64 > rng.wave_kmax) return;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             f32x16 st, dp;
@@ -782,8 +821,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_DQ_BLOCKS : 2) void attn_bw
                 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(kimg, kb * 32, ds, lane), qf[ds], st, 0, 0, 0);
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows<D>(vimg, kb * 32, ds, lane), gf[ds], dp, 0, 0, 0);
             }
-            const bool need_mask = (kt * 64 + kb * 32 + 31 >= p.Sk) || (kt * 64 + kb * 32 < kv_lo) ||
-                                   (p.causal && kt * 64 + kb * 32 + 31 > q0 + coff);
             unsigned keep = 0xffffu;                                          // bit r: probability r of this lane survived dropout
             if constexpr (DROP) {
                 // registers 2j, 2j+1 hold adjacent keys = one element pair = one hash (common.h; Sk even: host check)
@@ -797,15 +834,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_DQ_BLOCKS : 2) void attn_bw
                     keep |= ((hsh >> 16) >= p.drop_thresh ? 1u : 0u) << (r + 1);
                 }
             }
-            if (need_mask) {                                           // boundary tiles only (scalar branch, outside the element loop)
-                asm volatile("; boundary tile" ::: "memory");
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = kt * 64 + kb * 32 + acc_row(r, lane);
-                    const bool ok = key < p.Sk && key >= kv_lo && (!p.causal || key <= q_abs);
-                    st[r] = ok ? st[r] : -INFINITY;                   // exp2(-inf) = 0
-                }
-            }
+            mask_keys<1>(&st, p, p.causal, rng, kt * 64 + kb * 32, lane);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float pv = __builtin_amdgcn_exp2f(fmaf(st[r], p.scale_log2, -lse));
@@ -822,41 +851,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_DQ_BLOCKS : 2) void attn_bw
             }
         }
     };
-#define DESTA_KV_STAGE(KT, KR, VR)                                                   \
-    __syncthreads(); /* previous tile's LDS reads are done */                        \
-    asm volatile("; stage " #KR ::: "memory"); /* distinct text: keeps the two halves from being tail-merged */ \
-    tile_store<D, 64, NT>(kimg, KR);                                                     \
-    tile_store<D, 64, NT>(vimg, VR);                                                     \
-    __syncthreads();                                                                 \
-    if ((KT) + PF < t_hi) {                                                          \
-        KR = tile_load<D, 64, NT>(kbase, p.k_rs, ((KT) + PF) * 64, p.Sk - 1);            \
-        VR = tile_load<D, 64, NT>(vbase, p.v_rs, ((KT) + PF) * 64, p.Sk - 1);            \
-    }
-    for (int kt = t_lo; kt < t_hi; kt += 2) {
-        DESTA_KV_STAGE(kt, kr0, vr0)
-        compute(kt);
-        if (kt + 1 < t_hi) {
-            if constexpr (PF == 2) {
-                DESTA_KV_STAGE(kt + 1, kr1, vr1)
-            } else {
-                DESTA_KV_STAGE(kt + 1, kr0, vr0)
-            }
-            compute(kt + 1);
-        }
-    }
-#undef DESTA_KV_STAGE
-    if (qcol < p.Sq) {
-        bf16_t* optr = p.dQ + (long)b * p.dq_bs + (long)qcol * p.dq_rs + (long)h * D;
-#pragma unroll
-        for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                u16x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = f2bf(dq[i][4 * rq + e]);
-                *(u16x4*)(optr + i * 32 + 8 * rq + 4 * h2) = o;
-            }
-    }
+    kv_tile_walk<D, NW, ATTN_DQ_PF, 0>(p, w, rng, kimg, vimg, compute);
+    if (qcol < p.Sq) store_row_bf16<D>(p.dQ + (long)b * p.dq_bs + (long)qcol * p.dq_rs + (long)h * D, dq, h2);
 }
 
 // ------------------------------------------------------------------------------------------ backward: dQ, 8 waves per block
@@ -869,86 +865,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_DQ_BLOCKS : 2) void attn_bw
 // separate delta launch (0.53 ms per step) is gone.
 template <int D, bool CAUSAL, int HPB>
 __global__ __launch_bounds__(512, 2) void attn_bwd_dq8_k(AttnArgs p, float* __restrict__ delta_out) {
-    constexpr int NT = 512, RB = 256 / HPB, WPH = RB / 32;
-    constexpr int TILE = 64 * D * 2, SLOT = 2 * TILE;
-    constexpr int NCH = 64 * (D / 8) / NT;
+    constexpr int RB = 256 / HPB;
+    constexpr int TILE = KVStream8<D>::TILE, SLOT = 2 * TILE;
     __shared__ __attribute__((aligned(16))) char lds[2 * SLOT];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h2 = lane >> 5;
-    const int G = p.Hq / p.Hkv, nq = (p.Sq + RB - 1) / RB, hgroups = G / HPB, ngrp = p.B * p.Hkv;
-    int g, qblk, hg;
-    {
-        const int id = blockIdx.x, per = nq * hgroups;
-        if ((ngrp & 7) == 0) {
-            const int xcd = id & 7, slot = id >> 3, gpx = ngrp >> 3;
-            if (CAUSAL) {
-                const int r = slot % (hgroups * gpx);
-                qblk = nq - 1 - slot / (hgroups * gpx); hg = r / gpx; g = (r % gpx) * 8 + xcd;
-            } else {
-                const int r = slot % per;
-                g = (slot / per) * 8 + xcd; hg = r / nq; qblk = r % nq;
-            }
-        } else if (CAUSAL) {
-            const int r = id % (hgroups * ngrp);
-            qblk = nq - 1 - id / (hgroups * ngrp); hg = r / ngrp; g = r % ngrp;
-        } else {
-            const int r = id % per;
-            g = id / per; hg = r / nq; qblk = r % nq;
-        }
-    }
-    const int b = g / p.Hkv, hk = g % p.Hkv;
-    const int h = hk * G + hg * HPB + wave / WPH;
-    const int qb0 = qblk * RB, q0 = qb0 + (wave % WPH) * 32;
-    const int qcol = q0 + (lane & 31), qc = min(qcol, p.Sq - 1);
-    const bool wave_on = q0 < p.Sq;
+    const QWork w = attn_work_item8<CAUSAL, HPB>(p, wave, lane);
+    const int b = w.b, h = w.h, qcol = w.qcol, qc = min(qcol, p.Sq - 1);
+    const bool wave_on = w.wave_on;
+    const KeyRange rng = attn_key_range(p, CAUSAL, w, RB);
+    const int t_lo = rng.t_lo, t_hi = rng.t_hi;
+    KVStream8<D> kv(p, w);
 
-    const int coff = p.Sk - p.Sq;
-    const int kv_lo = p.kv_start ? max(0, min(p.kv_start[b], p.Sk)) : 0;
-    int kv_hi = p.Sk;
-    if (CAUSAL) kv_hi = min(p.Sk, min(qb0 + RB - 1, p.Sq - 1) + coff + 1);
-    const int t_lo = kv_lo / 64, t_hi = (kv_hi + 63) / 64;
-    const int q_abs = qcol + coff;
-    const int wave_kmax = CAUSAL ? min(q0 + 31, p.Sq - 1) + coff : p.Sk - 1;
-
-    const char* kbase = (const char*)(p.K + (long)b * p.k_bs + (long)hk * D);
-    const char* vbase = (const char*)(p.V + (long)b * p.v_bs + (long)hk * D);
-    int srow[NCH], sdst[NCH];
-    unsigned ksrc[NCH], vsrc[NCH];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        const int id = i * NT + threadIdx.x, r = id / (D / 8), c = id % (D / 8);
-        srow[i] = r;
-        sdst[i] = img_off<D>(r, c);
-        ksrc[i] = (unsigned)(r * (int)p.k_rs + c * 8) * 2u;
-        vsrc[i] = (unsigned)(r * (int)p.v_rs + c * 8) * 2u;
-    }
-    typedef typename stage_vec<NCH>::type stage8_t;
-    stage8_t kr = {}, vr = {};
-    auto load_tile = [&](const int kt) __attribute__((always_inline)) {
-        const char* kb_ = kbase + (long)kt * 64 * p.k_rs * 2;
-        const char* vb_ = vbase + (long)kt * 64 * p.v_rs * 2;
-        const bool ragged = kt * 64 + 64 > p.Sk;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            unsigned ko = ksrc[i], vo = vsrc[i];
-            if (ragged) {
-                const int rc = max(min(srow[i], p.Sk - 1 - kt * 64), -kt * 64), c = (i * NT + (int)threadIdx.x) % (D / 8);
-                ko = (unsigned)(rc * (int)p.k_rs + c * 8) * 2u;
-                vo = (unsigned)(rc * (int)p.v_rs + c * 8) * 2u;
-            }
-            const uint4 a = *(const uint4*)(kb_ + (long)(int)ko), c4 = *(const uint4*)(vb_ + (long)(int)vo);
-            kr[4 * i + 0] = a.x; kr[4 * i + 1] = a.y; kr[4 * i + 2] = a.z; kr[4 * i + 3] = a.w;
-            vr[4 * i + 0] = c4.x; vr[4 * i + 1] = c4.y; vr[4 * i + 2] = c4.z; vr[4 * i + 3] = c4.w;
-        }
-    };
-    auto store_tile = [&](char* slot) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-            *(uint4*)(slot + sdst[i]) = make_uint4(kr[4 * i + 0], kr[4 * i + 1], kr[4 * i + 2], kr[4 * i + 3]);
-            *(uint4*)(slot + TILE + sdst[i]) = make_uint4(vr[4 * i + 0], vr[4 * i + 1], vr[4 * i + 2], vr[4 * i + 3]);
-        }
-    };
-
-    load_tile(t_lo);
+    // prologue in attn_fwd8_k's order: first K / V tile, then the Q, dO and O fragments and lse, then the wait for them
+    kv.load_tile(p, t_lo);
     const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)qc * p.q_rs + (long)h * D;
     const bf16_t* gptr = p.dO + (long)b * p.do_bs + (long)qc * p.do_rs + (long)h * D;
     const bf16_t* optr = p.O + (long)b * p.o_bs + (long)qc * p.o_rs + (long)h * D;
@@ -969,44 +898,29 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq8_k(AttnArgs p, float* __re
 #pragma unroll
     for (int ds = 0; ds < D / 16; ++ds) asm volatile("" :: "v"(qf[ds]), "v"(gf[ds]));
     asm volatile("" :: "v"(nlse));
-    store_tile(lds);
-    load_tile(t_lo + 1);
+    kv.store_tile(lds);
+    kv.load_tile(p, t_lo + 1);
 
-    int kofs[D / 16], tofs[D / 32][2];
-#pragma unroll
-    for (int ds = 0; ds < D / 16; ++ds) {
-        kofs[ds] = img_off<D>(lane & 31, 2 * ds + h2);
-        asm volatile("" : "+v"(kofs[ds]));
-    }
-    {
-        const int i16 = lane & 15, gq = (lane >> 4) & 1, qq = i16 >> 2, pp = i16 & 3;
-#pragma unroll
-        for (int i = 0; i < D / 32; ++i) {
-            const int c = i * 32 + 16 * gq + 4 * pp;
-            tofs[i][0] = img_off<D>(4 * h2 + qq, c >> 3) + ((c & 4) << 1);           // K^T operand: rows r0 + 4 h2 + q of the K image
-            tofs[i][1] = img_off<D>(4 * h2 + qq + 8, c >> 3) + ((c & 4) << 1);
-            asm volatile("" : "+v"(tofs[i][0]), "+v"(tofs[i][1]));
-        }
-    }
+    int kofs[D / 16], tofs[D / 32][2];                              // K / V rows as the A operand; K^T from the K image
+    lds_read_offsets<D>(lane, 0, kofs, tofs);
     f32x16 dq[D / 32];
 #pragma unroll
     for (int i = 0; i < D / 32; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dq[i][r] = 0.f;
-#define ATTN_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-    ATTN_BARRIER();
+    attn_barrier();
 
     int sb = 0;
     for (int kt = t_lo; kt < t_hi; ++kt) {
         const int sn = SLOT - sb;
-        const bool act = wave_on && kt * 64 <= wave_kmax;
+        const bool act = wave_on && kt * 64 <= rng.wave_kmax;
         if (act) {
             int kad[D / 16];
 #pragma unroll
             for (int ds = 0; ds < D / 16; ++ds) { kad[ds] = kofs[ds] + sb; asm volatile("" : "+v"(kad[ds])); }
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
-                if (CAUSAL && kt * 64 + kb * 32 > wave_kmax) break;                  // upper half of a diagonal tile: masked for every row of the wave
+                if (CAUSAL && kt * 64 + kb * 32 > rng.wave_kmax) break;                  // upper half of a diagonal tile: masked for every row of the wave
                 f32x16 st, dp;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) { st[r] = 0.f; dp[r] = 0.f; }
@@ -1015,17 +929,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq8_k(AttnArgs p, float* __re
                     st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(lds + kad[ds] + kb * 32 * D * 2), qf[ds], st, 0, 0, 0);
                     dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*(const bf16x8*)(lds + kad[ds] + TILE + kb * 32 * D * 2), gf[ds], dp, 0, 0, 0);
                 }
-                const bool need_mask = (kt * 64 + kb * 32 + 31 >= p.Sk) || (kt * 64 + kb * 32 < kv_lo) ||
-                                       (CAUSAL && kt * 64 + kb * 32 + 31 > q0 + coff);
-                if (need_mask) {
-                    asm volatile("; boundary tile" ::: "memory");
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int key = kt * 64 + kb * 32 + acc_row(r, lane);
-                        const bool ok = key < p.Sk && key >= kv_lo && (!CAUSAL || key <= q_abs);
-                        st[r] = ok ? st[r] : -INFINITY;
-                    }
-                }
+                mask_keys<1>(&st, p, CAUSAL, rng, kt * 64 + kb * 32, lane);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float pv = __builtin_amdgcn_exp2f(fmaf(st[r], p.scale_log2, nlse));
@@ -1045,14 +949,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq8_k(AttnArgs p, float* __re
                 }
             }
         }
-        if (kt + 1 < t_hi) {
-            store_tile(lds + sn);
-            if (kt + 2 < t_hi) load_tile(kt + 2);
-        }
-        ATTN_BARRIER();
+        kv.advance(p, kt, t_hi, lds + sn);
+        attn_barrier();
         sb = sn;
     }
-#undef ATTN_BARRIER
 
     if (wave_on && qcol < p.Sq) {
         bf16_t* dqp = p.dQ + (long)b * p.dq_bs + (long)qcol * p.dq_rs + (long)h * D;
@@ -1069,20 +969,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dq8_k(AttnArgs p, float* __re
                     dq[i][4 * jj + 2] = g2 * c4.z + g3 * c4.w; dq[i][4 * jj + 3] = g3 * c4.z - g2 * c4.w;
                 }
         }
-#pragma unroll
-        for (int i = 0; i < D / 32; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                unsigned a[2], c[2];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    a[e] = (unsigned)f2bf(dq[i][8 * j + 2 * e]) | ((unsigned)f2bf(dq[i][8 * j + 2 * e + 1]) << 16);
-                    c[e] = (unsigned)f2bf(dq[i][8 * j + 4 + 2 * e]) | ((unsigned)f2bf(dq[i][8 * j + 4 + 2 * e + 1]) << 16);
-                }
-                const auto r0 = __builtin_amdgcn_permlane32_swap(a[0], c[0], false, false);
-                const auto r1 = __builtin_amdgcn_permlane32_swap(a[1], c[1], false, false);
-                *(uint4*)(dqp + i * 32 + 16 * j + 8 * h2) = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-            }
+        store_row_bf16_16B<D>(dqp, dq, h2);
     }
 }
 
@@ -1948,7 +1835,17 @@ int fill_args(const desta_attn_desc* d, AttnArgs& a) {
 
 }  // namespace
 
-namespace { int g_attn_opt[8] = {1, 0, 0, 0, 1, 0, 0, 0}; }      // [4]: one-pass backward for a single query tile (seq_q <= 64, D = 64)
+namespace {
+int g_attn_opt[8] = {1, 0, 0, 0, 1, 0, 0, 0};                    // [4]: one-pass backward for a single query tile (seq_q <= 64, D = 64)
+// 8-wave blocks (attn_fwd8_k, attn_bwd_dq8_k): hpb heads of one GQA group x 256 / hpb query rows (the heads share the K / V
+// tiles; non-causal: one head) -> the 1-D grid, which attn_work_item8() orders per XCD
+dim3 attn_grid8(const AttnArgs& a, int head_dim, int& hpb) {
+    const int G = a.Hq / a.Hkv;
+    hpb = !a.causal ? 1 : (head_dim == 128 ? (G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1)) : (G % 2 == 0 ? 2 : 1));
+    const int rb = 256 / hpb;
+    return dim3((unsigned)((a.Sq + rb - 1) / rb) * (unsigned)(G / hpb) * (unsigned)(a.B * a.Hkv));
+}
+}  // namespace
 extern "C" int desta_attention_set_option(int which, int value) {
     DESTA_CHECK_ARG(which >= 0 && which < 8, "attention_set_option: unknown option %d", which);
     g_attn_opt[which] = value;
@@ -1962,11 +1859,8 @@ extern "C" int desta_attention_fwd(const desta_attn_desc* d, void* stream) {
     DESTA_CHECK_ARG(d->o_row_stride % 8 == 0 && d->o_batch_stride % 8 == 0 && ((size_t)d->O & 15) == 0,
                     "attention_fwd: O must be 16-byte aligned with row / batch strides that are multiples of 8 elements");
     if (g_attn_opt[0] && !a.drop_thresh && a.Sq >= 128) {
-        // 8-wave blocks: HPB heads of one GQA group x 256 / HPB query rows (the heads share the K / V tiles)
-        const int G = a.Hq / a.Hkv;
-        const int hpb = !a.causal ? 1 : (d->head_dim == 128 ? (G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1)) : (G % 2 == 0 ? 2 : 1));
-        const int rb = 256 / hpb;
-        dim3 g8((unsigned)((a.Sq + rb - 1) / rb) * (unsigned)(G / hpb) * (unsigned)(a.B * a.Hkv));
+        int hpb;
+        const dim3 g8 = attn_grid8(a, d->head_dim, hpb);
         hipStream_t st = (hipStream_t)stream;
         if (d->head_dim == 128) {
             if (!a.causal) hipLaunchKernelGGL((attn_fwd8_k<128, false, 1>), g8, dim3(512), 0, st, a);
@@ -2215,10 +2109,8 @@ extern "C" int desta_attention_bwd(const desta_attn_desc* d, float* workspace, v
     if (g_attn_opt[0] && !g_attn_opt[3] && !a.drop_thresh && !a.O32 && a.Sq >= 128 && d->dq_row_stride % 8 == 0 && d->dq_batch_stride % 8 == 0 &&
         ((size_t)d->dQ & 15) == 0) {
         // 8-wave dQ kernel (computes delta itself and leaves it in the workspace), then dK / dV on the same stream
-        const int G = a.Hq / a.Hkv;
-        const int hpb = !a.causal ? 1 : (d->head_dim == 128 ? (G % 4 == 0 ? 4 : (G % 2 == 0 ? 2 : 1)) : (G % 2 == 0 ? 2 : 1));
-        const int rb = 256 / hpb;
-        dim3 g8((unsigned)((a.Sq + rb - 1) / rb) * (unsigned)(G / hpb) * (unsigned)(a.B * a.Hkv));
+        int hpb;
+        const dim3 g8 = attn_grid8(a, d->head_dim, hpb);
         // (the 8-wave dQ kernel on a side stream beside dK / dV, with delta by its own launch again, measured equal in the step:
         // 168.41 / 169.16 vs 168.54 / 169.16 ms in alternating runs on one box; removed)
         if (d->head_dim == 128) {

@@ -31,22 +31,22 @@ the bound collapses to "exactly 0".
 
 `emulate()` is the same computation in float64 with a bf16 rounding at each point where the kernels round.  Rounding points,
 by line of csrc/attention.hip (acc_frag, :116-121, is the fp32 -> bf16 conversion of an accumulator into an MFMA operand):
-  forward, 4 waves (attn_fwd_k)         P = exp2(s - m), m the RUNNING maximum after the current 64-key tile, unnormalised: :299
-                                        O = acc / l (l = sum of the unrounded P): :340;  O_f32 copy unrounded: :349;  lse fp32: :351
+  forward, 4 waves (attn_fwd_k)         P = exp2(s - m), m the RUNNING maximum after the current 64-key tile, unnormalised: :438
+                                        O = acc / l (l = sum of the unrounded P): :451, rounded in store_row_bf16, :288;  O_f32 copy unrounded: :453;  lse fp32: :454
   forward, 8 waves (attn_fwd8_k)        P against a reference that moves only when a tile maximum of the wave exceeds it by
-                                        more than 2^6 (:579-588), unnormalised: :610;  O: :665-666;  O_f32: :678;  lse: :680.
+                                        more than 2^6 (:668-677), unnormalised: :699;  O: :739, rounded in store_row_bf16_16B, :304-305;  O_f32: :741;  lse: :742.
                                         OTHER values are rounded than in the 4-wave kernel (the same p against another power-of-two-
                                         free reference), independently of it: its own emulation flag, `fwd8`
-  delta (attn_delta_k)                  fp32 sum of dO * O from the bf16 O (:705) or from O_f32 (:701): no rounding of its own
-  dQ, 4 waves (attn_bwd_dq_k)           P = exp2(s - lse) kept in fp32; dS = P (dP - delta) scale: :818;  dQ: :856
-  dQ, 8 waves (attn_bwd_dq8_k)          delta formed in the kernel from the bf16 O in fp32 (:963-967): the SAME values as
-                                        attn_delta_k up to summation order, so no flag of its own;  dS: :1041;  dQ: :1079-1080
-  dK / dV (attn_bwd_dkdv_k)             P = exp2(s - lse), NORMALISED, for dV and dS for dK: :1247;  dK, dV: :1296 / :1313
-  one query tile (attn_bwd_q64_k)       dS: :1464-1465 (the LDS image read by the dQ MFMAs) and :1470 (same values); P: :1470;
-                                        dK, dV: :1507 / :1527;  the per-chunk dQ partials stay fp32 (:1541-1547) and are summed
-                                        in fp32 before the ONE rounding of attn_dq_sum_k, :1604: no rounding point beyond the
+  delta (attn_delta_k)                  fp32 sum of dO * O from the bf16 O (:767) or from O_f32 (:763): no rounding of its own
+  dQ, 4 waves (attn_bwd_dq_k)           P = exp2(s - lse) kept in fp32; dS = P (dP - delta) scale: :847;  dQ: :855 (store_row_bf16)
+  dQ, 8 waves (attn_bwd_dq8_k)          delta formed in the kernel from the bf16 O in fp32 (:892-896): the SAME values as
+                                        attn_delta_k up to summation order, so no flag of its own;  dS: :945;  dQ: :972 (store_row_bf16_16B)
+  dK / dV (attn_bwd_dkdv_k)             P = exp2(s - lse), NORMALISED, for dV and dS for dK: :1134;  dK, dV: :1183 / :1200
+  one query tile (attn_bwd_q64_k)       dS: :1351-1352 (the LDS image read by the dQ MFMAs) and :1357 (same values); P: :1357;
+                                        dK, dV: :1394 / :1414;  the per-chunk dQ partials stay fp32 (:1428-1434) and are summed
+                                        in fp32 before the ONE rounding of attn_dq_sum_k, :1491: no rounding point beyond the
                                         two-kernel path's, so no flag of its own either
-  bias sums (attn_bwd_q64_k, TR)        fp32 sums of the UNROUNDED dK / dV accumulators: :1498
+  bias sums (attn_bwd_q64_k, TR)        fp32 sums of the UNROUNDED dK / dV accumulators: :1385
 The emulation flags are therefore `o_f32` (delta from the unrounded output) and `fwd8` (the 8-wave forward's deferred
 reference; every backward path takes O and so delta from the forward that ran).  Not emulated (the GPU test's factor 2 is for
 these): fp32 accumulation order, the exp2 approximation, lse stored in fp32.
@@ -191,7 +191,7 @@ def emulate(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False, mutati
     s2m = torch.nn.functional.pad(s2.masked_fill(~ok, float("-inf")), (0, nt * 64 - Sk), value=float("-inf"))
     tmax = s2m.view(B, Hq, Sq, nt, 64).amax(-1)
     if fwd8:
-        # attention.hip:573-588: a wave (32 query rows) moves EVERY row's reference to max(reference, tile maximum) when some row's
+        # attention.hip:662-677: a wave (32 query rows) moves EVERY row's reference to max(reference, tile maximum) when some row's
         # tile maximum exceeds its reference by more than 2^6, and leaves all of them where they are otherwise
         nw = (Sq + 31) // 32
         mref, refs = torch.full((B, Hq, Sq), float("-inf"), dtype=torch.float64), []

@@ -481,12 +481,14 @@ def test_attention_fp32_output_copy_feeds_delta(hip):
     assert errs[True] < 1.5e-2 and errs[True] <= errs[False] * 1.05
 
 
-@pytest.mark.parametrize("hd,smajor", [(128, True), (64, False)])
-def test_rope_in_gemm_epilogue_and_attention_backward(hip, hd, smajor):
-    """desta_gemm_desc.rope_*: the q|k|v projection with permuted q / k weight rows leaves q, k rotated (adjacent pairs) —
-    equal, after undoing the permutation, to HF's apply_rotary_pos_emb on the plain projection.  desta_attn_desc.rope_cos_sin:
-    the backward returns gradients of the projection OUTPUTS (checked against torch autograd through rotate + attention)."""
-    B, S, Hq, Hkv, K = 2, 160, 4, 2, 256
+ROPE_SHAPE = (2, 160, 4, 2, 256)                                            # B, S, Hq, Hkv, K
+ROPE_CASES = [(128, True), (64, False)]                                      # head dim, position-major rows
+
+
+def rope_projection(hip, hd, smajor):
+    """Operands of test_rope_in_gemm_epilogue_and_attention_backward and the rotated q|k|v projection `out` (device) ->
+    (generator, x, W, fr [S, hd/2], cs_il [S, hd/2, 2], pos, out)"""
+    B, S, Hq, Hkv, K = ROPE_SHAPE
     g = torch.Generator().manual_seed(hd)
     nqk, w = (Hq + Hkv) * hd, (Hq + 2 * Hkv) * hd
     x = bf(torch.randn(B * S, K, generator=g))
@@ -499,6 +501,36 @@ def test_rope_in_gemm_epilogue_and_attention_backward(hip, hd, smajor):
     Wil[:nqk] = W[:nqk].view(Hq + Hkv, 2, hd // 2, K).transpose(1, 2).reshape(nqk, K)
     out = torch.empty(B * S, w, dtype=torch.bfloat16, device="cuda")
     hip.gemm(x.cuda(), Wil.cuda(), out, B * S, w, K, rope=(cs_il.cuda(), pos.cuda(), nqk, hd))
+    return g, x, W, fr, cs_il, pos, out
+
+
+def rope_attention(hip, out, cs_il, do, hd, smajor, fill=0.0):
+    """Causal attention on the rotated projections `out` and its backward to the projection outputs -> (o, lse, dqkv), device
+    buffers that start as `fill`"""
+    B, S, Hq, Hkv, K = ROPE_SHAPE
+    nqk, w = (Hq + Hkv) * hd, (Hq + 2 * Hkv) * hd
+    rs, bs = (B * w, w) if smajor else (w, S * w)
+    o = torch.full((B * S, Hq * hd), fill, dtype=torch.bfloat16, device="cuda")
+    lse = torch.full((B, Hq, S), fill, device="cuda")
+    d = hip.attn_desc(out, out, out, o, lse, batch=B, hq=Hq, hkv=Hkv, sq=S, sk=S, hd=hd, scale=hd ** -0.5, causal=True,
+                      q_off=0, k_off=Hq * hd, v_off=nqk, q_rs=rs, k_rs=rs, v_rs=rs, o_rs=rs // w * Hq * hd,
+                      q_bs=bs, k_bs=bs, v_bs=bs, o_bs=bs // w * Hq * hd)
+    hip.attention_fwd(d)
+    dqkv = torch.full((B * S, w), fill, dtype=torch.bfloat16, device="cuda")
+    ors, obs = rs // w * Hq * hd, bs // w * Hq * hd
+    hip.attention_bwd(d, do.cuda(), dqkv, dqkv, dqkv, dq_off=0, dk_off=Hq * hd, dv_off=nqk, do_rs=ors, dq_rs=rs, dk_rs=rs, dv_rs=rs,
+                      do_bs=obs, dq_bs=bs, dk_bs=bs, dv_bs=bs, rope_cos_sin=cs_il.cuda())
+    return o, lse, dqkv
+
+
+@pytest.mark.parametrize("hd,smajor", ROPE_CASES)
+def test_rope_in_gemm_epilogue_and_attention_backward(hip, hd, smajor):
+    """desta_gemm_desc.rope_*: the q|k|v projection with permuted q / k weight rows leaves q, k rotated (adjacent pairs) —
+    equal, after undoing the permutation, to HF's apply_rotary_pos_emb on the plain projection.  desta_attn_desc.rope_cos_sin:
+    the backward returns gradients of the projection OUTPUTS (checked against torch autograd through rotate + attention)."""
+    B, S, Hq, Hkv, K = ROPE_SHAPE
+    nqk, w = (Hq + Hkv) * hd, (Hq + 2 * Hkv) * hd
+    g, x, W, fr, cs_il, pos, out = rope_projection(hip, hd, smajor)
     # reference: plain projection (fp32), HF rotation, then the same permutation of the head dim
     y = (x.float() @ W.float().T).requires_grad_(True)
     yh = y[:, :nqk].view(B * S, Hq + Hkv, hd)
@@ -510,18 +542,8 @@ def test_rope_in_gemm_epilogue_and_attention_backward(hip, hd, smajor):
     assert rel_err(out[:, :nqk].float().cpu(), ye_il.detach()) < 6e-3
     assert rel_err(out[:, nqk:].float().cpu(), y[:, nqk:].detach()) < 6e-3
     # attention on the rotated projections, backward to the projection outputs
-    rs, bs = (B * w, w) if smajor else (w, S * w)
-    o = torch.zeros(B * S, Hq * hd, dtype=torch.bfloat16, device="cuda")
-    lse = torch.zeros(B, Hq, S, device="cuda")
-    d = hip.attn_desc(out, out, out, o, lse, batch=B, hq=Hq, hkv=Hkv, sq=S, sk=S, hd=hd, scale=hd ** -0.5, causal=True,
-                      q_off=0, k_off=Hq * hd, v_off=nqk, q_rs=rs, k_rs=rs, v_rs=rs, o_rs=rs // w * Hq * hd,
-                      q_bs=bs, k_bs=bs, v_bs=bs, o_bs=bs // w * Hq * hd)
-    hip.attention_fwd(d)
     do = bf(torch.randn(B * S, Hq * hd, generator=g))
-    dqkv = torch.zeros(B * S, w, dtype=torch.bfloat16, device="cuda")
-    ors, obs = rs // w * Hq * hd, bs // w * Hq * hd
-    hip.attention_bwd(d, do.cuda(), dqkv, dqkv, dqkv, dq_off=0, dk_off=Hq * hd, dv_off=nqk, do_rs=ors, dq_rs=rs, dk_rs=rs, dv_rs=rs,
-                      do_bs=obs, dq_bs=bs, dk_bs=bs, dv_bs=bs, rope_cos_sin=cs_il.cuda())
+    o, lse, dqkv = rope_attention(hip, out, cs_il, do, hd, smajor)
     # torch: rows -> [B, S] order, rotate, attention, autograd back to y
     idx = (torch.arange(S)[None, :] * B + torch.arange(B)[:, None]).reshape(-1) if smajor else torch.arange(B * S)
     qe = ye[idx][:, :Hq].view(B, S, Hq, hd)
@@ -591,13 +613,23 @@ def test_dropout_mask_gemm_epilogue_and_backward_kernel(hip):
     torch.testing.assert_close(y.float().cpu(), x.float() * mask / (1 - pdrop), rtol=8e-3, atol=1e-6)
 
 
-@pytest.mark.parametrize("Sq,Sk", [(64, 64), (64, 200), (64, 1500), (40, 520)])
-def test_attention_dropout_fwd_bwd(hip, Sq, Sk):
-    B, H, D, pdrop, seed = 2, 3, 64, 0.1, (3 << 40) | 77
+DROPOUT_SHAPES = [(64, 64), (64, 200), (64, 1500), (40, 520)]                # Sq, Sk
+DROPOUT_P, DROPOUT_SEED = 0.1, (3 << 40) | 77
+
+
+def dropout_operands(Sq, Sk, B, H, D):
+    """q [B * Sq, H * D], k|v [B * Sk, 2 * H * D] and dO of test_attention_dropout_fwd_bwd (CPU, bf16)"""
     g = torch.Generator().manual_seed(Sq + Sk)
     qb = bf(torch.randn(B * Sq, H * D, generator=g))
     kvb = bf(torch.randn(B * Sk, 2 * H * D, generator=g))
     do = bf(torch.randn(B * Sq, H * D, generator=g))
+    return qb, kvb, do
+
+
+@pytest.mark.parametrize("Sq,Sk", DROPOUT_SHAPES)
+def test_attention_dropout_fwd_bwd(hip, Sq, Sk):
+    B, H, D, pdrop, seed = 2, 3, 64, DROPOUT_P, DROPOUT_SEED
+    qb, kvb, do = dropout_operands(Sq, Sk, B, H, D)
     mask = hip.dropout_mask(seed, B * H * Sq * Sk, pdrop).float().cpu().view(B, H, Sq, Sk)
     q = qb.float().view(B, Sq, H, D).clone().requires_grad_(True)
     k = kvb[:, :H * D].float().reshape(B, Sk, H, D).clone().requires_grad_(True)
