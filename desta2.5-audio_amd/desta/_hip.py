@@ -769,6 +769,38 @@ def sample(logits, ld, rows, cols, out, *, do_sample=True, temperature=1.0, top_
           "desta_sample_bf16")
 
 
+_spec_draft = _sig("desta_spec_ngram_draft", vp, i64, i32, i32, vp, i32, i32, i32, vp, vp)
+_spec_accept = _sig("desta_spec_accept", vp, vp, i32, i32, vp, vp, i32, i64, i32, vp, i64, i32, vp, vp, vp, i64, i32, vp)
+SPEC_DRAFT_CALLS = 0               # prompt-lookup launches issued by this process
+SPEC_ACCEPT_CALLS = 0              # acceptance launches issued by this process (one per verify step)
+
+
+def spec_ngram_draft(hist, hist_len, row_start, k, n_max, n_min, draft):
+    """Prompt lookup per row of the int64 history hist[:, :hist_len]: draft[b] = the k tokens behind the latest earlier occurrence
+    (start >= row_start[b]) of the row's last n tokens, n from n_max down to n_min; -1 where there is none (desta_spec_ngram_draft)."""
+    global SPEC_DRAFT_CALLS
+    assert hist.dtype == torch.int64 and draft.dtype == torch.int64 and hist.stride(1) == 1 and draft.is_contiguous()
+    assert row_start is None or (row_start.dtype == torch.int32 and row_start.numel() >= hist.shape[0])
+    check(_spec_draft(p(hist), hist.stride(0), hist.shape[0], hist_len, p(row_start), k, n_max, n_min, p(draft), stream()),
+          "desta_spec_ngram_draft")
+    SPEC_DRAFT_CALLS += 1
+
+
+def spec_accept(pred, inp, k, finished, eos, pad, max_take, out, n, next_tok, taken, hist=None, hist_col=0):
+    """Lockstep acceptance of one verify step (desta_spec_accept): pred / inp int64 [B, k + 1] contiguous, finished bool or uint8
+    [B], eos int64 [n_eos] or None, out int64 [B, >= n + max_take] written at columns [n, n + a), next_tok int64 [B], taken int32
+    [1] = a; hist (optional, int64 [B, >= hist_col + max_take]) receives the same tokens at column hist_col."""
+    global SPEC_ACCEPT_CALLS
+    B = pred.numel() // (k + 1)
+    assert pred.dtype == inp.dtype == out.dtype == next_tok.dtype == torch.int64 and taken.dtype == torch.int32
+    assert pred.is_contiguous() and inp.is_contiguous() and out.stride(1) == 1 and finished.element_size() == 1 and finished.numel() >= B
+    assert hist is None or (hist.dtype == torch.int64 and hist.stride(1) == 1)
+    check(_spec_accept(p(pred), p(inp), B, k, p(finished), p(eos), 0 if eos is None else int(eos.numel()), int(pad), max_take, p(out),
+                       out.stride(0), n, p(next_tok), p(taken), p(hist), 0 if hist is None else hist.stride(0), hist_col, stream()),
+          "desta_spec_accept")
+    SPEC_ACCEPT_CALLS += 1
+
+
 # ----------------------------------------------------------------------------- data-parallel exchange without torch.distributed
 class CommUniqueId(C.Structure):
     _fields_ = [("internal", C.c_char * 128)]

@@ -433,6 +433,18 @@ def check_prefill_chunk(n) -> None:
         raise ValueError(f"prefill_chunk must be None or an int >= {PREFILL_CHUNK_MIN}, got {n!r}")
 
 
+SPECULATIVE_MAX = 7                                 # draft tokens per verify step (desta_spec_accept)
+SPEC_NGRAM_MAX, SPEC_NGRAM_MIN = 3, 1               # suffix lengths the prompt lookup tries, longest first
+
+
+def check_speculative_arg(k) -> None:
+    """`set_speculative`: None or 0 (off) or the number of draft tokens per verify step, an int in 1..SPECULATIVE_MAX."""
+    if k is None:
+        return
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= SPECULATIVE_MAX:
+        raise ValueError(f"speculative must be None, 0 or an int in 1..{SPECULATIVE_MAX} draft tokens per step, got {k!r}")
+
+
 def prefill_chunks(S: int, C: int) -> List[Tuple[int, int]]:
     """Position ranges [c0, c1) of the chunked prompt pass: [0, S) in order, C positions each, a ragged last one."""
     return [(c0, min(c0 + C, S)) for c0 in range(0, S, C)]
@@ -1545,6 +1557,22 @@ class CausalLMHIP:
         self.kv_cache = self.kv_scale = None
         self.prefill_chunk = None                   # `set_prefill_chunk`: positions per chunk of generate()'s lean prompt pass; None = `forward`
         self.kv_stage = self._pf = None
+        self.speculative = None                     # `set_speculative`: draft tokens per verify step of greedy generate(); None = one token per step
+        self._spec = None
+        self.spec_stats = None
+
+    def set_speculative(self, k: Optional[int]) -> None:
+        """Greedy generate(): None or 0 (default) = one token per sequence per pass over the weights; an int k in 1..7 = draft and
+        verify: k tokens proposed by looking the row's last tokens up in its own prompt and output (`H.spec_ngram_draft`), all k + 1
+        rows per sequence checked by ONE pass (`verify_step`), and the longest run every unfinished row agrees on is emitted
+        (`H.spec_accept`; acceptance is in lockstep, so the cache keeps one length).  The tokens are those of the plain loop up to
+        the rounding of a different row count.  Sampling, a repetition penalty, `logprobs`, `forced_tokens`, a `layer_hook`
+        (ORCA), the FP8 KV cache and B * (k + 1) > H.DECODE_MAX_ROWS run the plain loop; `spec_stats` says which ran and why."""
+        check_speculative_arg(k)
+        k = k or None
+        if k != getattr(self, "speculative", None):                           # the verify buffers go with the setting
+            self._spec = None
+        self.speculative = k
 
     def set_prefill_chunk(self, n: Optional[int]) -> None:
         """Prompt pass of generate(): None (default) = the training `forward` with its per-layer save set; an int >= 16 = the
@@ -2020,12 +2048,171 @@ class CausalLMHIP:
         proj(self.g_x, self.norm, self.head, self.head8 if fp8 else None, self.g_logits, self.V, ldc=self.Vp)
         return self.g_logits
 
+    # -- draft-and-verify greedy decoding (`set_speculative`): k + 1 rows per sequence through one pass over the weights ---------
+    def _spec_alloc(self, B: int, k: int) -> dict:
+        """Buffers of `verify_step` for M = B * (k + 1) rows (batch-major, k + 1 rows per sequence) and the loop's integer state."""
+        sp = self._spec
+        if sp is not None and sp["key"] == (B, k):
+            return sp
+        self._spec = sp = None                                               # free the old set before the new one is made
+        h, dev, w = self.h, self.dev, k + 1
+        M = B * w
+
+        def b16(*s):
+            return torch.empty(*s, dtype=BF16, device=dev)
+
+        def i64(*s):
+            return torch.zeros(*s, dtype=torch.int64, device=dev)
+        self._spec = sp = dict(key=(B, k), x=b16(M, h), xm=b16(M, h), hb=b16(M, h), qkv=b16(M, self.qkvw), att=b16(M, self.hq * self.hd),
+                               act=b16(M, self.I), r=torch.empty(M, dtype=F32, device=dev), lse=torch.empty(B, self.hq, w, dtype=F32, device=dev),
+                               logits=torch.zeros(M, self.Vp, dtype=BF16, device=dev), pred=i64(B, w), inp=i64(B, w), draft=i64(B, k),
+                               taken=torch.zeros(1, dtype=torch.int32, device=dev), taken_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
+                               event=torch.cuda.Event())
+        return sp
+
+    def verify_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, pos_shift: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """k + 1 tokens per sequence in one pass: `tokens` [B, k + 1] (ids >= 0; column 0 the last emitted token, columns 1..k the
+        drafts), row j of a sequence sits at cache slot cur + j.  Returns logits [B * (k + 1), Vp] (batch-major): row j predicts
+        slot cur + j + 1 GIVEN the chunk's tokens in front of it.  `decode_step`'s kernels and weight forms, chosen by the row
+        count M = B * (k + 1) (at most H.DECODE_MAX_ROWS); the chunk's rotated K | V go to slots [cur, cur + k] of the bf16 cache
+        and the chunk attends slots [kv_start, cur + k] through the forward kernel under the mask "key <= query + (seq_k - seq_q)",
+        the descriptor of `prefill`.  Only slots in front of the next step's `cur` are ever trusted: the slots at or behind it
+        hold drafts that were not accepted, and the next chunk rewrites them (its slot0 is the new `cur`, its width k + 1) before
+        its attention, or any later one, reads them."""
+        c, h = self.c, self.h
+        B, w = tokens.shape
+        M = B * w
+        assert self._gen_shape[0] == B and self._gen_kind == "bf16" and M <= H.DECODE_MAX_ROWS and cur + w <= self._gen_shape[1]
+        sp = self._spec_alloc(B, w - 1)
+        Smax, kvw, aw = self._gen_shape[1], self.kvw, self.hq * self.hd
+        scale = self.hd ** -0.5
+        x, xm, hb, qkv, att, act, r, logits = (sp[n] for n in ("x", "xm", "hb", "qkv", "att", "act", "r", "logits"))
+        H.embed_gather(self.embed, None, tokens.reshape(-1).to(torch.int32), M, h, x)
+        if pos_shift is None:
+            pos_shift = (cur - kv_start).to(torch.int32).contiguous()        # position of the chunk's row j: cur + j - left pad
+        fuse = H.rms_fusable(M, h)
+
+        fp8 = self.decode_weights == "fp8"
+        if fp8:
+            self._fp8_decode_weights()
+
+        def mm(xin, w_, w8, out, N, K, wide=M > 16, **kw):   # `decode_step`'s choice, by M
+            if wide:
+                H.gemm_wide(xin, w_ if w8 is None else w8[0], out, M, N, K, scale=None if w8 is None else w8[1], **kw)
+            elif w8 is not None:
+                H.gemm_w8(xin, w8[0], w8[1], out, M, N, K, **kw)
+            else:
+                H.gemm(xin, w_, out, M, N, K, **kw)
+
+        def proj(xin, nw, w_, w8, out, N, **kw):
+            if fuse:
+                mm(xin, w_, w8, out, N, h, a_rms_weight=nw, a_rms_eps=c.rms_norm_eps, **kw)
+            else:
+                H.rmsnorm_fwd(xin, nw, c.rms_norm_eps, hb, r)
+                mm(hb, w_, w8, out, N, h, **kw)
+        for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
+            q8 = ly["q8"] if fp8 else {}
+            if self.lora is None:
+                proj(x, ly["n1"], ly["wqkv"], q8.get("wqkv"), qkv, self.qkvw)
+            else:
+                proj(x, ly["n1"], self._lora_merged(li), None, qkv, self.qkvw, wide=False)
+            self._kv_append(li, ly, qkv, M, w, pos_shift, cur)
+            H.attention_fwd(H.attn_desc(qkv, cache, cache, att, sp["lse"], batch=B, hq=self.hq, hkv=self.hkv, sq=w, sk=cur + w, hd=self.hd,
+                                        scale=scale, causal=True, kv_start=kv_start, q_off=0, k_off=0, v_off=self.hkv * self.hd,
+                                        q_rs=self.qkvw, k_rs=kvw, v_rs=kvw, o_rs=aw, k_bs=Smax * kvw, v_bs=Smax * kvw))
+            mm(att, ly["wo"], q8.get("wo"), xm, h, aw, residual=x)
+            proj(xm, ly["n2"], ly["wgu"], q8.get("wgu"), act, self.I, act=4)
+            mm(act, ly["wd"], q8.get("wd"), x, h, self.I, residual=xm)
+        proj(x, self.norm, self.head, self.head8 if fp8 else None, logits, self.V, ldc=self.Vp)
+        return logits
+
+    def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook) -> Optional[str]:
+        """Why a call with speculation on runs the plain loop all the same; None when it does not."""
+        if do_sample:
+            return "do_sample"
+        if use_pen:
+            return "repetition_penalty"
+        if logprobs is not None:
+            return "logprobs"
+        if forced_tokens is not None:
+            return "forced_tokens"
+        if layer_hook is not None:
+            return "layer_hook"
+        if self.kv_cache_kind == "fp8":
+            return "fp8 kv cache"
+        if B * (k + 1) > H.DECODE_MAX_ROWS:
+            return f"B * (k + 1) = {B * (k + 1)} rows > {H.DECODE_MAX_ROWS}"
+        return None
+
+    def _speculative_loop(self, logits, B: int, S: int, k: int, kv_start, T: int, pad_token_id: int, eos_token_ids, collect_logits: bool,
+                          draft_tokens, lookup_ids):
+        """The decode loop of `generate_greedy` with k drafts per step.  Token 0 is the prompt pass's; then, with n tokens emitted
+        and the last of them (not yet in the cache) due at slot cur = S + n - 1: draft -> `verify_step` on [last, drafts] ->
+        argmax of all M rows -> `H.spec_accept`, which emits a >= 1 tokens for every row (the run all unfinished rows accept, the
+        correction behind it included) and hands back a through a pinned int32: ONE host wait per verify step."""
+        dev, w = self.dev, k + 1
+        sp = self._spec_alloc(B, k)
+        pred, inp, draft, taken, taken_host, event = (sp[n] for n in ("pred", "inp", "draft", "taken", "taken_host", "event"))
+        out = torch.full((B, T), int(pad_token_id), dtype=torch.int64, device=dev)
+        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
+        hist = row_start = None
+        P = 0
+        if draft_tokens is not None:                                         # the proposal for emitted position t, -1 = none
+            props = torch.full((B, T + k), -1, dtype=torch.int64, device=dev)
+            props[:, :T] = draft_tokens.to(dev, torch.int64)[:, :T]
+        else:                                                                # lookup history: the prompt's ids (-1 = never matches), then the output
+            P = 0 if lookup_ids is None else int(lookup_ids.shape[1])
+            hist = torch.full((B, P + T), -1, dtype=torch.int64, device=dev)
+            if P:
+                hist[:, :P] = lookup_ids.to(dev, torch.int64)
+            row_start = kv_start if P else torch.zeros(B, dtype=torch.int32, device=dev)
+        steps_logits = [logits[:, :self.V].clone()] if collect_logits else None
+        H.argmax_bf16(logits, self.Vp, B, self.V, self.g_next)
+        out[:, 0] = self.g_next
+        if hist is not None:
+            hist[:, P] = self.g_next
+        if eos is not None:
+            finished |= (self.g_next.unsqueeze(1) == eos.unsqueeze(0)).any(dim=1)
+        n, steps = 1, 0
+        while n < T:                                                         # once every row is finished a = T - n: no early-exit check
+            cur = S + n - 1
+            if hist is None:
+                draft.copy_(props[:, n:n + k])
+            else:
+                H.spec_ngram_draft(hist, P + n, row_start, k, SPEC_NGRAM_MAX, SPEC_NGRAM_MIN, draft)
+            inp[:, 0] = self.g_next
+            inp[:, 1:] = draft
+            vl = self.verify_step(inp.clamp_min(0), cur, kv_start)          # a -1 draft is embedded as token 0 and can never be accepted
+            H.argmax_bf16(vl, self.Vp, B * w, self.V, pred)
+            H.spec_accept(pred, inp, k, finished, eos, pad_token_id, T - n, out, n, self.g_next, taken, hist=hist, hist_col=P + n)
+            taken_host.copy_(taken, non_blocking=True)
+            event.record()
+            if collect_logits:
+                rows = vl.view(B, w, self.Vp)[:, :, :self.V].transpose(0, 1).clone()      # [k + 1, B, V], before the wait
+            event.synchronize()
+            a = int(taken_host[0])
+            if collect_logits:
+                steps_logits.extend(rows[:min(a, w)])                        # a > k + 1 only once every row is finished: trimmed below
+            n += a
+            steps += 1
+        n_new = n
+        if eos is not None and n_new > 1:                                    # trim columns after every sequence finished
+            hit = (out.unsqueeze(2) == eos.view(1, 1, -1)).any(dim=2)
+            done_at = hit.int().argmax(dim=1)
+            last = int(torch.where(hit.any(dim=1), done_at + 1, torch.full_like(done_at, n_new)).max())
+            n_new = min(n_new, last)
+        self.spec_stats = dict(path="speculative", reason=None, verify_steps=steps, emitted=n_new, drafts_accepted=max(0, n_new - 1 - steps))
+        out = out[:, :n_new]
+        return (out, torch.stack(steps_logits[:n_new])) if collect_logits else out
+
     def generate_greedy(self, x0_filler, B: int, S: int, kv_start: torch.Tensor, max_new_tokens: int, pad_token_id: int,
                         eos_token_ids=None, forced_tokens: Optional[torch.Tensor] = None, collect_logits: bool = False,
                         do_sample: bool = False, temperature: float = 1.0, top_p: float = 1.0, seed: int = 0, layer_hook=None,
                         after_prompt=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                         repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None, chunk_hook=None,
-                        logprobs: Optional[int] = None):
+                        logprobs: Optional[int] = None, speculate: Optional[int] = None, draft_tokens: Optional[torch.Tensor] = None,
+                        lookup_ids: Optional[torch.Tensor] = None):
         """Prompt pass + KV-cached decode (greedy, or temperature / top-p sampling with the library's counter RNG).  Returns new token ids [B, n_new] (int64; finished sequences are
         filled with pad_token_id, generation stops early once every sequence has produced an EOS), and, with
         collect_logits, the per-step logits [n_new, B, V] (bf16).  `forced_tokens` [B, T] teacher-forces the
@@ -2039,12 +2226,20 @@ class CausalLMHIP:
         finished substitutions applied) and ranks the row's n most likely tokens; a `TokenLogprobs` is appended to the result.  The
         distribution is the MODEL'S OWN, log_softmax of the raw logits in front of the repetition penalty, the temperature and the
         top-k / top-p / min-p filters: HF's log_softmax(output_logits), not its processed output_scores.  The EOS token itself is
-        scored; the padding behind it is not (0 / -1 / 0).  None: no launch, no allocation."""
+        scored; the padding behind it is not (0 / -1 / 0).  None: no launch, no allocation.
+        speculate = k (1..7; None: the model's `set_speculative`, 0: off): draft-and-verify decoding, `_speculative_loop`; the
+        plain loop below runs instead, and `spec_stats["reason"]` says why, under the conditions `set_speculative` lists.  The
+        drafts come from a lookup in `lookup_ids` [B, S] (the prompt's token ids, -1 at left pads and audio positions) followed by
+        the emitted tokens, or from `draft_tokens` [B, max_new_tokens] (int64; the proposal for emitted position t, -1 = none)."""
         assert max_new_tokens >= 1
         check_decode_rows(B)
         use_pen = repetition_penalty is not None and float(repetition_penalty) != 1.0
         chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0)))
-        Smax = S + max_new_tokens
+        check_speculative_arg(speculate)
+        spec_k = (self.speculative if speculate is None else speculate) or 0
+        spec_reason = self._spec_reason(spec_k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook) if spec_k else "off"
+        # a verify chunk writes up to k slots past the last accepted one: cache, cos / sin table and workspaces get k more slots
+        Smax = S + max_new_tokens + (spec_k if spec_reason is None else 0)
         self._gen_alloc(B, Smax)
         dev = self.dev
         kv_start = kv_start.to(torch.int32).contiguous()
@@ -2056,6 +2251,9 @@ class CausalLMHIP:
                                   kv_cache=self.kv_cache, layer_hook=layer_hook)
         if after_prompt is not None:
             after_prompt()
+        if spec_reason is None:
+            return self._speculative_loop(logits, B, S, spec_k, kv_start, max_new_tokens, int(pad_token_id), eos_token_ids, collect_logits,
+                                          draft_tokens, lookup_ids)
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
         P = 0
         if chain:                                                            # token history = [prompt ids,] emitted tokens: out is its tail
@@ -2109,6 +2307,7 @@ class CausalLMHIP:
             has = (out.unsqueeze(2) == eos.view(1, 1, -1)).any(dim=2).any(dim=1)
             last = int(torch.where(has, done_at + 1, torch.full_like(done_at, n_new)).max())
             n_new = min(n_new, last)
+        self.spec_stats = dict(path="plain", reason=spec_reason, verify_steps=0, emitted=n_new, drafts_accepted=0)
         out = out[:, :n_new]
         res = (out, torch.stack(steps_logits[:n_new])) if collect_logits else (out,)
         if logprobs is not None:
@@ -2400,6 +2599,14 @@ class DeSTA25AudioModel:
         check_prefill_chunk(n)
         self.llm.set_prefill_chunk(n)
 
+    def set_speculative(self, k: Optional[int]) -> None:
+        """Greedy decoding of `generate` / `_generate_step` / the trainer's evaluate: None or 0 (default) = one token per step; an
+        int k in 1..7 = k draft tokens per step from a lookup in the row's own prompt (the spliced transcription included) and
+        output, verified by one pass over the weights (`CausalLMHIP.set_speculative`, which lists what runs the plain loop
+        instead).  `model.llm.spec_stats` reports the path taken and the acceptance of the last call."""
+        check_speculative_arg(k)
+        self.llm.set_speculative(k)
+
     def eval(self):
         return self.train(False)
 
@@ -2593,7 +2800,7 @@ class DeSTA25AudioModel:
     @torch.no_grad()
     def _generate_step(self, inputs, pad_token_id, temperature=0.7, top_p=0.9, max_new_tokens=512, do_sample=True,
                        eos_token_id=None, forced_tokens=None, collect_logits=False, seed=0, top_k=None, min_p=None,
-                       repetition_penalty=None, prompt_in_history=False, logprobs=None):
+                       repetition_penalty=None, prompt_in_history=False, logprobs=None, draft_tokens=None):
         """Reference `_generate_step` (modeling_desta25.py:1358-1431): audio features spliced into the prompt
         embeddings, then `llm_model.generate(inputs_embeds=…)` — here the KV-cached decoder on the HIP path.
         Returns ONLY the new tokens, as HF does for inputs_embeds prompts.  do_sample=False: greedy (temperature / top_p
@@ -2605,7 +2812,10 @@ class DeSTA25AudioModel:
         prompt passed as input_ids (`prompt_in_history=True`, the text-only leg of `generate`).
         logprobs = n: a `TokenLogprobs` becomes the last element of the result, (ids, lp) or (ids, logits, lp): every emitted
         token's log-probability and the n most likely tokens of its step under the model's own distribution, log_softmax of the
-        raw logits (HF's output_logits, not the processed output_scores; see `CausalLMHIP.generate_greedy`)."""
+        raw logits (HF's output_logits, not the processed output_scores; see `CausalLMHIP.generate_greedy`).
+        With `set_speculative(k)` greedy calls decode by draft and verify; the drafts are looked up in the row's prompt ids (the
+        spliced transcription included, audio slots and pads never match) and its output, or taken from `draft_tokens`
+        [B, max_new_tokens] (the proposal for emitted position t, -1 = none: tests and benchmarks)."""
         check_sampling_args(top_k, min_p, repetition_penalty)
         check_logprobs_arg(logprobs)
         cfg, dev = self.config, self.device
@@ -2654,7 +2864,12 @@ class DeSTA25AudioModel:
                 if isinstance(eos, int):
                     eos = [eos]
                 self._fwd = None
-                return self.llm.generate_greedy(fill, B, S, kv_start, int(max_new_tokens), int(pad_token_id), eos,
+                lookup = None
+                if self.llm.speculative:                                     # the lookup history: the ids the prompt embeds, -1 at pads and audio slots
+                    lookup = src.view(B, S).to(torch.int64)
+                    lookup = torch.where((attention_mask == 0) | (lookup < 0), torch.full_like(lookup, -1), lookup)
+                return self.llm.generate_greedy(fill, B, S, kv_start, int(max_new_tokens), int(pad_token_id), eos, draft_tokens=draft_tokens,
+                                                lookup_ids=lookup,
                                                 forced_tokens=forced_tokens, collect_logits=collect_logits, do_sample=bool(do_sample),
                                                 temperature=1.0 if temperature is None else float(temperature),
                                                 top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after,

@@ -194,6 +194,18 @@ def prefill_chunk(cfg: Cfg):
     return n
 
 
+SPECULATIVE_MAX = 7
+
+
+def speculative(cfg: Cfg):
+    """trainer.speculative (this port's key; absent, null or 0 = None, off): draft tokens per verify step of the greedy decoding
+    of evaluate / generate, an integer in 1..7 (`DeSTA25AudioModel.set_speculative`)."""
+    k = cfg.trainer.get("speculative", None)
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= SPECULATIVE_MAX):
+        raise ValueError(f"trainer.speculative={k!r} is not supported (an integer in 1..{SPECULATIVE_MAX} draft tokens per step, 0 or absent)")
+    return k or None
+
+
 def load_pretrained_weights(model, path: str) -> None:
     """Lightning-style {'state_dict': ...} with a 'model.' prefix (reference :73-83); tensors only."""
     import torch
@@ -258,6 +270,7 @@ def main(argv=None):
     decode_weights = decode_weights_kind(cfg)                               # a bad value fails here, before any GPU work
     kv_cache = kv_cache_kind(cfg)
     chunk = prefill_chunk(cfg)
+    spec = speculative(cfg)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
@@ -267,6 +280,7 @@ def main(argv=None):
     model.set_decode_weights(decode_weights)
     model.set_kv_cache(kv_cache)
     model.set_prefill_chunk(chunk)
+    model.set_speculative(spec)
     if cfg.get("init_from_pretrained_weights"):
         load_pretrained_weights(model, cfg.init_from_pretrained_weights)
     train_ds, eval_ds, collate, tok = create_datasets(cfg, model, rank)

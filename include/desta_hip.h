@@ -620,6 +620,32 @@ int desta_rope_kv_append_e4m3(void* qkv, int64_t ld, int rows, int seq, int n_q_
                               const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
                               float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream);
 
+/* Draft-and-verify greedy decoding (additive since ABI 8; `CausalLMHIP.verify_step` runs k + 1 rows per sequence through one
+ * pass over the weights).  Both kernels work on int64 token ids and take k in 1..7; anything else returns DESTA_EINVAL and
+ * launches nothing.
+ *
+ * desta_spec_ngram_draft: prompt lookup, what PromptLookupCandidateGenerator.get_candidates does on the host for
+ * `llm_model.generate(prompt_lookup_num_tokens=k)` (TF:generation/candidate_generator.py; the greedy loop it feeds is
+ * modeling_desta25.py:1419 / :1703).  One block per row of hist [batch, hist_ld], of which hist_len entries are valid.  For n from
+ * n_max down to n_min (1 <= n_min <= n_max <= 4) it looks for the largest i >= row_start[b] (NULL: 0) with i + n <= hist_len - 1
+ * and hist[b, i .. i + n) == hist[b, hist_len - n .. hist_len); negative ids (left pads, audio placeholders) never match.  The
+ * first n with a match wins: draft[b, j] = hist[b, i + n + j] while i + n + j < hist_len, else -1; no match: every entry -1. */
+int desta_spec_ngram_draft(const int64_t* hist, int64_t hist_ld, int batch, int hist_len, const int32_t* row_start, int k,
+                           int n_max, int n_min, int64_t* draft, void* stream);
+/* desta_spec_accept: the acceptance rule of the greedy loop of `llm_model.generate` (modeling_desta25.py:1419 / :1703) run with
+ * candidates (TF:generation/candidate_generator.py PromptLookupCandidateGenerator feeds HF's assisted decoding), in LOCKSTEP: every
+ * row advances by the same number of tokens.  inp [batch, k + 1] is the verify pass's input (last emitted token, then k drafts, -1 =
+ * no draft), pred [batch, k + 1] the argmax of its rows.  For an unfinished row m_b = number of leading j in 1..k with
+ * inp[b, j] >= 0 && inp[b, j] == pred[b, j - 1]; the row may take pred[b, 0 .. m_b].  A row with one of the n_eos ids among
+ * those finishes at it and limits nobody; a = min(max_take, min over the other unfinished rows of m_b + 1) >= 1.  Written:
+ * out[b, n .. n + a) (row stride ld_out; predictions, `pad` behind a row's EOS and on rows finished before the call),
+ * finished[b], next[b] = out[b, n + a - 1], taken[0] = a, and, with hist != NULL, the same a tokens at
+ * hist[b, hist_col .. hist_col + a) (the lookup history).  One block, plain stores.  DESTA_EINVAL unless max_take >= 1,
+ * n + max_take <= ld_out and hist_col + max_take <= hist_ld. */
+int desta_spec_accept(const int64_t* pred, const int64_t* inp, int batch, int k, uint8_t* finished, const int64_t* eos, int n_eos,
+                      int64_t pad, int max_take, int64_t* out, int64_t ld_out, int n, int64_t* next, int32_t* taken, int64_t* hist,
+                      int64_t hist_ld, int hist_col, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange: the MEAN over ranks of the flat fp32 gradient arena as one
  * RCCL all-reduce (ncclAvg) on `stream`, in place — what DDP's bucketed reducer does for the reference (accelerate
