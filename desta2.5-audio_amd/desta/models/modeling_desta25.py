@@ -1554,23 +1554,25 @@ class CausalLMHIP:
         self.decode_weights = "bf16"                # `set_decode_weights`: what the projections of a KV-cached decode step stream
         self.head8 = None
         self.kv_cache_kind = "bf16"                 # `set_kv_cache`: what generate()'s KV cache holds
-        self.kv_cache = self.kv_scale = None
+        self.kv_cache = self.kv_scale = self.kv_scale_v = None
+        self._gen_shape = self._gen_kind = None     # (B, Smax) and cache kind of `_gen_alloc`'s buffers; None = allocate at the next generate()
         self.prefill_chunk = None                   # `set_prefill_chunk`: positions per chunk of generate()'s lean prompt pass; None = `forward`
         self.kv_stage = self._pf = None
         self.speculative = None                     # `set_speculative`: draft tokens per verify step of greedy generate(); None = one token per step
-        self._spec = None
+        self._step1 = self._spec = None             # `_step_alloc` sets of the plain step (`_gen_alloc`) and of the verify step (`_spec_alloc`)
         self.spec_stats = None
 
     def set_speculative(self, k: Optional[int]) -> None:
         """Greedy generate(): None or 0 (default) = one token per sequence per pass over the weights; an int k in 1..7 = draft and
         verify: k tokens proposed by looking the row's last tokens up in its own prompt and output (`H.spec_ngram_draft`), all k + 1
-        rows per sequence checked by ONE pass (`verify_step`), and the longest run every unfinished row agrees on is emitted
-        (`H.spec_accept`; acceptance is in lockstep, so the cache keeps one length).  The tokens are those of the plain loop up to
-        the rounding of a different row count.  Sampling, a repetition penalty, `logprobs`, `forced_tokens`, a `layer_hook`
-        (ORCA), the FP8 KV cache and B * (k + 1) > H.DECODE_MAX_ROWS run the plain loop; `spec_stats` says which ran and why."""
+        rows per sequence checked by ONE pass (`verify_step`: the step body of `decode_step`, `_step_rows`, at width k + 1), and
+        the longest run every unfinished row agrees on is emitted (`H.spec_accept`; acceptance is in lockstep, so the cache keeps
+        one length).  The tokens are those of the plain loop up to the rounding of a different row count.  Sampling, a repetition
+        penalty, `logprobs`, `forced_tokens`, a `layer_hook` (ORCA), the FP8 KV cache and B * (k + 1) > H.DECODE_MAX_ROWS run the
+        plain loop; `spec_stats` says which ran and why."""
         check_speculative_arg(k)
         k = k or None
-        if k != getattr(self, "speculative", None):                           # the verify buffers go with the setting
+        if k != self.speculative:                                            # the verify buffers go with the setting
             self._spec = None
         self.speculative = k
 
@@ -1726,12 +1728,12 @@ class CausalLMHIP:
                     H.gemm(dt[:, 16 * j:], self.lhb, ar.grad(na[j]), r, h, Mp, trans_a=True, trans_b=True, lda=KP, ldb=h)
             H.gemm(dt, ly["a16"], dhb, M, h, KP, trans_b=True, ldb=h, residual=dhb)
 
-    def _alloc(self, B: int, S: int):
-        h, dev, M = self.h, self.dev, B * S
-        self.B, self.S, self.M = B, S, M
+    def _b16(self, *shape) -> torch.Tensor:
+        return torch.empty(*shape, dtype=BF16, device=self.dev)
 
-        def b16(*s):
-            return torch.empty(*s, dtype=BF16, device=dev)
+    def _alloc(self, B: int, S: int):
+        h, dev, M, b16 = self.h, self.dev, B * S, self._b16
+        self.B, self.S, self.M = B, S, M
         fr = torch.outer(torch.arange(S, device=dev, dtype=F32), self.inv_freq)
         self.cos_sin = torch.stack([fr.cos(), fr.sin()], dim=1).contiguous()                 # [S, 2, hd/2]
         self.cos_sin_il = torch.stack([fr.cos(), fr.sin()], dim=2).contiguous()              # [S, hd/2, 2]: (cos, sin) per adjacent pair
@@ -1870,16 +1872,13 @@ class CausalLMHIP:
 
     # -- greedy decoding with a KV cache (reference: llm_model.generate, modeling_desta25.py:1419) ------
     def _gen_alloc(self, B: int, Smax: int):
-        if getattr(self, "_gen_shape", None) == (B, Smax) and self._gen_kind == self.kv_cache_kind:
+        if self._gen_shape == (B, Smax) and self._gen_kind == self.kv_cache_kind:
             return
-        dev, h = self.dev, self.h
-
-        def b16(*s):
-            return torch.empty(*s, dtype=BF16, device=dev)
+        dev, b16 = self.dev, self._b16
         self._gen_shape, self._gen_kind = (B, Smax), self.kv_cache_kind
         self.kvw = 2 * self.hkv * self.hd
         # one [B, Smax, K|V] slab per layer: a decode step reads keys/values with row stride kvw, batch stride Smax*kvw
-        self.kv_cache = self.kv_scale = self.kv_scale_v = self.kv_stage = None     # free the old slabs before the new ones are made
+        self.kv_cache = self.kv_scale = self.kv_scale_v = self.kv_stage = self._step1 = None     # free the old slabs before the new ones are made
         if self.kv_cache_kind == "fp8":                                      # e4m3 bytes + fp32 scales [B, Smax, K heads | V heads]
             self.kv_cache = [torch.empty(B, Smax, self.kvw, dtype=torch.uint8, device=dev) for _ in range(self.L)]
             self.kv_scale = [torch.empty(B, Smax, 2 * self.hkv, dtype=F32, device=dev) for _ in range(self.L)]
@@ -1892,16 +1891,18 @@ class CausalLMHIP:
             self.kv_cache = [b16(B, Smax, self.kvw) for _ in range(self.L)]
         fr = torch.outer(torch.arange(Smax, device=dev, dtype=F32), self.inv_freq)
         self.gen_cos_sin = torch.stack([fr.cos(), fr.sin()], dim=1).contiguous()
-        self.g_x, self.g_xm, self.g_hb = b16(B, h), b16(B, h), b16(B, h)
-        self.g_qkv, self.g_att = b16(B, self.qkvw), b16(B, self.hq * self.hd)
-        self.g_lse = torch.empty(B, self.hq, 1, dtype=F32, device=dev)
+        self._step1 = self._step_alloc(B, 1)                                 # one row per sequence; its logits also take the prompt pass's last row
         # fp32 chunk partials of the split-KV decode attention, sized once for the longest cache (0 bytes while it fits one chunk)
         ws = H.attention_decode_workspace_bytes(B, self.hq, Smax, self.hd) if self.hd == 128 and self.hq // self.hkv <= 8 else 0
         self.g_attn_ws = torch.empty(ws // 4, dtype=F32, device=dev) if ws else None
-        self.g_act = b16(B, self.I)
-        self.g_r = torch.empty(B, dtype=F32, device=dev)
-        self.g_logits = torch.zeros(B, self.Vp, dtype=BF16, device=dev)
         self.g_next = torch.zeros(B, dtype=torch.int64, device=dev)
+
+    def _step_alloc(self, B: int, w: int) -> dict:
+        """Activations of one KV-cached step (`_step_rows`) over M = B * w rows, batch-major with w rows per sequence."""
+        h, dev, b16, M = self.h, self.dev, self._b16, B * w
+        return dict(x=b16(M, h), xm=b16(M, h), hb=b16(M, h), qkv=b16(M, self.qkvw), att=b16(M, self.hq * self.hd),
+                    lse=torch.empty(B, self.hq, w, dtype=F32, device=dev), act=b16(M, self.I), r=torch.empty(M, dtype=F32, device=dev),
+                    logits=torch.zeros(M, self.Vp, dtype=BF16, device=dev))     # pad columns stay 0
 
     def _kv_append(self, li: int, ly: dict, qkv: torch.Tensor, rows: int, seq: int, shift: torch.Tensor, slot0: int) -> None:
         """Rotate q, k of `qkv` [rows, qkvw] (batch-major, `seq` rows per sequence, position = row's index + shift[b]) in place and
@@ -1916,6 +1917,16 @@ class CausalLMHIP:
         else:
             H.rope_kv_append(*args, slot0)
 
+    def _cache_attn_desc(self, qkv: torch.Tensor, slab: torch.Tensor, att: torch.Tensor, lse: torch.Tensor, B: int, sq: int, sk: int, causal: bool,
+                         kv_start: torch.Tensor, **strides):
+        """Attention of `sq` query rows per sequence over slots [kv_start, sk) of a cache slab: Q the first columns of `qkv`
+        [B * sq, qkvw] (batch-major), K | V the halves of `slab` [B, Smax, kvw] (a layer's cache, or `kv_stage`), O into `att`.
+        causal: the mask "key <= query + (sk - sq)"."""
+        qkvw, kvw, bs = self.qkvw, self.kvw, slab.stride(0)
+        return H.attn_desc(qkv, slab, slab, att, lse, batch=B, hq=self.hq, hkv=self.hkv, sq=sq, sk=sk, hd=self.hd, scale=self.hd ** -0.5,
+                           causal=causal, kv_start=kv_start, q_off=0, k_off=0, v_off=self.hkv * self.hd, q_rs=qkvw, k_rs=kvw, v_rs=kvw,
+                           o_rs=self.hq * self.hd, k_bs=bs, v_bs=bs, **strides)
+
     # -- lean, chunked prompt pass of generate() (`set_prefill_chunk`): nothing is kept for a backward ---------------------------
     def _prefill_alloc(self, B: int, S: int, Cm: int) -> dict:
         """Buffers of `prefill`: the prompt's embeddings [B*S, h] (the only one sized by S) and ONE set of per-chunk activations
@@ -1924,10 +1935,7 @@ class CausalLMHIP:
         if pf is not None and pf["key"] == (B, S, Cm):
             return pf
         self._pf = pf = None                                                 # free the old set before the new one is made
-        h, dev, M = self.h, self.dev, B * Cm
-
-        def b16(*s):
-            return torch.empty(*s, dtype=BF16, device=dev)
+        h, dev, M, b16 = self.h, self.dev, B * Cm, self._b16
         self._pf = pf = dict(key=(B, S, Cm), x0=b16(B * S, h), xa=b16(M, h), xb=b16(M, h), hb=b16(M, h), qkv=b16(M, self.qkvw),
                              att=b16(M, self.hq * self.hd), xm=b16(M, h), gu=b16(M, 2 * self.I), act=b16(M, self.I),
                              lse=torch.empty(B * self.hq * Cm, dtype=F32, device=dev), r=torch.empty(M, dtype=F32, device=dev))
@@ -1949,7 +1957,6 @@ class CausalLMHIP:
         pf = self._prefill_alloc(B, S, chunks[0][1])
         Smax, kvw, aw, eps = self._gen_shape[1], self.kvw, hq * hd, c.rms_norm_eps
         kv8 = self._gen_kind == "fp8"
-        scale = hd ** -0.5
         x0_filler(pf["x0"])
         x0 = pf["x0"].view(B, S, h)
         if self.lora is not None:
@@ -1975,9 +1982,7 @@ class CausalLMHIP:
                     kv = self.kv_stage
                 else:
                     kv = cache
-                H.attention_fwd(H.attn_desc(qkv, kv, kv, att, lse, batch=B, hq=hq, hkv=hkv, sq=Cc, sk=c1, hd=hd, scale=scale, causal=True,
-                                            kv_start=kv_start, q_off=0, k_off=0, v_off=hkv * hd, q_rs=self.qkvw, k_rs=kvw, v_rs=kvw, o_rs=aw,
-                                            k_bs=Smax * kvw, v_bs=Smax * kvw))
+                H.attention_fwd(self._cache_attn_desc(qkv, kv, att, lse, B, Cc, c1, True, kv_start))
                 H.gemm(att, ly["wo"], xm, M, h, aw, residual=x)
                 H.rmsnorm_fwd(xm, ly["n2"], eps, hb, r)
                 if blocked:
@@ -1993,111 +1998,30 @@ class CausalLMHIP:
         H.gemm(hb[Cc - 1:], self.head, last_logits, B, self.V, h, lda=Cc * h, ldc=self.Vp)     # row Cc - 1 of each sequence: A is a strided view
         return last_logits
 
-    def decode_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, pos_shift: torch.Tensor, layer_hook=None) -> torch.Tensor:
-        """One token per sequence: `tokens` [B] (ids) sit at cache slot `cur`; returns logits [B, Vp] for slot cur+1."""
-        c, h, B = self.c, self.h, self._gen_shape[0]
-        Smax = self._gen_shape[1]
-        scale = self.hd ** -0.5
-        H.embed_gather(self.embed, None, tokens.to(torch.int32), B, h, self.g_x)
-        x = self.g_x
-        fuse = H.rms_fusable(B, h)                      # RMSNorm folded into the projection that consumes it
-
-        fp8 = self.decode_weights == "fp8"
-        if fp8:
-            self._fp8_decode_weights()
-
-        def mm(xin, w, w8, out, N, K, wide=B > 16, **kw):   # one projection on the bf16 weight, or on its e4m3 copy (q, scale)
-            if wide:                                    # B = 17..64: every weight byte once for all rows
-                H.gemm_wide(xin, w if w8 is None else w8[0], out, B, N, K, scale=None if w8 is None else w8[1], **kw)
-            elif w8 is not None:
-                H.gemm_w8(xin, w8[0], w8[1], out, B, N, K, **kw)
-            else:
-                H.gemm(xin, w, out, B, N, K, **kw)
-
-        def proj(xin, nw, w, w8, out, N, **kw):
-            if fuse:
-                mm(xin, w, w8, out, N, h, a_rms_weight=nw, a_rms_eps=c.rms_norm_eps, **kw)
-            else:
-                H.rmsnorm_fwd(xin, nw, c.rms_norm_eps, self.g_hb, self.g_r)
-                mm(self.g_hb, w, w8, out, N, h, **kw)
-        # long caches: split-KV kernel (K / V once per GQA group, a row's chunks on different CUs); a rule of the shape alone
-        split_kv = self.hd == 128 and self.hq // self.hkv <= 8 and cur + 1 >= H.DECODE_ATTN_MIN_KEYS
-        kv8 = self._gen_kind == "fp8"                   # FP8 cache: the kv8 kernel at every cur (the forward kernel cannot read bytes)
-        for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
-            q8 = ly["q8"] if fp8 else {}
-            if self.lora is None:
-                proj(x, ly["n1"], ly["wqkv"], q8.get("wqkv"), self.g_qkv, self.qkvw)
-            else:                                                             # the merged weight stays on H.gemm at every B
-                proj(x, ly["n1"], self._lora_merged(li), None, self.g_qkv, self.qkvw, wide=False)
-            self._kv_append(li, ly, self.g_qkv, B, 1, pos_shift, cur)        # rotate q,k + append K|V at slot cur
-            ad = H.attn_desc(self.g_qkv, cache, cache, self.g_att, self.g_lse, batch=B, hq=self.hq, hkv=self.hkv, sq=1, sk=cur + 1,
-                             hd=self.hd, scale=scale, causal=False, kv_start=kv_start, q_off=0, k_off=0, v_off=self.hkv * self.hd,
-                             q_rs=self.qkvw, k_rs=self.kvw, v_rs=self.kvw, o_rs=self.hq * self.hd,
-                             q_bs=self.qkvw, k_bs=Smax * self.kvw, v_bs=Smax * self.kvw, o_bs=self.hq * self.hd)
-            if kv8:
-                H.attention_decode_kv8(ad, self.kv_scale[li], self.kv_scale_v[li], Smax * 2 * self.hkv, 2 * self.hkv, self.g_attn_ws)
-            elif split_kv:
-                H.attention_decode(ad, self.g_attn_ws)
-            else:
-                H.attention_fwd(ad)
-            mm(self.g_att, ly["wo"], q8.get("wo"), self.g_xm, h, self.hq * self.hd, residual=x)
-            proj(self.g_xm, ly["n2"], ly["wgu"], q8.get("wgu"), self.g_act, self.I, act=4)     # norm + gate|up projection + SwiGLU
-            mm(self.g_act, ly["wd"], q8.get("wd"), self.g_x, h, self.I, residual=self.g_xm)
-            if layer_hook is not None:                                        # ORCA deep injection on the new row of every sequence
-                layer_hook(li, self.g_x)
-        proj(self.g_x, self.norm, self.head, self.head8 if fp8 else None, self.g_logits, self.V, ldc=self.Vp)
-        return self.g_logits
-
-    # -- draft-and-verify greedy decoding (`set_speculative`): k + 1 rows per sequence through one pass over the weights ---------
-    def _spec_alloc(self, B: int, k: int) -> dict:
-        """Buffers of `verify_step` for M = B * (k + 1) rows (batch-major, k + 1 rows per sequence) and the loop's integer state."""
-        sp = self._spec
-        if sp is not None and sp["key"] == (B, k):
-            return sp
-        self._spec = sp = None                                               # free the old set before the new one is made
-        h, dev, w = self.h, self.dev, k + 1
-        M = B * w
-
-        def b16(*s):
-            return torch.empty(*s, dtype=BF16, device=dev)
-
-        def i64(*s):
-            return torch.zeros(*s, dtype=torch.int64, device=dev)
-        self._spec = sp = dict(key=(B, k), x=b16(M, h), xm=b16(M, h), hb=b16(M, h), qkv=b16(M, self.qkvw), att=b16(M, self.hq * self.hd),
-                               act=b16(M, self.I), r=torch.empty(M, dtype=F32, device=dev), lse=torch.empty(B, self.hq, w, dtype=F32, device=dev),
-                               logits=torch.zeros(M, self.Vp, dtype=BF16, device=dev), pred=i64(B, w), inp=i64(B, w), draft=i64(B, k),
-                               taken=torch.zeros(1, dtype=torch.int32, device=dev), taken_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
-                               event=torch.cuda.Event())
-        return sp
-
-    def verify_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, pos_shift: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """k + 1 tokens per sequence in one pass: `tokens` [B, k + 1] (ids >= 0; column 0 the last emitted token, columns 1..k the
-        drafts), row j of a sequence sits at cache slot cur + j.  Returns logits [B * (k + 1), Vp] (batch-major): row j predicts
-        slot cur + j + 1 GIVEN the chunk's tokens in front of it.  `decode_step`'s kernels and weight forms, chosen by the row
-        count M = B * (k + 1) (at most H.DECODE_MAX_ROWS); the chunk's rotated K | V go to slots [cur, cur + k] of the bf16 cache
-        and the chunk attends slots [kv_start, cur + k] through the forward kernel under the mask "key <= query + (seq_k - seq_q)",
-        the descriptor of `prefill`.  Only slots in front of the next step's `cur` are ever trusted: the slots at or behind it
-        hold drafts that were not accepted, and the next chunk rewrites them (its slot0 is the new `cur`, its width k + 1) before
-        its attention, or any later one, reads them."""
-        c, h = self.c, self.h
+    def _step_rows(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, layer_hook=None) -> torch.Tensor:
+        """The KV-cached step, the one body of `decode_step` (w = 1) and `verify_step` (w = k + 1): `tokens` [B, w] (ids), row j of
+        a sequence sits at cache slot cur + j (position = slot - left pad); returns logits [B * w, Vp] (batch-major), row j for
+        slot cur + j + 1.  The row count M = B * w picks the buffer set, the projection kernel (M > 16: `gemm_wide`, else `gemm_w8`
+        on FP8 decode weights, else `gemm`; the LoRA-merged q|k|v stays on `gemm`) and the RMSNorm fusion (`H.rms_fusable`); the
+        rotated K | V go to slots [cur, cur + w) of the cache.  w picks the attention alone: w = 1 reads slots [kv_start, cur] without
+        a mask, through the kv8 kernel under the FP8 cache, the split-KV kernel from H.DECODE_ATTN_MIN_KEYS keys on where the
+        geometry allows, else the forward kernel; w > 1 (bf16 cache) reads slots [kv_start, cur + w) through the forward kernel under
+        the causal mask, the descriptor of `prefill`.  `layer_hook(l, x)` runs behind every layer on the step's rows [M, h]."""
+        h, aw, eps = self.h, self.hq * self.hd, self.c.rms_norm_eps
         B, w = tokens.shape
         M = B * w
-        assert self._gen_shape[0] == B and self._gen_kind == "bf16" and M <= H.DECODE_MAX_ROWS and cur + w <= self._gen_shape[1]
-        sp = self._spec_alloc(B, w - 1)
-        Smax, kvw, aw = self._gen_shape[1], self.kvw, self.hq * self.hd
-        scale = self.hd ** -0.5
-        x, xm, hb, qkv, att, act, r, logits = (sp[n] for n in ("x", "xm", "hb", "qkv", "att", "act", "r", "logits"))
+        bufs = self._step1 if w == 1 else self._spec_alloc(B, w - 1)
+        x, xm, hb, qkv, att, act, r, lse, logits = (bufs[n] for n in ("x", "xm", "hb", "qkv", "att", "act", "r", "lse", "logits"))
         H.embed_gather(self.embed, None, tokens.reshape(-1).to(torch.int32), M, h, x)
-        if pos_shift is None:
-            pos_shift = (cur - kv_start).to(torch.int32).contiguous()        # position of the chunk's row j: cur + j - left pad
-        fuse = H.rms_fusable(M, h)
+        shift = (cur - kv_start).to(torch.int32).contiguous()                # position of the step's row j: cur + j - left pad
+        fuse = H.rms_fusable(M, h)                      # RMSNorm folded into the projection that consumes it
 
         fp8 = self.decode_weights == "fp8"
         if fp8:
             self._fp8_decode_weights()
 
-        def mm(xin, w_, w8, out, N, K, wide=M > 16, **kw):   # `decode_step`'s choice, by M
-            if wide:
+        def mm(xin, w_, w8, out, N, K, wide=M > 16, **kw):   # one projection on the bf16 weight, or on its e4m3 copy (q, scale)
+            if wide:                                    # M = 17..64: every weight byte once for all rows
                 H.gemm_wide(xin, w_ if w8 is None else w8[0], out, M, N, K, scale=None if w8 is None else w8[1], **kw)
             elif w8 is not None:
                 H.gemm_w8(xin, w8[0], w8[1], out, M, N, K, **kw)
@@ -2106,25 +2030,69 @@ class CausalLMHIP:
 
         def proj(xin, nw, w_, w8, out, N, **kw):
             if fuse:
-                mm(xin, w_, w8, out, N, h, a_rms_weight=nw, a_rms_eps=c.rms_norm_eps, **kw)
+                mm(xin, w_, w8, out, N, h, a_rms_weight=nw, a_rms_eps=eps, **kw)
             else:
-                H.rmsnorm_fwd(xin, nw, c.rms_norm_eps, hb, r)
+                H.rmsnorm_fwd(xin, nw, eps, hb, r)
                 mm(hb, w_, w8, out, N, h, **kw)
+        # long caches: split-KV kernel (K / V once per GQA group, a row's chunks on different CUs); a rule of the shape alone
+        split_kv = w == 1 and self.hd == 128 and self.hq // self.hkv <= 8 and cur + 1 >= H.DECODE_ATTN_MIN_KEYS
+        kv8 = self._gen_kind == "fp8"                   # FP8 cache: the kv8 kernel at every cur (the forward kernel cannot read bytes)
+        one = dict(q_bs=self.qkvw, o_bs=aw) if w == 1 else {}
+        Smax = self._gen_shape[1]
         for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
             q8 = ly["q8"] if fp8 else {}
             if self.lora is None:
                 proj(x, ly["n1"], ly["wqkv"], q8.get("wqkv"), qkv, self.qkvw)
-            else:
+            else:                                                             # the merged weight stays on H.gemm at every M
                 proj(x, ly["n1"], self._lora_merged(li), None, qkv, self.qkvw, wide=False)
-            self._kv_append(li, ly, qkv, M, w, pos_shift, cur)
-            H.attention_fwd(H.attn_desc(qkv, cache, cache, att, sp["lse"], batch=B, hq=self.hq, hkv=self.hkv, sq=w, sk=cur + w, hd=self.hd,
-                                        scale=scale, causal=True, kv_start=kv_start, q_off=0, k_off=0, v_off=self.hkv * self.hd,
-                                        q_rs=self.qkvw, k_rs=kvw, v_rs=kvw, o_rs=aw, k_bs=Smax * kvw, v_bs=Smax * kvw))
+            self._kv_append(li, ly, qkv, M, w, shift, cur)                   # rotate q,k + append K|V at slots [cur, cur + w)
+            ad = self._cache_attn_desc(qkv, cache, att, lse, B, w, cur + w, w > 1, kv_start, **one)
+            if kv8:
+                H.attention_decode_kv8(ad, self.kv_scale[li], self.kv_scale_v[li], Smax * 2 * self.hkv, 2 * self.hkv, self.g_attn_ws)
+            elif split_kv:
+                H.attention_decode(ad, self.g_attn_ws)
+            else:
+                H.attention_fwd(ad)
             mm(att, ly["wo"], q8.get("wo"), xm, h, aw, residual=x)
-            proj(xm, ly["n2"], ly["wgu"], q8.get("wgu"), act, self.I, act=4)
+            proj(xm, ly["n2"], ly["wgu"], q8.get("wgu"), act, self.I, act=4)  # norm + gate|up projection + SwiGLU
             mm(act, ly["wd"], q8.get("wd"), x, h, self.I, residual=xm)
+            if layer_hook is not None:                                        # ORCA deep injection on the new rows of every sequence
+                layer_hook(li, x)
         proj(x, self.norm, self.head, self.head8 if fp8 else None, logits, self.V, ldc=self.Vp)
         return logits
+
+    def decode_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, layer_hook=None) -> torch.Tensor:
+        """One token per sequence: `tokens` [B] (ids) sit at cache slot `cur`; returns logits [B, Vp] for slot cur+1.  `_step_rows`
+        at w = 1."""
+        return self._step_rows(tokens.unsqueeze(1), cur, kv_start, layer_hook)
+
+    # -- draft-and-verify greedy decoding (`set_speculative`): k + 1 rows per sequence through one pass over the weights ---------
+    def _spec_alloc(self, B: int, k: int) -> dict:
+        """The `_step_alloc` set of `verify_step` for B * (k + 1) rows, and the loop's integer state."""
+        sp = self._spec
+        if sp is not None and sp["key"] == (B, k):
+            return sp
+        self._spec = sp = None                                               # free the old set before the new one is made
+        dev, w = self.dev, k + 1
+
+        def i64(*s):
+            return torch.zeros(*s, dtype=torch.int64, device=dev)
+        self._spec = sp = dict(key=(B, k), **self._step_alloc(B, w), pred=i64(B, w), inp=i64(B, w), draft=i64(B, k),
+                               taken=torch.zeros(1, dtype=torch.int32, device=dev), taken_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
+                               event=torch.cuda.Event())
+        return sp
+
+    def verify_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor) -> torch.Tensor:
+        """k + 1 tokens per sequence in one pass: `tokens` [B, k + 1] (ids >= 0; column 0 the last emitted token, columns 1..k the
+        drafts), row j of a sequence sits at cache slot cur + j.  Returns logits [B * (k + 1), Vp] (batch-major): row j predicts
+        slot cur + j + 1 GIVEN the chunk's tokens in front of it.  `_step_rows` at w = k + 1: `decode_step`'s body over
+        M = B * (k + 1) rows (at most H.DECODE_MAX_ROWS) of the bf16 cache, with the causal forward-kernel attention over slots
+        [kv_start, cur + k].  Only slots in front of the next step's `cur` are ever trusted: the slots at or behind it
+        hold drafts that were not accepted, and the next chunk rewrites them (its slot0 is the new `cur`, its width k + 1) before
+        its attention, or any later one, reads them."""
+        B, w = tokens.shape
+        assert self._gen_shape[0] == B and self._gen_kind == "bf16" and B * w <= H.DECODE_MAX_ROWS and cur + w <= self._gen_shape[1]
+        return self._step_rows(tokens, cur, kv_start)
 
     def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook) -> Optional[str]:
         """Why a call with speculation on runs the plain loop all the same; None when it does not."""
@@ -2144,18 +2112,24 @@ class CausalLMHIP:
             return f"B * (k + 1) = {B * (k + 1)} rows > {H.DECODE_MAX_ROWS}"
         return None
 
-    def _speculative_loop(self, logits, B: int, S: int, k: int, kv_start, T: int, pad_token_id: int, eos_token_ids, collect_logits: bool,
-                          draft_tokens, lookup_ids):
-        """The decode loop of `generate_greedy` with k drafts per step.  Token 0 is the prompt pass's; then, with n tokens emitted
-        and the last of them (not yet in the cache) due at slot cur = S + n - 1: draft -> `verify_step` on [last, drafts] ->
-        argmax of all M rows -> `H.spec_accept`, which emits a >= 1 tokens for every row (the run all unfinished rows accept, the
-        correction behind it included) and hands back a through a pinned int32: ONE host wait per verify step."""
-        dev, w = self.dev, k + 1
+    @staticmethod
+    def _trim_after_eos(out: torch.Tensor, eos: Optional[torch.Tensor], n_new: int) -> int:
+        """n_new without the columns of `out` [B, >= n_new] behind the point where every sequence has produced an EOS."""
+        if eos is None or n_new <= 1:
+            return n_new
+        hit = (out.unsqueeze(2) == eos.view(1, 1, -1)).any(dim=2)
+        done_at = hit.int().argmax(dim=1)
+        return min(n_new, int(torch.where(hit.any(dim=1), done_at + 1, torch.full_like(done_at, n_new)).max()))
+
+    def _speculative_loop(self, logits, out, finished, eos, S: int, k: int, kv_start, pad_token_id: int, collect_logits: bool, draft_tokens, lookup_ids):
+        """The decode loop of `generate_greedy` with k drafts per step, on its `out` [B, T] / `finished` / `eos`.  Token 0 is the
+        prompt pass's; then, with n tokens emitted and the last of them (not yet in the cache) due at slot cur = S + n - 1: draft ->
+        `verify_step` on [last, drafts] -> argmax of all M rows -> `H.spec_accept`, which emits a >= 1 tokens for every row (the
+        run all unfinished rows accept, the correction behind it included) and hands back a through a pinned int32: ONE host wait
+        per verify step."""
+        dev, w, (B, T) = self.dev, k + 1, out.shape
         sp = self._spec_alloc(B, k)
         pred, inp, draft, taken, taken_host, event = (sp[n] for n in ("pred", "inp", "draft", "taken", "taken_host", "event"))
-        out = torch.full((B, T), int(pad_token_id), dtype=torch.int64, device=dev)
-        finished = torch.zeros(B, dtype=torch.bool, device=dev)
-        eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
         hist = row_start = None
         P = 0
         if draft_tokens is not None:                                         # the proposal for emitted position t, -1 = none
@@ -2196,12 +2170,7 @@ class CausalLMHIP:
                 steps_logits.extend(rows[:min(a, w)])                        # a > k + 1 only once every row is finished: trimmed below
             n += a
             steps += 1
-        n_new = n
-        if eos is not None and n_new > 1:                                    # trim columns after every sequence finished
-            hit = (out.unsqueeze(2) == eos.view(1, 1, -1)).any(dim=2)
-            done_at = hit.int().argmax(dim=1)
-            last = int(torch.where(hit.any(dim=1), done_at + 1, torch.full_like(done_at, n_new)).max())
-            n_new = min(n_new, last)
+        n_new = self._trim_after_eos(out, eos, n)
         self.spec_stats = dict(path="speculative", reason=None, verify_steps=steps, emitted=n_new, drafts_accepted=max(0, n_new - 1 - steps))
         out = out[:, :n_new]
         return (out, torch.stack(steps_logits[:n_new])) if collect_logits else out
@@ -2244,17 +2213,19 @@ class CausalLMHIP:
         dev = self.dev
         kv_start = kv_start.to(torch.int32).contiguous()
         neg_pad = (-kv_start).contiguous()                                   # prompt: position = index - left_pad
+        logits = self._step1["logits"]                                       # the prompt's last row goes where the first pick reads
         if self.prefill_chunk is not None:                                   # lean prompt pass: chunks on rolling buffers, no save set
-            logits = self.prefill(x0_filler, B, S, kv_start, self.g_logits, layer_hook=layer_hook, chunk_hook=chunk_hook)
+            self.prefill(x0_filler, B, S, kv_start, logits, layer_hook=layer_hook, chunk_hook=chunk_hook)
         else:
-            logits = self.forward(x0_filler, B, S, kv_start, None, False, pos_shift=neg_pad, cos_sin=self.gen_cos_sin, last_logits=self.g_logits,
-                                  kv_cache=self.kv_cache, layer_hook=layer_hook)
+            self.forward(x0_filler, B, S, kv_start, None, False, pos_shift=neg_pad, cos_sin=self.gen_cos_sin, last_logits=logits,
+                         kv_cache=self.kv_cache, layer_hook=layer_hook)
         if after_prompt is not None:
             after_prompt()
-        if spec_reason is None:
-            return self._speculative_loop(logits, B, S, spec_k, kv_start, max_new_tokens, int(pad_token_id), eos_token_ids, collect_logits,
-                                          draft_tokens, lookup_ids)
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
+        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
+        if spec_reason is None:
+            return self._speculative_loop(logits, out, finished, eos, S, spec_k, kv_start, int(pad_token_id), collect_logits, draft_tokens, lookup_ids)
         P = 0
         if chain:                                                            # token history = [prompt ids,] emitted tokens: out is its tail
             P = 0 if prompt_ids is None else int(prompt_ids.shape[1])
@@ -2270,8 +2241,6 @@ class CausalLMHIP:
             st_tok = torch.empty(B, dtype=F32, device=dev)                   # one step's rows, contiguous for the kernel
             st_ids = torch.empty(B, logprobs, dtype=torch.int32, device=dev)
             st_top = torch.empty(B, logprobs, dtype=F32, device=dev)
-        finished = torch.zeros(B, dtype=torch.bool, device=dev)
-        eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
         n_new = 0
         for t in range(max_new_tokens):
             if collect_logits:
@@ -2299,14 +2268,8 @@ class CausalLMHIP:
                     break
             if t + 1 == max_new_tokens:
                 break
-            cur = S + t
-            shift = (cur - kv_start).to(torch.int32).contiguous()            # decode: position = slot - left_pad
-            logits = self.decode_step(nxt, cur, kv_start, shift, layer_hook=layer_hook)
-        if eos is not None and n_new > 1:                                    # trim columns after every sequence finished
-            done_at = (out.unsqueeze(2) == eos.view(1, 1, -1)).any(dim=2).int().argmax(dim=1)
-            has = (out.unsqueeze(2) == eos.view(1, 1, -1)).any(dim=2).any(dim=1)
-            last = int(torch.where(has, done_at + 1, torch.full_like(done_at, n_new)).max())
-            n_new = min(n_new, last)
+            logits = self.decode_step(nxt, S + t, kv_start, layer_hook=layer_hook)
+        n_new = self._trim_after_eos(out, eos, n_new)
         self.spec_stats = dict(path="plain", reason=spec_reason, verify_steps=0, emitted=n_new, drafts_accepted=0)
         out = out[:, :n_new]
         res = (out, torch.stack(steps_logits[:n_new])) if collect_logits else (out,)

@@ -9,6 +9,9 @@ slots [cur, cur + k] of every layer and every row's logits.  Both paths run the 
 differ only in kernel choice (row count) and summation order, so their distance is bounded by 1.5 x the plain path's own distance
 from the fp32 oracle on the same inputs, the rule of tests/test_gpu_prefill_chunk.py::test_chunked_vs_oracle; the cache rows are
 intermediate activations of that same computation and are held to the same figure.
+Launches: `verify_step` and `decode_step` are one body (`CausalLMHIP._step_rows`); at equal row counts (M = 12 and 24, bf16 and FP8
+decode weights) the recorded launches of the two are equal lists (name, M, N, K, act, fused norm, residual), the attention entry
+and the append's rows per sequence apart, and those two are what each width is meant to run.
 Model (tiny Qwen3 geometry, B = 3 with left pads, T = 24): the emitted tokens do not depend on where the drafts come from (perfect,
 none, corrupted, random, the lookup kernel) and equal the plain loop's and the fp32 oracle's; the number of verify steps is the one
 the drafts imply; every fallback runs the plain loop with the bits of `set_speculative(None)`.
@@ -293,6 +296,81 @@ def test_verify_step_vs_single_steps(hip, g4, weights, k):
     finally:
         model.set_decode_weights("bf16")
         model.set_speculative(None)
+
+
+STEP_LAUNCHES = ("embed_gather", "rmsnorm_fwd", "gemm", "gemm_w8", "gemm_wide", "rope_kv_append", "attention_fwd", "attention_decode")
+
+
+def _record_launches(hip, monkeypatch, step):
+    """The launches of one step as a list, in order.  Projections: (name, M, N, K, act, a_rms_weight given, residual given); the
+    row-wise kernels: (name, rows, width); the append additionally its rows per sequence; attention: (name, batch, seq_q, seq_k,
+    causal)."""
+    log = []
+
+    def wrap(name, entry):
+        real = getattr(hip, name)
+
+        def f(*a, **kw):
+            log.append((name,) + entry(*a, **kw))
+            return real(*a, **kw)
+        return f
+
+    def proj(*a, act=0, a_rms_weight=None, residual=None, **kw):
+        M, N, K = a[-3:]
+        return (M, N, K, act, a_rms_weight is not None, residual is not None)
+
+    def attn(d, *a):
+        return (d.batch, d.seq_q, d.seq_k, d.causal)
+    entries = dict(embed_gather=lambda table, audio, src, rows, hidden, out: (rows, hidden),
+                   rmsnorm_fwd=lambda x, w, eps, y, rstd=None: (x.numel() // x.shape[-1], x.shape[-1]),
+                   gemm=proj, gemm_w8=proj, gemm_wide=proj, rope_kv_append=lambda buf, ld, rows, seq, *a: (rows, ld, seq),
+                   attention_fwd=attn, attention_decode=attn)
+    assert sorted(entries) == sorted(STEP_LAUNCHES)
+    with monkeypatch.context() as m:
+        for name in STEP_LAUNCHES:
+            m.setattr(hip, name, wrap(name, entries[name]))
+        step()
+        torch.cuda.synchronize()
+    return log
+
+
+def _without_what_differs(log):
+    """The attention entry and the append's rows per sequence are meant to differ between the two widths."""
+    return [("attention",) if e[0].startswith("attention") else e[:3] if e[0] == "rope_kv_append" else e for e in log]
+
+
+@pytest.mark.parametrize("k", [3, 7])                                        # M = 12 and 24: both sides of the 16-row threshold
+@pytest.mark.parametrize("weights", ["bf16", "fp8"])
+def test_verify_step_launches_what_decode_step_launches(hip, monkeypatch, weights, k):
+    """`verify_step` at B = 3 with k drafts and `decode_step` at B = 3 (k + 1), each behind a prompt of S = 20, are one body over
+    M = 3 (k + 1) rows: the same launches with the same shapes, epilogues and fusions in the same order, the attention apart."""
+    d, w, model = _model(False)
+    llm, S, w1 = model.llm, 20, k + 1
+    M = 3 * w1
+    gen = torch.Generator().manual_seed(k)
+    toks = torch.randint(3, d.vocab, (M,), generator=gen).cuda()
+    try:
+        model.set_decode_weights(weights)
+        model.set_speculative(None)
+        pads = [0, 5, 11]
+        _gen(model, _text_inputs(d, S, pads, seed=S)[2], k + 2)              # the prompt pass; the cache has room for slots [S, S + k]
+        kv3 = torch.tensor(pads, dtype=torch.int32, device="cuda")
+        ver = _record_launches(hip, monkeypatch, lambda: llm.verify_step(toks.view(3, w1), S, kv3))
+        pads = [i % 7 for i in range(M)]
+        _gen(model, _text_inputs(d, S, pads, seed=S)[2], 2)
+        kvm = torch.tensor(pads, dtype=torch.int32, device="cuda")
+        dec = _record_launches(hip, monkeypatch, lambda: llm.decode_step(toks, S, kvm))
+    finally:
+        model.set_decode_weights("bf16")
+        model.set_speculative(None)
+    L = d.llm_layers
+    assert _without_what_differs(ver) == _without_what_differs(dec)
+    names = {e[0] for e in ver}
+    assert ("gemm_wide" in names) == (M > 16) and ("gemm_w8" in names) == (weights == "fp8" and M <= 16)
+    assert [e for e in ver if e[0].startswith("attention")] == [("attention_fwd", 3, w1, S + w1, 1)] * L
+    split = d.llm_hd == 128 and d.llm_hq // d.llm_hkv <= 8 and S + 1 >= hip.DECODE_ATTN_MIN_KEYS
+    assert [e for e in dec if e[0].startswith("attention")] == [("attention_decode" if split else "attention_fwd", M, 1, S + 1, 0)] * L
+    assert [e[3] for e in ver if e[0] == "rope_kv_append"] == [w1] * L and [e[3] for e in dec if e[0] == "rope_kv_append"] == [1] * L
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5
