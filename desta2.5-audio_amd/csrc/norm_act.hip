@@ -940,6 +940,175 @@ extern "C" int desta_rope_kv_append_e4m3(void* qkv, int64_t ld, int rows, int se
     return DESTA_OK;
 }
 
+// ------------------------------------------------------------------------------------ RoPE with a q|k|v projection bias
+// Qwen2 / Qwen2.5 (TF:models/qwen2/modeling_qwen2.py attention: q_proj, k_proj, v_proj = nn.Linear(bias=True)).  The projection
+// GEMM stays bias-free on every path and leaves bf16(x W^T); the kernel that rotates reads that row, adds the fp32 bias
+// [(n_q + 2 n_kv) * HD], then rotates q and k in fp32 and rounds once, and rounds v as bf16(v + b).  So the grid always covers
+// the V heads, which the bias-free forms touch only to copy them into a cache.  No q/k-norm (no model has both), no backward
+// (d(pre-bias) = d(post-bias), the bias itself is frozen).  With a zero bias the q|k bits are rope_k's / rope_kv8_k's: the
+// rotation is spelled as in rope_fwd_rotate and x + 0 = x (an input of -0 would come out as +0; a GEMM output is not -0).
+namespace {
+template <int HD>
+__device__ __forceinline__ void rope_bias_head(const bf16_t* p, const float* __restrict__ bias, int head, int j, bool rotate, int pos,
+                                               const float* __restrict__ cs, float (&oa)[8], float (&ob)[8]) {
+    constexpr int H2 = HD / 2;
+    float a[8], b[8], ba[8], bb[8];
+    load8(p, 8 * j, 0, a);
+    load8(p, H2 + 8 * j, 0, b);
+    load8(bias, (long)head * HD + 8 * j, 1, ba);
+    load8(bias, (long)head * HD + H2 + 8 * j, 1, bb);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { a[e] += ba[e]; b[e] += bb[e]; }
+    if (rotate) {
+        float c[8], s[8];
+        load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
+        load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { oa[e] = fmaf(a[e], c[e], -(b[e] * s[e])); ob[e] = fmaf(b[e], c[e], a[e] * s[e]); }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { oa[e] = a[e]; ob[e] = b[e]; }
+    }
+}
+// n_heads = n_q + n_kv rotated heads, then n_kv V heads; kv.dst == nullptr: in place only (training / eval forward).
+template <int HD>
+__global__ __launch_bounds__(256) void rope_bias_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
+                                                   const float* __restrict__ cs, const float* __restrict__ bias,
+                                                   const int* __restrict__ pos_shift, RopeKV kv, int sm_batch) {
+    constexpr int G = HD / 16, H2 = HD / 2;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long grp = gid / G;
+    const int j = (int)(gid % G);
+    const int all_heads = 2 * n_heads - n_q;
+    if (grp >= (long)rows * all_heads) return;                           // no whole-wave op follows
+    const int row = (int)(grp / all_heads), head = (int)(grp % all_heads);
+    const int spos = sm_batch ? row / sm_batch : row % S, bidx = sm_batch ? row % sm_batch : row / S;
+    const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
+    bf16_t* p = buf + (long)row * ld + (long)head * HD;
+    float oa[8], ob[8];
+    rope_bias_head<HD>(p, bias, head, j, head < n_heads, pos, cs, oa, ob);
+    store8_bf16(p, 8 * j, oa); store8_bf16(p, H2 + 8 * j, ob);
+    if (kv.dst && head >= n_q) {                                         // cache rows are batch-major (the entry point passes sm_batch = 0)
+        bf16_t* d = kv.dst + (long)(row / S) * kv.bs + (long)(kv.slot0 + row % S) * kv.rs + (long)(head - n_q) * HD;
+        store8_bf16(d, 8 * j, oa); store8_bf16(d, H2 + 8 * j, ob);
+    }
+}
+// rope_kv8_k with the bias: the per-head power-of-two scale is taken from the bf16 values AFTER the bias (k: after the rotation).
+__global__ __launch_bounds__(256) void rope_kv8_bias_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
+                                                       const float* __restrict__ cs, const float* __restrict__ bias,
+                                                       const int* __restrict__ pos_shift, RopeKV8 kv) {
+    constexpr int HD = 128, G = HD / 16, H2 = HD / 2;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long grp = gid / G;
+    const int j = (int)(gid % G);
+    const int all_heads = n_heads + kv.n_v;
+    const bool active = grp < (long)rows * all_heads;                    // a head is 8 adjacent lanes: a group is active or not as a whole
+    const int row = active ? (int)(grp / all_heads) : 0, head = active ? (int)(grp % all_heads) : 0;
+    bf16_t* p = buf + (long)row * ld + (long)head * HD;
+    const int spos = row % S, bidx = row / S;
+    const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
+    float oa[8], ob[8];
+    rope_bias_head<HD>(p, bias, head, j, head < n_heads, pos, cs, oa, ob);
+    u16x8 ca, cb;                                                        // the bf16 bits a bf16 cache would hold
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { ca[e] = f2bf(oa[e]); cb[e] = f2bf(ob[e]); }
+    if (active) { *(u16x8*)(p + 8 * j) = ca; *(u16x8*)(p + H2 + 8 * j) = cb; }
+    unsigned amax = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = max(amax, max((unsigned)(ca[e] & 0x7fff), (unsigned)(cb[e] & 0x7fff)));
+#pragma unroll
+    for (int o = 1; o < G; o <<= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, o, 64));
+    if (!active || head < n_q) return;
+    const int ex = amax ? e4m3_row_exponent(amax) : 0;
+    const long b = row / S, slot = kv.slot0 + row % S;
+    uint8_t* d = kv.dst + b * kv.bs + slot * kv.rs + (long)(head - n_q) * HD;
+    unsigned w[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const u16x8& v = h ? cb : ca;
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = ldexpf(bf2f(v[e]), -ex);
+        int lo = 0, hi = 0;
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+        w[2 * h] = (unsigned)lo; w[2 * h + 1] = (unsigned)hi;
+    }
+    *(uint2*)(d + 8 * j) = make_uint2(w[0], w[1]);
+    *(uint2*)(d + H2 + 8 * j) = make_uint2(w[2], w[3]);
+    if (j == 0) kv.scale[b * kv.sbs + slot * kv.srs + (head - n_q)] = pow2f(ex);
+}
+}  // namespace
+
+static int rope_bias_launch(const char* who, void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                            const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
+                            const int32_t* pos_shift, RopeKV kv, int sm_batch, void* stream) {
+    DESTA_CHECK_ARG(buf && cos_sin && qkv_bias, "%s: null argument", who);
+    DESTA_CHECK_ARG(!q_norm_w && !k_norm_w, "%s: a q|k|v bias together with q/k-norm weights is not supported", who);
+    DESTA_CHECK_ARG(head_dim == 64 || head_dim == 128, "%s: head_dim %d unsupported (64 or 128)", who, head_dim);
+    DESTA_CHECK_ARG(rows > 0 && seq > 0 && n_q_heads > 0 && n_kv_heads > 0, "%s: bad shape", who);
+    DESTA_CHECK_ARG(ld % 8 == 0 && ld >= (int64_t)(n_q_heads + 2 * n_kv_heads) * head_dim, "%s: ld %lld does not hold q|k|v", who, (long long)ld);
+    DESTA_CHECK_ARG((uintptr_t)buf % 16 == 0 && (uintptr_t)qkv_bias % 16 == 0 && (uintptr_t)cos_sin % 16 == 0, "%s: buffers must be 16-byte aligned", who);
+    const int nh = n_q_heads + n_kv_heads;
+    const long nthreads = (long)rows * (nh + n_kv_heads) * (head_dim / 16);
+    const dim3 grid((unsigned)((nthreads + 255) / 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (head_dim == 128)
+        hipLaunchKernelGGL((rope_bias_k<128>), grid, dim3(256), 0, st, (bf16_t*)buf, (long)ld, rows, seq, nh, n_q_heads, cos_sin, qkv_bias, pos_shift, kv, sm_batch);
+    else
+        hipLaunchKernelGGL((rope_bias_k<64>), grid, dim3(256), 0, st, (bf16_t*)buf, (long)ld, rows, seq, nh, n_q_heads, cos_sin, qkv_bias, pos_shift, kv, sm_batch);
+    DESTA_CHECK_LAUNCH(who);
+    return DESTA_OK;
+}
+
+extern "C" int desta_rope_bias(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                               const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
+                               const int32_t* pos_shift, int s_major_batch, void* stream) {
+    DESTA_CHECK_ARG(s_major_batch >= 0 && (s_major_batch == 0 || rows % s_major_batch == 0), "rope_bias: rows must be a multiple of s_major_batch");
+    const RopeKV kv = {nullptr, 0, 0, 0, 0};
+    return rope_bias_launch("rope_bias", buf, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, qkv_bias, pos_shift, kv,
+                            s_major_batch, stream);
+}
+
+extern "C" int desta_rope_kv_append_bias(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                                         const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
+                                         const int32_t* pos_shift, void* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                                         int slot0, void* stream) {
+    DESTA_CHECK_ARG(kv_cache && kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0 && slot0 >= 0 && head_dim > 0 &&
+                    kv_row_stride >= 2L * n_kv_heads * head_dim && kv_batch_stride >= 0, "rope_kv_append_bias: bad cache argument");
+    DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0, "rope_kv_append_bias: buffers must be 16-byte aligned");
+    DESTA_CHECK_ARG(rows > 0 && seq > 0 && rows % seq == 0, "rope_kv_append_bias: rows must be a multiple of seq");
+    const RopeKV kv = {(bf16_t*)kv_cache, (long)kv_batch_stride, (long)kv_row_stride, slot0, n_kv_heads};
+    return rope_bias_launch("rope_kv_append_bias", qkv, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, qkv_bias,
+                            pos_shift, kv, 0, stream);
+}
+
+extern "C" int desta_rope_kv_append_e4m3_bias(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                                              const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
+                                              const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                                              float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream) {
+    DESTA_CHECK_ARG(qkv && cos_sin && qkv_bias, "rope_kv_append_e4m3_bias: null argument");
+    DESTA_CHECK_ARG(!q_norm_w && !k_norm_w, "rope_kv_append_e4m3_bias: a q|k|v bias together with q/k-norm weights is not supported");
+    DESTA_CHECK_ARG(head_dim == 128, "rope_kv_append_e4m3_bias: head_dim %d unsupported (128)", head_dim);
+    DESTA_CHECK_ARG(rows > 0 && seq > 0 && rows % seq == 0 && n_q_heads > 0 && n_kv_heads > 0, "rope_kv_append_e4m3_bias: bad shape");
+    DESTA_CHECK_ARG(ld % 8 == 0 && ld >= (int64_t)(n_q_heads + 2 * n_kv_heads) * 128, "rope_kv_append_e4m3_bias: ld %lld does not hold q|k|v", (long long)ld);
+    DESTA_CHECK_ARG(kv_cache && kv_scale && kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0 && slot0 >= 0 &&
+                    kv_row_stride >= 2L * n_kv_heads * 128 && scale_row_stride >= 2L * n_kv_heads && scale_batch_stride >= 0 && kv_batch_stride >= 0,
+                    "rope_kv_append_e4m3_bias: bad cache argument");
+    DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)kv_scale % 4 == 0 && (uintptr_t)qkv_bias % 16 == 0 &&
+                    (uintptr_t)cos_sin % 16 == 0, "rope_kv_append_e4m3_bias: buffers must be 16-byte aligned");
+    const RopeKV8 kv = {kv_cache, kv_scale, (long)kv_batch_stride, (long)kv_row_stride, (long)scale_batch_stride, (long)scale_row_stride,
+                        slot0, n_kv_heads};
+    const int nh = n_q_heads + n_kv_heads;
+    const long nthreads = (long)rows * (nh + n_kv_heads) * 8;
+    hipLaunchKernelGGL(rope_kv8_bias_k, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, (long)ld, rows, seq,
+                       nh, n_q_heads, cos_sin, qkv_bias, pos_shift, kv);
+    DESTA_CHECK_LAUNCH("rope_kv_append_e4m3_bias");
+    return DESTA_OK;
+}
+
 extern "C" int desta_swiglu_fwd(const void* gate_up, void* act, int64_t rows, int inter, void* stream) {
     DESTA_CHECK_ARG(gate_up && act && rows > 0 && inter % 8 == 0, "swiglu_fwd: bad argument");
     hipLaunchKernelGGL(swiglu_fwd_k, dim3(nblocks(rows * (inter / 8))), dim3(256), 0, (hipStream_t)stream,

@@ -353,6 +353,7 @@ lib.desta_colsum_workspace_floats.restype = c_size_t
 lib.desta_colsum_workspace_floats.argtypes = [i32, i32]
 _colsum = _sig("desta_colsum_bf16", vp, i32, i32, i64, vp, i32, vp, vp)
 _rope = _sig("desta_rope", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, f32, vp, i64, i32, vp, i32, vp)
+_rope_bias = _sig("desta_rope_bias", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp)
 _swiglu_fwd = _sig("desta_swiglu_fwd", vp, vp, i64, i32, vp)
 _swiglu_bwd = _sig("desta_swiglu_bwd", vp, vp, vp, i64, i32, vp)
 _gelu_bwd = _sig("desta_gelu_bwd", vp, vp, vp, i64, vp)
@@ -408,7 +409,15 @@ def colsum(x, rows, cols, ld, out, accumulate=False, tag="ws"):
 
 @_profiled("rope", lambda buf, ld, rows, seq, n_q, n_kv, hd, *a, **k: 4 * rows * (n_q + n_kv) * hd)      # q|k read + written in place
 def rope(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w=None, k_norm_w=None, eps=1e-6, pre_norm=None,
-         ld_pre=0, backward=False, pos_shift=None, s_major_batch=0):
+         ld_pre=0, backward=False, pos_shift=None, s_major_batch=0, bias=None):
+    """bias (fp32 [(n_q + 2 n_kv) * hd], forward only): the q|k|v projection bias, added in front of the rotation; the V heads
+    that follow K in `buf` get theirs too (include/desta_hip.h, desta_rope_bias).  The backward takes none."""
+    if bias is not None:
+        if backward:
+            raise ValueError("rope: the backward takes no bias (d(pre-bias) = d(post-bias))")
+        check(_rope_bias(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), p(bias), p(pos_shift), s_major_batch,
+                         stream()), "desta_rope_bias")
+        return
     check(_rope(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pre_norm), ld_pre,
                 int(backward), p(pos_shift), s_major_batch, stream()), "desta_rope")
 
@@ -730,8 +739,16 @@ def mask_tokens_bf16(logits, ld, rows, cols, ids):
 _rope_kv = _sig("desta_rope_kv_append", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, f32, vp, vp, i64, i64, i32, vp)
 
 
-def rope_kv_append(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, cache, kv_bs, kv_rs, slot0):
-    """Forward rope on a fused q|k|v buffer + append of the rotated K and the V heads to the KV cache slab."""
+_rope_kv_bias = _sig("desta_rope_kv_append_bias", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, vp)
+
+
+def rope_kv_append(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, cache, kv_bs, kv_rs, slot0, bias=None):
+    """Forward rope on a fused q|k|v buffer + append of the rotated K and the V heads to the KV cache slab.  bias (fp32
+    [(n_q + 2 n_kv) * hd]): the q|k|v projection bias, added in front of the rotation (v: bf16(v + b), in place and in the cache)."""
+    if bias is not None:
+        check(_rope_kv_bias(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), p(bias), p(pos_shift), p(cache), kv_bs,
+                            kv_rs, slot0, stream()), "desta_rope_kv_append_bias")
+        return
     check(_rope_kv(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pos_shift), p(cache), kv_bs,
                    kv_rs, slot0, stream()), "desta_rope_kv_append")
 
@@ -739,9 +756,17 @@ def rope_kv_append(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_
 _rope_kv8 = _sig("desta_rope_kv_append_e4m3", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, f32, vp, vp, i64, i64, vp, i64, i64, i32, vp)
 
 
+_rope_kv8_bias = _sig("desta_rope_kv_append_e4m3_bias", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, i32, vp)
+
+
 def rope_kv_append_e4m3(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, cache, kv_bs, kv_rs,
-                        scale, scale_bs, scale_rs, slot0):
-    """rope_kv_append into the FP8 cache: e4m3 bytes to `cache` (strides in bytes), one fp32 scale per head to `scale`."""
+                        scale, scale_bs, scale_rs, slot0, bias=None):
+    """rope_kv_append into the FP8 cache: e4m3 bytes to `cache` (strides in bytes), one fp32 scale per head to `scale`.  bias: as
+    in rope_kv_append; the scales are taken after it."""
+    if bias is not None:
+        check(_rope_kv8_bias(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), p(bias), p(pos_shift), p(cache), kv_bs,
+                             kv_rs, p(scale), scale_bs, scale_rs, slot0, stream()), "desta_rope_kv_append_e4m3_bias")
+        return
     check(_rope_kv8(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pos_shift), p(cache), kv_bs,
                     kv_rs, p(scale), scale_bs, scale_rs, slot0, stream()), "desta_rope_kv_append_e4m3")
 

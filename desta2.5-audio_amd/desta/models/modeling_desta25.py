@@ -96,10 +96,35 @@ class LLMConfig:
     rope_scaling: Optional[dict] = None          # {"rope_type":"llama3","factor":8,"low_freq_factor":1,...} or None
     tie_word_embeddings: bool = False
     eos_token_id: Optional[List[int]] = None     # generation stops on any of these (HF generation_config semantics)
+    attention_bias: bool = False                 # q_proj / k_proj / v_proj carry a bias (Qwen2 / Qwen2.5: always; else config.json's flag)
 
     @property
     def qk_norm(self) -> bool:
         return self.model_type == "qwen3"
+
+
+def check_llm_bias_tensors(c: LLMConfig, names) -> None:
+    """Every `*.bias` tensor of the decoder checkpoint has to be one the kernels add: the q|k|v projection biases of an
+    `attention_bias` model (TF:models/qwen2/modeling_qwen2.py attention), added by the rotary kernels.  Anything else (Llama's
+    `attention_bias` also puts one on o_proj, `mlp_bias` on gate / up / down) raises by name here, at load, instead of being
+    dropped silently; so does a checkpoint that lacks a bias its config promises."""
+    used = set()
+    if c.attention_bias:
+        if c.qk_norm:
+            raise NotImplementedError(f"attention_bias together with the q/k-norm of model_type '{c.model_type}' is not implemented")
+        used = {f"{LLM}model.layers.{i}.self_attn.{m}_proj.bias" for i in range(c.num_hidden_layers) for m in "qkv"}
+    if names is None:
+        return
+    names = set(names)
+    for n in sorted(names):
+        if n.startswith(LLM) and n.endswith(".bias") and n not in used:
+            why = ("o_proj.bias (Llama-style attention_bias)" if n.endswith("o_proj.bias") else
+                   "mlp_bias" if ".mlp." in n else
+                   "a q|k|v bias without attention_bias in config.json" if n.endswith(("q_proj.bias", "k_proj.bias", "v_proj.bias")) else "an unused bias")
+            raise NotImplementedError(f"decoder tensor '{n[len(LLM):]}' is not implemented: {why}; only q_proj / k_proj / v_proj biases are added")
+    missing = sorted(used - names)
+    if missing:
+        raise KeyError(f"attention_bias is set but the checkpoint has no '{missing[0][len(LLM):]}'")
 
 
 def _read_hf_config(path_or_id: str) -> dict:
@@ -197,7 +222,13 @@ class DeSTA25Config:
         scaling = c.get("rope_scaling") or ({k: v for k, v in rp.items() if k != "rope_theta"} if rp.get("rope_type", "default") != "default" else None)
         if scaling is not None and scaling.get("rope_type", scaling.get("type", "default")) in ("default", None):
             scaling = None
+        # biases and masks no kernel here implements: named at load, never dropped (the tensors themselves: `check_llm_bias_tensors`)
+        if c.get("mlp_bias"):
+            raise NotImplementedError("mlp_bias: true (biases on gate_proj / up_proj / down_proj) is not implemented")
+        if c.get("use_sliding_window"):
+            raise NotImplementedError("use_sliding_window: true (sliding-window attention) is not implemented")
         return LLMConfig(
+            attention_bias=c.get("model_type", "llama") == "qwen2" or bool(c.get("attention_bias", False)),
             model_type=c.get("model_type", "llama"), hidden_size=c["hidden_size"], num_hidden_layers=c["num_hidden_layers"],
             num_attention_heads=heads, num_key_value_heads=c.get("num_key_value_heads", heads),
             head_dim=c.get("head_dim") or c["hidden_size"] // heads, intermediate_size=c["intermediate_size"],
@@ -1485,7 +1516,7 @@ class OrcaHIP:
 
 # =========================================================================================== causal LM
 class CausalLMHIP:
-    """Frozen Llama-3.1 / Qwen3 decoder: forward + dX-only backward."""
+    """Frozen Llama-3.1 / Qwen3 / Qwen2.5 decoder: forward + dX-only backward."""
 
     def __init__(self, cfg: DeSTA25Config, w: Dict[str, torch.Tensor], device):
         c = cfg.llm_config
@@ -1496,6 +1527,7 @@ class CausalLMHIP:
         self.qkvw = (self.hq + 2 * self.hkv) * self.hd
         self.Vp = _r64(self.V)
         dev = device
+        check_llm_bias_tensors(c, w.keys() if hasattr(w, "keys") else None)   # (a lazy weight source makes what is asked for: nothing to list)
 
         def g(name):
             return w[LLM + name].to(dev)
@@ -1529,7 +1561,11 @@ class CausalLMHIP:
                 ly["wguT_b"] = T(ly["wgu_b"])
             else:
                 ly["wguT"] = T(wgu)
-            if not c.qk_norm and not cfg.use_lora:            # (with adapters the fused-rope path is never taken: no second copy)
+            if c.attention_bias:
+                # q|k|v projection bias (Qwen2 / Qwen2.5), fp32: the projection GEMMs stay bias-free on every path and the kernel
+                # that rotates adds it (`H.rope` / `_kv_append`; rounding rule: DESIGN §3).  The LoRA-merged weight keeps this bias.
+                ly["bqkv"] = torch.cat([g(p + f"self_attn.{m}_proj.bias").float() for m in "qkv"]).contiguous()
+            if not c.qk_norm and not c.attention_bias and not cfg.use_lora:   # (with adapters the fused-rope path is never taken: no second copy)
                 # rotary embedding fused into the q|k|v projection (frozen weights, so a re-layout at load is free): the rows of
                 # every q / k head in the order 0, hd/2, 1, hd/2+1, ... put HF's rotate_half pair (i, i + hd/2) on ADJACENT output
                 # columns, which one lane of the GEMM epilogue owns; q.k is invariant under a permutation of the head dim applied
@@ -1546,7 +1582,8 @@ class CausalLMHIP:
         self.head = self.embed if c.tie_word_embeddings else g("lm_head.weight").to(BF16).contiguous()
         self.headT = T(self.head)                                             # [h, Vp], zero padded
         self.inv_freq = rope_inv_freq(c).to(dev)
-        self.fuse_rope = not c.qk_norm              # A/B switch (bench.py --no-rope-fusion); q/k-norm models (Qwen3) keep the rope kernel
+        # A/B switch (bench.py --no-rope-fusion); q/k-norm models (Qwen3) and q|k|v-bias models (Qwen2.5) keep the rope kernel
+        self.fuse_rope = not c.qk_norm and not c.attention_bias
         self.B = self.S = 0
         self.lora = None
         self.skip_dead_rows = True                  # A/B switch (bench.py --no-dead-row-skip): last layer on the target tail, layer-0 dX on the audio rows
@@ -1822,7 +1859,7 @@ class CausalLMHIP:
                 pass                                                          # q, k left the projection rotated
             elif kv_cache is None:
                 H.rope(s["qkv"], self.qkvw, M, S, self.hq, self.hkv, self.hd, cs, ly.get("qn"), ly.get("kn"), c.rms_norm_eps, pos_shift=pos_shift,
-                       s_major_batch=smb)
+                       s_major_batch=smb, **({"bias": ly["bqkv"]} if "bqkv" in ly else {}))
             else:                                                             # generate(): `kv_cache` is self.kv_cache, `cos_sin` its table
                 self._kv_append(i, ly, s["qkv"], M, S, pos_shift, 0)
             aw = self.hq * self.hd
@@ -1907,15 +1944,17 @@ class CausalLMHIP:
     def _kv_append(self, li: int, ly: dict, qkv: torch.Tensor, rows: int, seq: int, shift: torch.Tensor, slot0: int) -> None:
         """Rotate q, k of `qkv` [rows, qkvw] (batch-major, `seq` rows per sequence, position = row's index + shift[b]) in place and
         append the rotated K | V of layer `li` at slots [slot0, slot0 + seq) of its cache slab.  The slab's dtype picks the kernel:
-        bf16 as it is, uint8 (FP8 cache) quantised per head with the scales into `kv_scale[li]`.  Every stride is the tensor's."""
+        bf16 as it is, uint8 (FP8 cache) quantised per head with the scales into `kv_scale[li]`.  Every stride is the tensor's.
+        A q|k|v bias (`bqkv`) is added by the same kernel in front of the rotation, so no caller has a branch for it."""
         cache = self.kv_cache[li]
+        bias = {"bias": ly["bqkv"]} if "bqkv" in ly else {}                   # bias-free models make the call they always made
         args = (qkv, self.qkvw, rows, seq, self.hq, self.hkv, self.hd, self.gen_cos_sin, ly.get("qn"), ly.get("kn"), self.c.rms_norm_eps, shift,
                 cache, cache.stride(0), cache.stride(1))
         if cache.dtype == torch.uint8:
             sc = self.kv_scale[li]
-            H.rope_kv_append_e4m3(*args, sc, sc.stride(0), sc.stride(1), slot0)
+            H.rope_kv_append_e4m3(*args, sc, sc.stride(0), sc.stride(1), slot0, **bias)
         else:
-            H.rope_kv_append(*args, slot0)
+            H.rope_kv_append(*args, slot0, **bias)
 
     def _cache_attn_desc(self, qkv: torch.Tensor, slab: torch.Tensor, att: torch.Tensor, lse: torch.Tensor, B: int, sq: int, sk: int, causal: bool,
                          kv_start: torch.Tensor, **strides):

@@ -44,6 +44,8 @@ class RandomWeights:
             n = name[len(LLM):]
             h, I, hd = c.hidden_size, c.intermediate_size, c.head_dim
             if n in ("model.embed_tokens.weight", "lm_head.weight"): return (c.vocab_size, h)
+            if n.endswith("q_proj.bias"): return (c.num_attention_heads * hd,)             # attention_bias decoders (Qwen2.5)
+            if n.endswith(("k_proj.bias", "v_proj.bias")): return (c.num_key_value_heads * hd,)
             if "q_proj" in n: return (c.num_attention_heads * hd, h)
             if "k_proj" in n or "v_proj" in n: return (c.num_key_value_heads * hd, h)
             if "o_proj" in n: return (h, c.num_attention_heads * hd)
@@ -118,7 +120,18 @@ def _qwen3(h, layers, heads, kv, inter, tied, theta=1000000.0):
                 tie_word_embeddings=tied)
 
 
-FULL_CONFIGS = {
+class _Configs(dict):
+    """Keys = the names of the shipped model YAMLs (examples/train/config); `ALIASES` are short names that resolve to one of them
+    on lookup without becoming keys."""
+    ALIASES = {"qwen2.5-7B": "desta25_qwen25-7B_Qformer6L"}
+
+    def __missing__(self, key):
+        if key in self.ALIASES:
+            return self[self.ALIASES[key]]
+        raise KeyError(key)
+
+
+FULL_CONFIGS = _Configs({
     # BASELINE.json configs[1]/[2]: Whisper-large-v3 + Llama-3.1-8B, Q-Former 6L (SURVEY Appendix B dims)
     "desta25_llama31-8B_Qformer6L": dict(
         llm_model_id="DeSTA-ntu/Llama-3.1-8B-Instruct", encoder_model_id="openai/whisper-large-v3",
@@ -143,7 +156,15 @@ FULL_CONFIGS = {
         llm_model_id="Qwen/Qwen3-0.6B", encoder_model_id="openai/whisper-large-v3-turbo",
         qformer_num_hidden_layers=6, prompt_size=64, placeholder_token="<|video_pad|>",
         llm_config=_qwen3(1024, 28, 16, 8, 3072, True), encoder_config=_ENC_LARGE_V3),
-}
+    # Qwen2.5-7B-Instruct (its config.json): q|k|v projection biases, no q/k-norm, 7 query heads per KV head, untied lm_head
+    "desta25_qwen25-7B_Qformer6L": dict(
+        llm_model_id="Qwen/Qwen2.5-7B-Instruct", encoder_model_id="openai/whisper-large-v3",
+        qformer_num_hidden_layers=6, prompt_size=64, placeholder_token="<|video_pad|>",
+        llm_config=dict(model_type="qwen2", hidden_size=3584, num_hidden_layers=28, num_attention_heads=28, num_key_value_heads=4,
+                        head_dim=128, intermediate_size=18944, vocab_size=152064, rms_norm_eps=1e-6, rope_theta=1000000.0,
+                        tie_word_embeddings=False),
+        encoder_config=_ENC_LARGE_V3),
+})
 # the three ORCA-hybrid configs the reference ships (examples/train/config/desta25_{llama31-8B,qwen3-0.6b,qwen3-4b}_ORCAHybrid.yaml):
 # global + local tokens in the gated cross-attention behind every decoder layer, 0.05 loss weights, whisper-large-v3
 _ORCA = dict(connector_mode="orca_hybrid", orca_enabled=True, orca_local_enabled=True, orca_global_cross_attn=True,

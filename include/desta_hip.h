@@ -620,6 +620,28 @@ int desta_rope_kv_append_e4m3(void* qkv, int64_t ld, int rows, int seq, int n_q_
                               const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
                               float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream);
 
+/* The three rotary entry points for decoders whose q_proj / k_proj / v_proj carry a bias (Qwen2 / Qwen2.5,
+ * TF:models/qwen2/modeling_qwen2.py attention: `nn.Linear(..., bias=True)` for q, k, v and no bias for o).  Additive since
+ * ABI 8; forward only (d(pre-bias) = d(post-bias), so the backward is desta_rope's).  The projection GEMM stays bias-free
+ * and leaves bf16(x W^T) in the fused [rows, ld] q|k|v buffer; these kernels read it, add qkv_bias (fp32
+ * [(n_q_heads + 2 n_kv_heads) * head_dim], q then k then v, 16-byte aligned) and write back IN PLACE: q and k heads rotated
+ * in fp32 and rounded once, v heads as bf16(v + b).  So ld must hold all three parts, also for desta_rope_bias.  The cache
+ * forms append the rotated K heads and the biased V heads as their bias-free twins do; in the e4m3 form the per-head
+ * power-of-two scale is taken from those bf16 values, i.e. after the bias.  With a zero bias every output bit is the twin's.
+ * q_norm_w / k_norm_w must be NULL: a bias together with q/k-norm weights returns DESTA_EINVAL and launches nothing, as does
+ * any other bad argument.  The remaining arguments are those of the twin. */
+int desta_rope_bias(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                    const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
+                    const int32_t* pos_shift, int s_major_batch, void* stream);
+int desta_rope_kv_append_bias(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                              const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
+                              const int32_t* pos_shift, void* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                              int slot0, void* stream);
+int desta_rope_kv_append_e4m3_bias(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                                   const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
+                                   const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                                   float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream);
+
 /* Draft-and-verify greedy decoding (additive since ABI 8; `CausalLMHIP.verify_step` runs k + 1 rows per sequence through one
  * pass over the weights).  Both kernels work on int64 token ids and take k in 1..7; anything else returns DESTA_EINVAL and
  * launches nothing.
