@@ -583,6 +583,7 @@ __global__ __launch_bounds__(256) void dropout_mask_k(unsigned slo, unsigned shi
 constexpr int ARGMAX_SPLIT = 64;
 __device__ __forceinline__ unsigned long argmax_key(float v, int idx) {
     unsigned b = __float_as_uint(v);
+    if (b == 0x80000000u) b = 0u;                                       // -0 maps onto +0 (they compare equal in torch)
     b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);                     // monotone map of float order onto unsigned
     return ((unsigned long)b << 32) | (unsigned)(~(unsigned)idx);
 }
@@ -625,7 +626,12 @@ __global__ __launch_bounds__(64) void argmax_final_k(const unsigned long* __rest
 // search over the key space (each step one pass over the row: L2-resident, 256 KiB for a 128k vocabulary).  Tokens that
 // TIE with the boundary logit are all kept (torch.sort leaves their order unspecified).  The sample is drawn by
 // inverting the prefix sum of the kept masses in index order with one counter-based uniform per (seed, step, row).
-__device__ __forceinline__ unsigned bf16_key(bf16_t b) { return (b & 0x8000u) ? (unsigned)(~b & 0xffffu) : (unsigned)(b | 0x8000u); }
+// A -inf logit (desta_mask_tokens_bf16) is never kept; a row without a finite logit keeps nothing and yields token 0.
+__device__ __forceinline__ unsigned bf16_key(bf16_t b) {
+    if (b == 0x8000u) b = 0u;                                      // -0 maps onto +0: one key for equal logits
+    return (b & 0x8000u) ? (unsigned)(~b & 0xffffu) : (unsigned)(b | 0x8000u);
+}
+constexpr unsigned BF16_KEY_NINF = 0x007fu;                        // bf16_key(-inf): a suppressed token, never kept (mass 0)
 __device__ __forceinline__ float block_sum_1024(float v, float* red) {
     v = wave_sum(v);
     __syncthreads();
@@ -676,7 +682,7 @@ __global__ __launch_bounds__(1024) void sample_top_p_k(const bf16_t* __restrict_
     float mine = 0.f;
     for (int c = c0; c < c1; ++c) {
         const bf16_t b = row[c];
-        const bool keep = bf16_key(b) >= kstar;
+        const bool keep = bf16_key(b) >= kstar && bf16_key(b) != BF16_KEY_NINF;
         if (keep) mine += __expf((bf2f(b) - mx) * inv_temp);
         if (keep_mask) keep_mask[(long)blockIdx.x * cols + c] = keep ? 1 : 0;
     }
@@ -705,13 +711,13 @@ __global__ __launch_bounds__(1024) void sample_top_p_k(const bf16_t* __restrict_
         int tok = -1, last = -1;
         for (int c = c0; c < c1; ++c) {
             const bf16_t b = row[c];
-            if (bf16_key(b) >= kstar) {
+            if (bf16_key(b) >= kstar && bf16_key(b) != BF16_KEY_NINF) {
                 last = c;
                 run += __expf((bf2f(b) - mx) * inv_temp);
                 if (run > rem) { tok = c; break; }
             }
         }
-        out[blockIdx.x] = tok >= 0 ? tok : last;
+        out[blockIdx.x] = tok >= 0 ? tok : (last >= 0 ? last : 0);   // nothing kept in the chunk (no finite logit in the row): token 0
     }
 }
 

@@ -260,7 +260,8 @@ __global__ __launch_bounds__(SNT) void sample_chain_k(const bf16_t* __restrict__
 
     // MinPLogitsWarper on the survivors: p_i >= min_p * p_max  <=>  exp(t_i - t_max) >= min_p; then the kept masses per
     // thread over a contiguous index chunk, so the draw's prefix sum runs in index order
-    auto kept = [&](float t) -> bool { return f32_key(t) >= thr && (min_p <= 0.f || expf(t - tmax) >= min_p); };
+    // (a -inf score, as desta_mask_tokens_bf16 leaves it, has mass 0 and is never kept)
+    auto kept = [&](float t) -> bool { return t > -INFINITY && f32_key(t) >= thr && (min_p <= 0.f || expf(t - tmax) >= min_p); };
     const int chunk = (((cols + SNT - 1) / SNT) + 7) & ~7;
     const int c0 = min(cols, tid * chunk), c1 = min(cols, c0 + chunk);
     u64 mine = 0;

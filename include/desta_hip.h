@@ -561,7 +561,8 @@ int desta_target_rows(const int64_t* labels, int batch, int seq, int32_t* idx, i
 int desta_scatter_rows_bf16(const void* in, const int32_t* idx, int rows, int hidden, void* out, void* stream);
 
 /* Greedy decoding helper: out[r] = argmax over the first `cols` entries of bf16 row r (first maximum, two-stage
- * reduction; `workspace` holds desta_argmax_workspace_bytes(rows) bytes).
+ * reduction; `workspace` holds desta_argmax_workspace_bytes(rows) bytes).  -0.0 and +0.0 are equal, as in torch.argmax and in
+ * desta_sample_bf16's greedy mode; a row of -inf alone gives 0.
  * Replaces the argmax of `llm_model.generate(do_sample=False)` (modeling_desta25.py:1419). */
 size_t desta_argmax_workspace_bytes(int rows);
 /* logits[r, ids[i]] = -inf (bf16 rows of `cols` entries, row stride ld) for every row r: token suppression in front of the argmax
@@ -574,7 +575,9 @@ int desta_argmax_bf16(const void* x, int64_t ld, int rows, int cols, int64_t* ou
  * (TF:generation/logits_process.py, TF:generation/utils.py `_sample`).  Token i is kept iff the softmax mass of all
  * tokens not more probable than i exceeds 1 - top_p; tokens tying with the boundary logit are all kept.  The draw uses
  * the library's counter-based RNG (seed, step, row) — same distribution as torch.multinomial, not the same stream.
- * keep_mask (optional, uint8 [rows, cols]) exports the kept set (tests). */
+ * keep_mask (optional, uint8 [rows, cols]) exports the kept set (tests): the tokens that can be drawn, so a -inf logit
+ * (desta_mask_tokens_bf16) is never in it, whatever top_p is; -0.0 and +0.0 are one logit value.  A row without a finite
+ * logit keeps nothing and yields token 0. */
 int desta_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int cols, float temperature, float top_p,
                             uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream);
 
@@ -593,7 +596,8 @@ int desta_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int cols, 
  *   7. one draw per row from the kept masses (index-order prefix sum) with desta_rng32(seed, (step << 32) | row), the
  *      counter of desta_sample_top_p_bf16.
  * Sums are fixed point (2^-40 of the row maximum's mass), so results are deterministic per (seed, step, row).
- * keep_mask (optional, uint8 [rows, cols]) exports the kept set (greedy: the pick).  DESTA_EINVAL unless T > 0,
+ * keep_mask (optional, uint8 [rows, cols]) exports the kept set (greedy: the pick): a -inf score is never kept, with every
+ * filter off too.  A row without a finite score keeps nothing and yields token 0, in both modes.  DESTA_EINVAL unless T > 0,
  * 0 < top_p <= 1, top_k >= 0, 0 <= min_p <= 1, repetition_penalty > 0, hist_len >= 0 (hist != NULL and hist_ld >= hist_len
  * when hist_len > 0), and cols <= 262144 when the penalty is active. */
 int desta_sample_bf16(const void* logits, int64_t ld, int rows, int cols, const int64_t* hist, int64_t hist_ld, int hist_len,
