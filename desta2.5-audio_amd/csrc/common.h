@@ -126,10 +126,14 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 // pairs, inside the 30.7 M-pair cross-attention tensor).  Round 4: a second, independently mixed word of the seed (`key`,
 // wave-uniform as well) is xored in BETWEEN the two multiplies of the finaliser, so two seeds select two different functions of the
 // index, and the host derives every site's seed with splitmix64 from (rank seed, forward count, layer, site) instead of packing
-// bit fields.  Checked on the host (numpy restatement, p = 0.1, 4-10 M pairs): keep fraction 0.90004; correlation between the
-// streams of seeds s and s + d for d = 1, 16, 256, 512, 256 * 60, 256 * 120, 256 * 1000 all |r| < 6e-4, and at the shift the
-// additive offset implies (d = 256 * 60: 8 870 912 pairs) 1e-3 — it was exactly 1.0 without the key; seed_hi neighbours 4e-5;
-// adjacent elements 4e-4; every output bit 0.4998..0.5005.
+// bit fields.  Checked on the host by tests/test_dropout_mask_host.py with the numpy restatement of tests/dropout_reference.py
+// (p = 0.1, 2^22 elements, every figure held to 4.5 sigma: 6.6e-4 on the keep fraction, 2.2e-3 on a correlation, 1.1e-3 on a
+// bit): keep fraction 0.89989; correlation between the streams of seeds s and s + d for d = 1, 16, 256, 512, 256 * 60,
+// 256 * 1000 all |r| < 9e-4, and at the shift the additive offset implies (d = 256 * 60: 8 870 912 pairs) 8e-4 — it is exactly
+// 1.0 without the key; seed_hi neighbours 4e-4; adjacent elements 2e-4; every output bit 0.4995..0.5004.  (Earlier figures from
+// an uncommitted script at 4-10 M pairs — 0.90004, 6e-4, 1e-3, 4e-5, 4e-4, 0.4998..0.5005 — are the same statement at other
+// seeds and sizes: all of these are sampling noise around 0.9, 0 and 0.5.)  tests/test_gpu_dropout_mask.py holds every kernel
+// that draws a mask to that restatement, pair for pair.
 __device__ __forceinline__ unsigned desta_rng32(unsigned seed_lo, unsigned seed_hi, unsigned long idx) {
     const unsigned key = (seed_lo ^ (seed_hi * 0x632be5abu)) * 0xc2b2ae35u;
     unsigned x = (unsigned)idx + seed_lo * 0x9e3779b9u + ((unsigned)(idx >> 32) + seed_hi) * 0x85ebca6bu;

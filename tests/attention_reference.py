@@ -29,6 +29,18 @@ moves dS_ij by scale p_ij Ed_i, coherently over the keys of the row (the reason 
 Where every term of a sum is zero (padded query rows, keys in front of kv_start) the M's are zero, the reference is zero and
 the bound collapses to "exactly 0".
 
+Dropout (`keep` bool [B, Hq, Sq, Sk], `drop_scale` = c, the fp32 1 / (1 - p) the kernels multiply by; the DROP kernels of
+csrc/attention.hip).  With pd_ij = c keep_ij p_ij the probabilities that enter P V and dV (the normaliser keeps the FULL sum):
+    O = sum_j pd_ij v_j        dV = sum_i pd_ij dO_i        delta_i = sum_d dO_id O_id (of the dropped O)
+    dS_ij = scale (pd_ij dP_ij - p_ij delta_i) = scale p_ij (c keep_ij dP_ij - delta_i)
+The same derivation holds term by term, no extra term is needed: the kernels round c keep P ONCE to bf16 (forward :423-424 then
+:438; dK / dV :1129 then :1134), so M_O and M_dV take pd for p; dS is rounded once, |error| <= 2^-9 scale (pd |dP| + p |delta|),
+so A_ij = pd_ij |dP_ij| + p_ij |delta_i|; and the error of delta from the rounded O still moves dS_ij by scale p_ij Ed_i (p,
+not pd: the delta term is not masked).  The product with c is one more fp32 rounding, under the doubling with the other fp32
+work.  A dropped pair contributes nothing to M_O, M_dV or the dP part of A, so the bound TIGHTENS by what was dropped.  Measured
+on the host (test_attention_bound_host.py, p = 0.1, mask of tests/dropout_reference.py): the emulation stays inside, ratios in
+that file's docstring.  The mask comes from the caller; tests/dropout_reference.py restates it independently of the kernels.
+
 `emulate()` is the same computation in float64 with a bf16 rounding at each point where the kernels round.  Rounding points,
 by line of csrc/attention.hip (acc_frag, :116-121, is the fp32 -> bf16 conversion of an accumulator into an MFMA operand):
   forward, 4 waves (attn_fwd_k)         P = exp2(s - m), m the RUNNING maximum after the current 64-key tile, unnormalised: :438
@@ -112,7 +124,15 @@ def _softmax2(s2, ok):
     return pu, m, pu.sum(-1, keepdim=True), live
 
 
-def exact(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False):
+def _drop(keep, drop_scale, like):
+    """The factor c * keep on the probabilities that enter P V and dV (1 without dropout): float64, like's shape."""
+    if keep is None:
+        return torch.ones_like(like)
+    assert drop_scale is not None and tuple(keep.shape) == tuple(like.shape)
+    return keep.double() * drop_scale
+
+
+def exact(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False, keep=None, drop_scale=None):
     B, Sq, Hq, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     G = Hq // Hkv
@@ -121,20 +141,22 @@ def exact(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False):
     pu, m, l, live = _softmax2(qh @ kh.transpose(-1, -2) * (scale * LOG2E), ok)
     p = torch.where(live, pu / l.clamp_min(1e-300), torch.zeros_like(pu))
     lse = torch.where(live, m + torch.log2(l.clamp_min(1e-300)), torch.full_like(m, float("inf"))).squeeze(-1)
-    O = p @ vh
+    cm = _drop(keep, drop_scale, p)
+    pd = p * cm                                                        # dropout: what enters P V and dV; the normaliser kept the full sum
+    O = pd @ vh
     dP = gh @ vh.transpose(-1, -2)
     delta = (gh * O).sum(-1, keepdim=True)
-    dS = p * (dP - delta) * scale
-    A = p * (dP.abs() + delta.abs())
+    dS = p * (cm * dP - delta) * scale
+    A = p * (cm * dP.abs() + delta.abs())
     Ed = torch.zeros_like(delta) if o_f32 else 2.0 ** -9 * (gh * O).abs().sum(-1, keepdim=True)
     W = scale * (2.0 ** -8 * A + 2.0 * p * Ed)
     return {
         "O": _rows_last(O), "lse": lse, "live": live.squeeze(-1),
         "dQ": _rows_last(dS @ kh),
         "dK": _rows_last(_group_sum(dS.transpose(-1, -2) @ qh, Hkv)),
-        "dV": _rows_last(_group_sum(p.transpose(-1, -2) @ gh, Hkv)),
-        "M_O": _rows_last(p @ vh.abs()),
-        "M_dV": _rows_last(_group_sum(p.transpose(-1, -2) @ gh.abs(), Hkv)),
+        "dV": _rows_last(_group_sum(pd.transpose(-1, -2) @ gh, Hkv)),
+        "M_O": _rows_last(pd @ vh.abs()),
+        "M_dV": _rows_last(_group_sum(pd.transpose(-1, -2) @ gh.abs(), Hkv)),
         "M_dQ": _rows_last(W @ kh.abs()),
         "M_dK": _rows_last(_group_sum(W.transpose(-1, -2) @ qh.abs(), Hkv)),
     }
@@ -169,7 +191,7 @@ def accepted(ratio, emu_ratio):
     return ratio <= min(2.0, 2.0 * emu_ratio)
 
 
-def emulate(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False, mutation=None, fwd8=False):
+def emulate(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False, mutation=None, fwd8=False, keep=None, drop_scale=None):
     """The conforming kernel (module docstring), optionally with one seeded mutation -> {"O", "dQ", "dK", "dV"} as float64 holding
     bf16 values, "lse" float64, and dK / dV before the store's rounding."""
     assert mutation is None or mutation in MUTATIONS
@@ -205,7 +227,8 @@ def emulate(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False, mutati
         mrun = torch.cummax(tmax, dim=-1).values
     mrun = mrun.repeat_interleave(64, dim=-1)[..., :Sk]
     mrun = torch.where(torch.isfinite(mrun), mrun, m.expand_as(mrun))   # tiles in front of the first visible key: P = 0 whatever the reference
-    pr = rbf(torch.exp2(s2.masked_fill(~ok, float("-inf")) - mrun)) * torch.exp2(mrun - m)
+    cm = _drop(keep, drop_scale, s2)
+    pr = rbf(torch.exp2(s2.masked_fill(~ok, float("-inf")) - mrun) * cm) * torch.exp2(mrun - m)
     linv = torch.where(live, 1.0 / l.clamp_min(1e-300), torch.zeros_like(l))
     O32 = (pr @ vh) * linv
     if mutation == "o_row_scaled":
@@ -219,11 +242,11 @@ def emulate(q, k, v, do, scale, causal=False, kv_start=None, o_f32=False, mutati
     if mutation == "delta_neighbour":
         row = Sq // 2 + 1
         delta[0, 0, row] = delta[0, 0, row - 1]
-    dS = rbf(p * ((gh @ vh.transpose(-1, -2)) - delta) * scale)
+    dS = rbf(p * (cm * (gh @ vh.transpose(-1, -2)) - delta) * scale)
     dK_h = dS.transpose(-1, -2) @ qh
     if mutation == "gqa_short_sum" and G > 1:
         dK_h[0, G - 1, max(Sk - 40, kv_lo)] = 0.0                    # a late key: few rows see it under the causal mask
-    dK32, dV32 = _rows_last(_group_sum(dK_h, Hkv)), _rows_last(_group_sum(rbf(p).transpose(-1, -2) @ gh, Hkv))
+    dK32, dV32 = _rows_last(_group_sum(dK_h, Hkv)), _rows_last(_group_sum(rbf(p * cm).transpose(-1, -2) @ gh, Hkv))
     return {"O": _rows_last(Ob), "lse": lse.squeeze(-1), "dQ": _rows_last(rbf(dS @ kh)), "dK": rbf(dK32), "dV": rbf(dV32),
             "dK_unrounded": dK32, "dV_unrounded": dV32}      # (the accumulators the one-pass kernel's bias sums are taken from)
 
@@ -251,10 +274,10 @@ def operands(case, seed=None):
     }
 
 
-def reference(ops, o_f32=False):
+def reference(ops, o_f32=False, keep=None, drop_scale=None):
     """(exact, {forward kind: emulation}, {forward kind: {tensor: the emulation's worst |err| / bound}}) of operands()' result;
-    forward kind False = the 4-wave forward, True = the 8-wave forward."""
+    forward kind False = the 4-wave forward, True = the 8-wave forward.  keep (bool [B, Hq, Sq, Sk]) and drop_scale: dropout."""
     a = (ops["q"], ops["k"], ops["v"], ops["do"], ops["scale"], ops["causal"], ops["kv_start"])
-    ref = exact(*a, o_f32=o_f32)
-    emu = {f8: emulate(*a, o_f32=o_f32, fwd8=f8) for f8 in (False, True)}
+    ref = exact(*a, o_f32=o_f32, keep=keep, drop_scale=drop_scale)
+    emu = {f8: emulate(*a, o_f32=o_f32, fwd8=f8, keep=keep, drop_scale=drop_scale) for f8 in (False, True)}
     return ref, emu, {f8: {n: worst_ratio(ref, n, emu[f8][n]) for n in TENSORS} for f8 in (False, True)}

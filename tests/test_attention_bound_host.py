@@ -28,6 +28,14 @@ HOST_CASES = [
     (1, 2, 2, 130, 700, 128, False, None),
 ]
 SEED = 20240611
+# the dropout cases of test_gpu_attention_fp64.py (head dim 64, not causal: the Q-Former), p and seed of that test
+DROPOUT_CASES = [
+    (2, 3, 3, 64, 1500, 64, False, None),
+    (2, 3, 3, 40, 520, 64, False, None),
+    (2, 3, 3, 64, 64, 64, False, None),
+    (1, 2, 2, 160, 200, 64, False, None),
+]
+DROPOUT_P, DROPOUT_SEED = 0.1, (3 << 40) | 77
 _REF = {}
 
 
@@ -112,6 +120,36 @@ def test_mutations_are_rejected_per_element(case):
         # the LLM's shape: every one of the five is a bug today's whole-tensor criterion lets through
         for m, r in res.items():
             assert r[0] and r[1], r[2]
+
+
+@pytest.mark.parametrize("case", DROPOUT_CASES)
+def test_dropout_emulation_is_inside_the_bound(case):
+    """Dropout (attention_reference.py, "Dropout"): with the mask of tests/dropout_reference.py planted in reference and
+    emulation alike the unchanged bound formula contains the emulation.  A mask that differs from the reference's in ONE pair
+    of the flat cross-attention case is rejected on dV (a pair is one of a key's 64 terms: 1.96 against the emulation's 0.78)
+    and seen on dK (0.89 against 0.65), but not on O or dQ, where a pair is 1 / 1500 of a row and sits far inside the rounding
+    allowance (0.17 and 0.15 either way): single pairs are the readouts' business (test_dropout_mask_host.py), this criterion
+    holds the arithmetic around the mask.  Measured emulation ratios, p = 0.1: O 0.17-0.57, dQ 0.15-0.36, dK 0.33-0.65,
+    dV 0.45-0.78."""
+    import dropout_reference as DR
+    B, Hq, Hkv, Sq, Sk = case[:5]
+    ops = R.operands(case, seed=SEED + Sq + Sk)
+    keep = torch.from_numpy(DR.attn_keep(DROPOUT_SEED, B, Hq, Sq, Sk, DROPOUT_P))
+    c = DR.drop_scale(DROPOUT_P)
+    ref, emu, ratios = R.reference(ops, keep=keep, drop_scale=c)
+    print(case, "dropout", {n: round(r, 3) for n, r in ratios[False].items()})
+    for n in R.TENSORS:
+        assert ratios[False][n] < 1.0, (n, ratios[False][n])
+        assert R.rel_l2(emu[False][n], ref[n]) < R.OLD_LIMIT[n]
+    plain = R.exact(*_args(ops))
+    assert not torch.equal(plain["O"], ref["O"]) and bool((ref["M_O"] <= c * plain["M_O"] * (1 + 1e-12)).all())
+    if case[:5] == (2, 3, 3, 64, 1500):
+        wrong = keep.clone()
+        wrong[1, 2, 33, 777] = ~wrong[1, 2, 33, 777]
+        out = R.emulate(*_args(ops), keep=wrong, drop_scale=c)
+        r = {n: R.worst_ratio(ref, n, out[n]) for n in R.TENSORS}
+        print("  one pair of the mask flipped:", {n: round(x, 2) for n, x in r.items()}, "against", {n: round(x, 2) for n, x in ratios[False].items()})
+        assert not R.accepted(r["dV"], ratios[False]["dV"])
 
 
 def test_every_mutation_passes_the_old_criterion_somewhere_and_is_rejected_there():

@@ -11,8 +11,10 @@ backward (dQ, dK, dV) and the dQ-only backward once.  Asserted for O, dQ, dK, dV
 4-wave kernel; the factor 2 is for what the emulation leaves out: fp32 accumulation order, exp2, lse in fp32).  Where the reference is exactly 0
 (padded query rows, keys in front of kv_start) the output must be exactly 0; every output buffer starts as 7.0, so a region a
 kernel does not write fails too.  lse (log2 domain): |lse - fp64| <= 1e-4 (1 + |fp64|) on rows with a visible key, +inf elsewhere.
-Further cases: O_f32 feeding delta (bound with Ed = 0); dkv_transposed + dkv_bias_grad; and, in test_gpu_ops.py, the spike
-operands of test_attention_deferred_rescale_threshold.
+Further cases: O_f32 feeding delta (bound with Ed = 0); dkv_transposed + dkv_bias_grad; dropout (p = 0.1, the DROP kernels, with the
+mask of tests/dropout_reference.py planted in reference and emulation: test_attention_dropout_fp64, whose kernels sit on the
+emulation too: O 0.171-0.604, dQ 0.179-0.379, dK 0.351-0.720, dV 0.390-0.779, profiles/r24_dropout_mask_tests.log); and, in
+test_gpu_ops.py, the spike operands of test_attention_deferred_rescale_threshold.
 
 Switches.  desta_attention_set_option / desta_attention_set_concurrent_bwd select kernel instantiations and launch orders; each
 setting is run on the ATTN_CASES whose dispatch it changes (worked out from desta_attention_fwd / desta_attention_bwd,
@@ -65,6 +67,8 @@ import pytest
 import torch
 
 import attention_reference as R
+import dropout_reference as DR
+from test_attention_bound_host import DROPOUT_CASES, DROPOUT_P, DROPOUT_SEED
 from test_gpu_ops import ATTN_CASES
 
 pytestmark = pytest.mark.gpu
@@ -85,11 +89,15 @@ def hip():
 class Prepared:
     """Operands, fp64 reference, emulation ratios and device copies of one case: built once per module."""
 
-    def __init__(self, case, o_f32, reference=True):
-        self.case, self.o_f32 = case, o_f32
+    def __init__(self, case, o_f32, reference=True, dropout=None):
+        self.case, self.o_f32, self.dropout = case, o_f32, dropout
         self.ops = R.operands(case)
         if reference:                                      # (tools/attention_bits.py digests the outputs: no reference)
-            self.ref, self.emu, self.emu_ratio = R.reference(self.ops, o_f32=o_f32)
+            keep = drop_scale = None
+            if dropout is not None:                        # (p, seed): the mask of tests/dropout_reference.py, not the kernels'
+                B, Hq, Hkv, Sq, Sk = case[:5]
+                keep, drop_scale = torch.from_numpy(DR.attn_keep(dropout[1], B, Hq, Sq, Sk, dropout[0])), DR.drop_scale(dropout[0])
+            self.ref, self.emu, self.emu_ratio = R.reference(self.ops, o_f32=o_f32, keep=keep, drop_scale=drop_scale)
         self.dev = None
         self.default = None                                # outputs of the default switches (test_attention_fwd_bwd_fp64 or first use)
 
@@ -105,10 +113,10 @@ class Prepared:
 _CASES = {}
 
 
-def _prepared(case, o_f32=False):
-    key = (repr(case), o_f32)
+def _prepared(case, o_f32=False, dropout=None):
+    key = (repr(case), o_f32, dropout)
     if key not in _CASES:
-        _CASES[key] = Prepared(case, o_f32)
+        _CASES[key] = Prepared(case, o_f32, dropout=dropout)
     return _CASES[key]
 
 
@@ -122,7 +130,8 @@ def _run(hip, P):
     o32 = torch.full((B * Sq, wq), 7.0, dtype=torch.float32, device="cuda") if P.o_f32 else None
     lse = torch.full((B, Hq, Sq), 7.0, device="cuda")
     d = hip.attn_desc(qd, kvd, kvd, o, lse, batch=B, hq=Hq, hkv=Hkv, sq=Sq, sk=Sk, hd=D, scale=o_["scale"], causal=causal,
-                      kv_start=kvs, q_off=o_["q_off"], k_off=o_["k_off"], v_off=o_["v_off"], o_f32=o32)
+                      kv_start=kvs, q_off=o_["q_off"], k_off=o_["k_off"], v_off=o_["v_off"], o_f32=o32,
+                      dropout_p=P.dropout[0] if P.dropout else 0.0, dropout_seed=P.dropout[1] if P.dropout else 0)
     hip.attention_fwd(d)
     if o_["fused"]:
         dqkv = torch.full((B * Sq, wq + 2 * wkv), 7.0, dtype=torch.bfloat16, device="cuda")
@@ -211,6 +220,18 @@ def _default_run(hip, P):
 def test_attention_fwd_bwd_fp64(hip, case):
     P = _prepared(case)
     _check(P, _default_run(hip, P), "default", _fwd8(case))
+
+
+@pytest.mark.parametrize("case", DROPOUT_CASES)
+def test_attention_dropout_fp64(hip, case):
+    """The DROP kernels under the same assertion, FACTOR and all: random operands, p = 0.1, the mask planted in the fp64 reference
+    and the emulation is tests/dropout_reference.py's restatement, not desta_dropout_mask.  No dropout case reaches an 8-wave
+    kernel (desta_attention_fwd / _bwd send dropout to the 4- and 2-wave kernels at any seq_q), so the emulation is the 4-wave
+    one.  Paths: 64 x 1500 and 40 x 520 attn_fwd_k<64,true,2> + attn_bwd_q64_k<true,false>; 64 x 64 (fused q|k|v buffer)
+    attn_fwd_k<64,true,2> + attn_bwd_dq_k<64,true,2> + attn_bwd_dkdv_k<64,true>; 160 x 200 attn_fwd_k<64,true> +
+    attn_bwd_dq_k<64,true> (4 waves) + attn_bwd_dkdv_k<64,true>; the dQ-only backward takes attn_bwd_dq_k in every case."""
+    P = _prepared(case, dropout=(DROPOUT_P, DROPOUT_SEED))
+    _check(P, _run(hip, P), f"dropout p={DROPOUT_P}", False)
 
 
 def _switch_cases(which):
