@@ -2049,3 +2049,296 @@ extern "C" int desta_gemm_wide_nt(const desta_gemm_desc* d, const float* b_scale
     g_last_kernel = 3;
     return DESTA_OK;
 }
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------------------
+// Weight-only MXFP4 GEMM, 1 <= M <= 64 (desta_gemm_w4a16_nt): the decode projections on weights stored as OCP e2m1 nibbles with
+// one e8m0 scale per 32 consecutive k (quant_mxfp4.hip).  Written around what the FP8 form measured: a 16-column tile re-reads
+// 32 B of activations per lane and 64-chunk whatever the weight format, which at 4 bits is 4 activation bytes through L1 / L2
+// per weight byte.  So an item here is always 64 weight rows (T = 4 MFMA tiles) over all M rows (MF = ceil(M / 16) activation
+// fragments): an activation fragment is fetched once and feeds four weight tiles, and lanes whose row does not exist
+// (16 f + r >= M) fetch nothing.
+// K order: a K-chunk is 128 elements.  Lane (r, g) loads the 16 bytes of weight row r that hold k = 128 c + 32 g .. + 31: exactly
+// one scale block, so ONE e8m0 byte is the scalef32 operand of all 16 v_cvt_scalef32_pk_bf16_fp4 of the load (exact: code * 2^e
+// is a bf16 value).  Dword j of the load (k = 128 c + 32 g + 8 j .. + 7) becomes the bf16x8 fragment of MFMA j, j = 0 .. 3, and the
+// lane's activation fragments are the matching 4 x 16 bytes A[m, 128 c + 32 g + 8 j ..]: both MFMA operands carry the same k per
+// (lane group, element), which is all a 16x16x32 MFMA needs.  K % 128 == 64: in the last chunk lane groups 2, 3 hold zeros and
+// load nothing.
+// Reduction chain (fixed, grid-independent): wave w of the 8 takes chunks w, w + 8, .. of the item's K-slice, four dependent
+// MFMAs each; the 8 partial tiles are summed in wave order through LDS; with ks > 1 K-slices the raw fp32 sums go to the
+// workspace slab [ks][M][weight rows] and gemm_bf16_nt_skinny_wide_fixup_kernel (b_scale = null: the sums are already scaled)
+// adds them in slice order and runs the epilogue.  ks is the wide kernel's rule on 128-chunks: a function of the tile and chunk
+// counts only.  The grid is persistent and the two-stage weight pipeline runs across items.
+// Activations: MF <= 2 double-buffers them beside the weights; MF >= 3 keeps ONE activation stage (64 VGPRs at MF = 4) that is
+// loaded in front of the next group's weight loads, so waiting for it does not wait for them; RMS (MF = 1, M * 2K <= 64 KiB)
+// normalises the rows into LDS once per block as the 16-row kernel does and reads the fragments from there.
+// SWIGLU: an item is 32 gate rows (tiles 0, 1) and the 32 matching up rows (tiles 2, 3), the wide kernel's pairing.
+#ifndef W4_SLICE_CHUNKS
+#define W4_SLICE_CHUNKS 8                                               // fewest 128-chunks a K-slice holds (one per wave)
+#endif
+struct W4Stage { u32x4 wq[4]; unsigned sc[4]; };
+
+// 8 e2m1 nibbles (element i in bits 4i .. 4i + 3) * scale -> one bf16x8 MFMA fragment
+__device__ __forceinline__ bf16x8 e2m1x8_to_bf16(unsigned q, float scale) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+    bf16x8 o;
+    const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 1);
+    const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, scale, 3);
+    o[0] = a[0]; o[1] = a[1]; o[2] = b[0]; o[3] = b[1]; o[4] = c[0]; o[5] = c[1]; o[6] = d[0]; o[7] = d[1];
+    return o;
+}
+
+template <int MF, bool SWIGLU, bool RMS>
+__global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const uint8_t* __restrict__ bsc, long ldsc, int ntiles, int ks, int cps,
+                                                            float* part) {
+    static_assert(!RMS || MF == 1, "the RMS prologue stages M <= 16 rows");
+    constexpr int T = 4;
+    constexpr bool XS = MF <= 2 && !RMS;                                 // activations double-buffered beside the weights
+    constexpr int RED_BYTES = 8 * T * MF * 1024;
+    __shared__ __attribute__((aligned(16))) char smem[RED_BYTES + (RMS ? SKINNY_XS_BYTES : 0)];
+    f32x4 (*red)[T * MF][64] = (f32x4 (*)[T * MF][64])smem;              // red[wave][t * MF + f][lane]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int ntot = SWIGLU ? 2 * p.N : p.N;                             // weight rows = columns of the partial slab
+    const char* Bq = (const char*)p.B + g * 16;                          // two elements per byte: 32 k of this lane group
+    const uint8_t* Sq = bsc + g;
+    const bf16_t* ap[MF];
+    bool xok[MF];
+#pragma unroll
+    for (int f = 0; f < MF; ++f) {
+        xok[f] = f * 16 + r < p.M;
+        ap[f] = p.A + (long)(xok[f] ? f * 16 + r : 0) * p.lda + g * 32;
+    }
+    const int rr = xok[0] ? r : 0;
+    const char* xrow = smem + RED_BYTES + rr * (p.K * 2);                // this lane's fragment row in LDS (RMS only)
+    const int nchunks = (p.K + 127) >> 7;
+    const int gpt = (cps + 7) >> 3;                                      // groups (one chunk per wave) per item
+    const int items = ntiles * ks;
+    const int my_items = ((int)blockIdx.x < items) ? (items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+    const int G = my_items * gpt;
+    f32x4 acc[T][MF];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int f = 0; f < MF; ++f) acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    W4Stage sa, sb;
+    bf16x8 xa[MF][4], xb[MF][4];
+    WideCursor lc = {(int)blockIdx.x, 0, (int)blockIdx.x % ntiles, (int)blockIdx.x / ntiles}, mc = lc;
+
+    auto advance = [&](WideCursor& c) {
+        if (++c.grp == gpt) { c.grp = 0; c.item += (int)gridDim.x; c.tile = c.item % ntiles; c.slice = c.item / ntiles; }
+    };
+    // weight row of MFMA tile t, row q of it; ok = it exists
+    auto wrow = [&](int tile, int t, int q, bool& ok) -> int {
+        if (SWIGLU) {
+            const int n = tile * 32 + (t & 1) * 16 + q;
+            ok = n < p.N;
+            return (t >= 2 ? p.N : 0) + min(n, p.N - 1);
+        }
+        const int n = tile * 64 + t * 16 + q;
+        ok = n < p.N;
+        return min(n, p.N - 1);
+    };
+    // this lane's 32 k of the cursor's chunk lie inside the K-slice and inside K
+    auto chunk_of = [&](const WideCursor& c, bool& live) -> int {
+        const int cc = c.slice * cps + wave + c.grp * 8;
+        live = cc < min((c.slice + 1) * cps, nchunks) && cc * 128 + g * 32 < p.K;
+        return cc;
+    };
+#define W4_XLOAD(X, CUR)                                                                    \
+    {                                                                                       \
+        bool live;                                                                          \
+        const int cx = chunk_of(CUR, live);                                                 \
+        _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                    \
+            if (live && xok[f]) {                                                           \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) X[f][j] = *(const bf16x8*)(ap[f] + (long)cx * 128 + 8 * j); \
+            } else {                                                                        \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) X[f][j] = bf16x8{};           \
+            }                                                                               \
+        }                                                                                   \
+    }
+#define W4_LOAD(S, X)                                                                       \
+    {                                                                                       \
+        bool live;                                                                          \
+        const int cc = chunk_of(lc, live);                                                  \
+        _Pragma("unroll") for (int t = 0; t < T; ++t) {                                     \
+            bool ok;                                                                        \
+            const long row = wrow(lc.tile, t, r, ok);        /* clamped rows: computed, never stored */ \
+            if (live) {                                                                     \
+                S.wq[t] = *(const u32x4*)(Bq + row * p.ldb + (long)cc * 64);                \
+                S.sc[t] = Sq[row * ldsc + cc * 4];                                          \
+            } else {                                                                        \
+                S.wq[t] = u32x4{0u, 0u, 0u, 0u};                                            \
+                S.sc[t] = 127u;                                                             \
+            }                                                                               \
+        }                                                                                   \
+        if (XS) W4_XLOAD(X, lc)                                                             \
+        advance(lc);                                                                        \
+    }
+#define W4_MMA(S, X)                                                                        \
+    {                                                                                       \
+        if (RMS) {                                                                          \
+            bool live;                                                                      \
+            const int slot = chunk_of(mc, live) * 16 + g * 4;                               \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j)                                   \
+                X[0][j] = (live && xok[0]) ? *(const bf16x8*)(xrow + (((slot + j) ^ rr) << 4)) : bf16x8{}; \
+        }                                                                                   \
+        _Pragma("unroll") for (int t = 0; t < T; ++t) {                                     \
+            const float sf = __uint_as_float(S.sc[t] << 23);                                \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                 \
+                const bf16x8 wf = e2m1x8_to_bf16(S.wq[t][j], sf);                           \
+                _Pragma("unroll") for (int f = 0; f < MF; ++f)                              \
+                    acc[t][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, X[f][j], acc[t][f], 0, 0, 0); \
+            }                                                                               \
+        }                                                                                   \
+        if (mc.grp == gpt - 1) finish_item(mc.tile, mc.slice);                              \
+        advance(mc);                                                                        \
+    }
+    // the 8 waves' partial tiles, summed in wave order
+    auto reduced = [&](int t, int f) -> f32x4 {
+        f32x4 sum = red[0][t * MF + f][lane];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) sum += red[w][t * MF + f][lane];
+        return sum;
+    };
+    auto finish_item = [&](int tile, int slice) {
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int f = 0; f < MF; ++f) { red[wave][t * MF + f][lane] = acc[t][f]; acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        __syncthreads();
+        if (ks > 1) {                                                    // raw sums of this K-slice; the fix-up launch finishes them
+            for (int u = wave; u < T * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int row = wrow(tile, t, g * 4, ok);                // N % 4 == 0: the four rows exist together
+                if (ok && m < p.M) *(f32x4*)(part + ((long)slice * p.M + m) * ntot + row) = reduced(t, f);
+            }
+        } else if (SWIGLU) {
+            for (int u = wave; u < 2 * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int n = wrow(tile, t, g * 4, ok);
+                if (ok && m < p.M) *(u16x4*)((bf16_t*)p.C + (long)m * p.ldc + n) = swiglu4_bf16(reduced(t, f), reduced(t + 2, f), p.alpha);
+            }
+        } else {
+            for (int u = wave; u < T * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int n = wrow(tile, t, g * 4, ok);
+                if (ok && m < p.M) epilogue4(p, 0, m, n, reduced(t, f));
+            }
+        }
+        __syncthreads();                                                 // red is free again before the next item's partial tiles land
+    };
+
+    if (G > 0) W4_LOAD(sa, xa)
+    if (RMS) {
+        for (int m = wave; m < p.M; m += 8) {                            // one wave per row, same summation order as rmsnorm_fwd_k
+            const bf16_t* xr = p.A + (long)m * p.lda;
+            float q = 0.f;
+#pragma unroll 4
+            for (int c = lane * 8; c < p.K; c += 512) {
+                const u16x8 v = *(const u16x8*)(xr + c);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float f = bf2f(v[e]); q += f * f; }
+            }
+            const float rstd = rsqrtf(wave_sum(q) / (float)p.K + p.rms_eps);
+#pragma unroll 2
+            for (int c = lane * 8; c < p.K; c += 512) {
+                const u16x8 v = *(const u16x8*)(xr + c);
+                const float4 w0 = *(const float4*)(p.rms_w + c), w1 = *(const float4*)(p.rms_w + c + 4);
+                const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+                u16x8 o;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = f2bf(wv[e] * bf2f(f2bf(bf2f(v[e]) * rstd)));
+                *(u16x8*)(smem + RED_BYTES + m * (p.K * 2) + (((c >> 3) ^ m) << 4)) = o;
+            }
+        }
+        __syncthreads();
+    }
+    for (int gi = 0; gi < G; gi += 2) {
+        if (!XS && !RMS) W4_XLOAD(xa, mc)
+        if (gi + 1 < G) W4_LOAD(sb, xb)
+        W4_MMA(sa, xa)
+        if (gi + 1 < G) {
+            if (!XS && !RMS) W4_XLOAD(xa, mc)
+            if (gi + 2 < G) W4_LOAD(sa, xa)
+            if (XS) W4_MMA(sb, xb) else W4_MMA(sb, xa)
+        }
+    }
+#undef W4_XLOAD
+#undef W4_LOAD
+#undef W4_MMA
+}
+
+}  // namespace
+
+// Weight-only MXFP4 form of the decode projections, 1 <= M <= 64 in one entry point: gemm_w4a16_nt_kernel with MF = ceil(M / 16).
+// What a decode step does not ask for is rejected by name, as desta_gemm_wide_nt does.
+extern "C" int desta_gemm_w4a16_nt(const desta_gemm_desc* d, const uint8_t* b_scale_e8m0, int64_t ld_scale, void* stream) {
+    DESTA_CHECK_ARG(d && d->A && d->B && d->C, "gemm_w4: null operand");
+    DESTA_CHECK_ARG(b_scale_e8m0, "gemm_w4: null scale pointer");
+    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm_w4: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
+    DESTA_CHECK_ARG(d->M <= 64, "gemm_w4: M=%d, the weight-only MXFP4 kernel is the decode path (M <= 64)", d->M);
+    DESTA_CHECK_ARG(d->act == 0 || d->act == 4, "gemm_w4: act %d unsupported (0, or 4 = SwiGLU over concatenated gate|up rows)", d->act);
+    DESTA_CHECK_ARG(d->K % BK == 0, "gemm_w4: K=%d must be a multiple of %d", d->K, BK);
+    DESTA_CHECK_ARG(d->N % 4 == 0, "gemm_w4: N=%d must be a multiple of 4", d->N);
+    DESTA_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 16 == 0 && d->ldb >= d->K / 2 && d->ldc % 4 == 0 && ld_scale >= d->K / 32,
+                    "gemm_w4: lda must be a multiple of 8, ldb (bytes) a multiple of 16 and >= K / 2, ldc a multiple of 4, ld_scale >= K / 32");
+    DESTA_CHECK_ARG(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0), "gemm_w4: operands must be 16-byte aligned");
+    DESTA_CHECK_ARG(d->batch == 1, "gemm_w4: batch %d unsupported (1)", d->batch);
+    DESTA_CHECK_ARG(!d->bias && !d->preact && !d->aux && d->dropout_p == 0.f && !d->trans_a && !d->trans_b && !d->rope_cos_sin,
+                    "gemm_w4: bias, preact, aux, dropout, transposed operands and the rotary epilogue are unsupported");
+    DESTA_CHECK_ARG(!d->residual || (d->ldr % 4 == 0 && !d->residual_f32), "gemm_w4: the residual is bf16 and ldr a multiple of 4");
+    DESTA_CHECK_ARG(d->act != 4 || (!d->out_f32 && !d->residual), "gemm_w4: act 4 needs a bf16 output and no residual");
+    DESTA_CHECK_ARG(!d->a_rms_weight || (d->M <= 16 && (size_t)d->M * 2 * (size_t)d->K <= (size_t)SKINNY_XS_BYTES && d->K % 512 == 0),
+                    "gemm_w4: a_rms_weight (fused RMSNorm of A) needs M <= 16, M*2K <= %d bytes of LDS and K %% 512 == 0", SKINNY_XS_BYTES);
+    GemmArgs a = {};
+    a.A = (const bf16_t*)d->A; a.B = (const bf16_t*)d->B; a.C = d->C;
+    a.M = d->M; a.N = d->N; a.K = d->K;
+    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
+    a.res = d->residual; a.ldr = d->ldr;
+    a.act = d->act; a.out_f32 = d->out_f32; a.alpha = d->alpha; a.drop_scale = 1.0f;
+    a.rms_w = d->a_rms_weight; a.rms_eps = d->a_rms_eps;
+    // K-slices: enough items for one block per CU, at least 8 chunks of 128 (one per wave) each.  A function of the tile and chunk
+    // counts alone, so every M and act 4 against its plain 2N-row form sum in the same order.
+    const int swiglu = d->act == 4;
+    const int ntiles = swiglu ? (d->N + 31) / 32 : (d->N + 63) / 64, nchunks = (d->K + 127) / 128;
+    const long ntot = swiglu ? 2L * d->N : d->N;
+    int ks = 256 / ntiles;
+    if (ks > nchunks / W4_SLICE_CHUNKS) ks = nchunks / W4_SLICE_CHUNKS;
+    if (ks > 8) ks = 8;
+    if (ks < 1) ks = 1;
+    // the last 4 KiB of the workspace belong to the tile kernels' tickets and queue counters
+    const bool ws_ok = d->workspace && ((uintptr_t)d->workspace % 16) == 0 && (size_t)ks * d->M * ntot * sizeof(float) + 4096 <= d->workspace_bytes;
+    DESTA_CHECK_ARG(ks == 1 || ws_ok, "gemm_w4: N=%d K=%d is cut into %d K-slices and needs %zu workspace bytes", d->N, d->K, ks,
+                    (size_t)ks * d->M * ntot * sizeof(float) + 4096);
+    const int cps = (nchunks + ks - 1) / ks;
+    float* part = ks > 1 ? (float*)d->workspace : nullptr;
+    const int mf = (d->M + 15) / 16;
+    // one block per CU (every form holds more than 128 VGPRs or more than 80 KiB of LDS) where the 16-row bf16 kernel has two
+    const int items = ntiles * ks, blocks = g_skinny_blocks > 1 ? g_skinny_blocks / 2 : 1;
+    const dim3 grid(items < blocks ? items : blocks);
+    hipStream_t st = (hipStream_t)stream;
+#define W4_LAUNCH(MF_, SW_, RMS_) \
+    hipLaunchKernelGGL((gemm_w4a16_nt_kernel<MF_, SW_, RMS_>), grid, dim3(512), 0, st, a, b_scale_e8m0, (long)ld_scale, ntiles, ks, cps, part)
+#define W4_LAUNCH_MF(MF_) do { if (swiglu) W4_LAUNCH(MF_, true, false); else W4_LAUNCH(MF_, false, false); } while (0)
+    if (mf == 1 && a.rms_w) { if (swiglu) W4_LAUNCH(1, true, true); else W4_LAUNCH(1, false, true); }
+    else if (mf == 1) W4_LAUNCH_MF(1);
+    else if (mf == 2) W4_LAUNCH_MF(2);
+    else if (mf == 3) W4_LAUNCH_MF(3);
+    else W4_LAUNCH_MF(4);
+#undef W4_LAUNCH_MF
+#undef W4_LAUNCH
+    DESTA_CHECK_LAUNCH("gemm_w4a16_nt");
+    if (ks > 1) {                                                        // the sums in the slab are already scaled: no b_scale
+        const dim3 fgrid((unsigned)(((long)d->M * (d->N / 4) + 255) / 256));
+        if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<true>), fgrid, dim3(256), 0, st, a, ks, part, (const float*)nullptr);
+        else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<false>), fgrid, dim3(256), 0, st, a, ks, part, (const float*)nullptr);
+        DESTA_CHECK_LAUNCH("gemm_w4a16_nt_fixup");
+    }
+    g_last_kernel = 3;
+    return DESTA_OK;
+}

@@ -196,6 +196,57 @@ def gemm_wide(A, B, out, M, N, K, *, scale=None, lda=None, ldb=None, ldc=None, r
     return out
 
 
+_quantize_rows_mxfp4 = _sig("desta_quantize_rows_mxfp4", vp, i32, i32, i64, vp, i64, vp, i64, vp)
+_gemm_w4 = _sig("desta_gemm_w4a16_nt", C.POINTER(GemmDesc), vp, i64, vp)
+GEMM_W4_CALLS = 0                  # weight-only MXFP4 projections issued by this process
+
+
+def quantize_rows_mxfp4(w, rows=None, cols=None, ld=None, q=None, ldq=None, scale=None, lds=None):
+    """bf16 weight [rows, cols] (row stride ld, cols % 32 == 0) -> (q [rows, cols / 2] uint8, scale [rows, cols / 32] uint8): OCP
+    MXFP4.  Byte j of a row of q holds the e2m1 codes of elements 2j (bits 3..0) and 2j + 1 (bits 7..4); a scale byte b is e8m0,
+    2^(b - 127), for 32 consecutive k, the smallest power of two with amax / scale <= 7 (all-zero block: 127).  Round to nearest,
+    ties to the even code, the magnitude saturating at 6.  code * scale is exact in bf16."""
+    assert w.dtype == torch.bfloat16 and w.dim() == 2 and w.stride(1) == 1
+    rows = w.shape[0] if rows is None else rows
+    cols = w.shape[1] if cols is None else cols
+    ld = w.stride(0) if ld is None else ld
+    q = torch.empty(rows, (cols // 2 + 15) // 16 * 16, dtype=torch.uint8, device=w.device)[:, :cols // 2] if q is None else q
+    scale = torch.empty(rows, cols // 32, dtype=torch.uint8, device=w.device) if scale is None else scale
+    ldq = q.stride(0) if ldq is None else ldq
+    lds = scale.stride(0) if lds is None else lds
+    check(_quantize_rows_mxfp4(p(w), rows, cols, ld, p(q), ldq, p(scale), lds, stream()), "desta_quantize_rows_mxfp4")
+    return q, scale
+
+
+def gemm_w4(A, B4, s, out, M, N, K, *, lda=None, ldb=None, ldc=None, ld_scale=None, residual=None, ldr=None, act=0, alpha=1.0,
+            a_rms_weight=None, a_rms_eps=0.0):
+    """out[M,N] = act(alpha * A[M,K] @ dequant(B4, s)[N,K]^T) + residual for 1 <= M <= 64: the decode projections on weights
+    stored as OCP MXFP4 (`quantize_rows_mxfp4`; ldb and ld_scale in bytes).  act 4: B4 / s hold the concatenated gate|up rows
+    [2N].  fp32 accumulation in a fixed order of its own (128-element K chunks): held to the fp64 bound of the operation, not
+    bit-equal to `gemm` on the dequantised weight.  K-slice partial sums go through the stream's GEMM workspace."""
+    global GEMM_W4_CALLS
+    d = GemmDesc()
+    d.A, d.B, d.C = p(A), p(B4), p(out)
+    d.M, d.N, d.K, d.batch = M, N, K, 1
+    d.lda = K if lda is None else lda
+    d.ldb = (B4.stride(0) if B4 is not None and B4.dim() == 2 else K // 2) if ldb is None else ldb
+    d.ldc = N if ldc is None else ldc
+    d.residual = p(residual)
+    d.ldr = N if ldr is None else ldr
+    d.residual_f32 = int(residual is not None and residual.dtype == torch.float32)
+    d.act = act
+    d.out_f32 = int(out.dtype == torch.float32)
+    d.ldp = N
+    d.alpha = alpha
+    d.a_rms_weight, d.a_rms_eps = p(a_rms_weight), a_rms_eps
+    d.workspace, d.workspace_bytes = _workspace(A.device, stream()).data_ptr(), GEMM_WS_BYTES
+    if ld_scale is None:
+        ld_scale = s.stride(0) if s is not None and s.dim() == 2 else K // 32
+    check(_gemm_w4(C.byref(d), p(s), ld_scale, stream()), "desta_gemm_w4a16_nt")
+    GEMM_W4_CALLS += 1
+    return out
+
+
 _gemm_prof = None
 _gemm_ws = {}                      # (device, stream) -> split-K scratch
 GEMM_WS_BYTES = (64 << 20) + 4096

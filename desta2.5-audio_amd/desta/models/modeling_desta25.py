@@ -1589,7 +1589,7 @@ class CausalLMHIP:
         self.skip_dead_rows = True                  # A/B switch (bench.py --no-dead-row-skip): last layer on the target tail, layer-0 dX on the audio rows
         self.fuse_swiglu = True                     # A/B switch (bench.py --no-swiglu-fusion): silu(gate) * up and its backward inside the gate|up / d(act) GEMM epilogues
         self.decode_weights = "bf16"                # `set_decode_weights`: what the projections of a KV-cached decode step stream
-        self.head8 = None
+        self.head8 = self.head4 = None
         self.kv_cache_kind = "bf16"                 # `set_kv_cache`: what generate()'s KV cache holds
         self.kv_cache = self.kv_scale = self.kv_scale_v = None
         self._gen_shape = self._gen_kind = None     # (B, Smax) and cache kind of `_gen_alloc`'s buffers; None = allocate at the next generate()
@@ -1627,18 +1627,26 @@ class CausalLMHIP:
 
     # -- weight-only FP8 (e4m3) decode: a second, half-size copy of the frozen decode-side weights -------------------------------
     DECODE_WEIGHT_KINDS = ("bf16", "fp8")
+    DECODE_WEIGHT_KINDS_MX = ("mxfp4",)             # block-scaled kinds: OCP MXFP4 (e2m1 nibbles, one e8m0 scale per 32 k)
 
     def set_decode_weights(self, kind: str) -> None:
-        """What `decode_step` streams: "bf16" (default, the reference's arithmetic) or "fp8" = OCP e4m3 bytes with one power-of-two
-        scale per output row (W8A16; activations, KV cache and accumulation unchanged).  The copies are made at the first decode
-        step that needs them and freed by "bf16".  The prompt pass and training always use the bf16 weights."""
-        if kind not in self.DECODE_WEIGHT_KINDS:
-            raise ValueError(f"decode_weights must be one of {self.DECODE_WEIGHT_KINDS}, got {kind!r}")
+        """What `decode_step` streams: "bf16" (default, the reference's arithmetic), "fp8" = OCP e4m3 bytes with one power-of-two
+        scale per output row (W8A16) or "mxfp4" = OCP e2m1 nibbles with one e8m0 scale per 32 consecutive k (W4A16, round to
+        nearest, no calibration); activations, KV cache and accumulation unchanged.  The copies are made at the first decode step
+        that needs them; "bf16" frees both sets, "fp8" and "mxfp4" free each other's.  The prompt pass and training always use the
+        bf16 weights."""
+        kinds = self.DECODE_WEIGHT_KINDS + self.DECODE_WEIGHT_KINDS_MX
+        if kind not in kinds:
+            raise ValueError(f"decode_weights must be one of {kinds}, got {kind!r}")
         self.decode_weights = kind
-        if kind == "bf16":
+        if kind != "fp8":
             self.head8 = None
             for ly in self.layers:
                 ly.pop("q8", None)
+        if kind != "mxfp4":
+            self.head4 = None
+            for ly in self.layers:
+                ly.pop("q4", None)
 
     # -- FP8 (e4m3) KV cache: bytes + one power-of-two scale per (row, slot, K-or-V head) (include/desta_hip.h) ------------------
     KV_CACHE_KINDS = ("bf16", "fp8")
@@ -1668,6 +1676,16 @@ class CausalLMHIP:
         for ly in self.layers:
             ly["q8"] = {n: H.quantize_rows_e4m3(ly[n]) for n in names}
         self.head8 = H.quantize_rows_e4m3(self.head)
+
+    def _mxfp4_decode_weights(self) -> None:
+        """`_fp8_decode_weights` for "mxfp4": (nibbles [rows, K / 2], e8m0 scales [rows, K / 32]) of the same weights into ly["q4"]
+        and `head4`; with adapters the q|k|v projection stays bf16."""
+        if self.head4 is not None:
+            return
+        names = ("wo", "wgu", "wd") if self.lora is not None else ("wqkv", "wo", "wgu", "wd")
+        for ly in self.layers:
+            ly["q4"] = {n: H.quantize_rows_mxfp4(ly[n]) for n in names}
+        self.head4 = H.quantize_rows_mxfp4(self.head)
     # -- LoRA adapters on q/k/v (reference: peft, modeling_desta25.py:720-729; published layer: y = W x + (alpha / r) B A drop(x)) --------
     LORA_KP = 64                                    # the three rank-r adapters side by side, padded to one 64-wide GEMM K block
 
@@ -2040,8 +2058,8 @@ class CausalLMHIP:
     def _step_rows(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, layer_hook=None) -> torch.Tensor:
         """The KV-cached step, the one body of `decode_step` (w = 1) and `verify_step` (w = k + 1): `tokens` [B, w] (ids), row j of
         a sequence sits at cache slot cur + j (position = slot - left pad); returns logits [B * w, Vp] (batch-major), row j for
-        slot cur + j + 1.  The row count M = B * w picks the buffer set, the projection kernel (M > 16: `gemm_wide`, else `gemm_w8`
-        on FP8 decode weights, else `gemm`; the LoRA-merged q|k|v stays on `gemm`) and the RMSNorm fusion (`H.rms_fusable`); the
+        slot cur + j + 1.  The row count M = B * w picks the buffer set, the projection kernel (MXFP4 decode weights: `gemm_w4` at
+        every M; else M > 16: `gemm_wide`, else `gemm_w8` on FP8 decode weights, else `gemm`; the LoRA-merged q|k|v stays on `gemm`) and the RMSNorm fusion (`H.rms_fusable`); the
         rotated K | V go to slots [cur, cur + w) of the cache.  w picks the attention alone: w = 1 reads slots [kv_start, cur] without
         a mask, through the kv8 kernel under the FP8 cache, the split-KV kernel from H.DECODE_ATTN_MIN_KEYS keys on where the
         geometry allows, else the forward kernel; w > 1 (bf16 cache) reads slots [kv_start, cur + w) through the forward kernel under
@@ -2059,8 +2077,14 @@ class CausalLMHIP:
         if fp8:
             self._fp8_decode_weights()
 
-        def mm(xin, w_, w8, out, N, K, wide=M > 16, **kw):   # one projection on the bf16 weight, or on its e4m3 copy (q, scale)
-            if wide:                                    # M = 17..64: every weight byte once for all rows
+        mx = self.decode_weights == "mxfp4"
+        if mx:
+            self._mxfp4_decode_weights()
+
+        def mm(xin, w_, w8, out, N, K, wide=M > 16, **kw):   # one projection on the bf16 weight, or on its e4m3 / MXFP4 copy (q, scale)
+            if mx and w8 is not None:                   # every M up to H.DECODE_MAX_ROWS
+                H.gemm_w4(xin, w8[0], w8[1], out, M, N, K, **kw)
+            elif wide:                                  # M = 17..64: every weight byte once for all rows
                 H.gemm_wide(xin, w_ if w8 is None else w8[0], out, M, N, K, scale=None if w8 is None else w8[1], **kw)
             elif w8 is not None:
                 H.gemm_w8(xin, w8[0], w8[1], out, M, N, K, **kw)
@@ -2079,7 +2103,7 @@ class CausalLMHIP:
         one = dict(q_bs=self.qkvw, o_bs=aw) if w == 1 else {}
         Smax = self._gen_shape[1]
         for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
-            q8 = ly["q8"] if fp8 else {}
+            q8 = ly["q4"] if mx else ly["q8"] if fp8 else {}
             if self.lora is None:
                 proj(x, ly["n1"], ly["wqkv"], q8.get("wqkv"), qkv, self.qkvw)
             else:                                                             # the merged weight stays on H.gemm at every M
@@ -2097,7 +2121,7 @@ class CausalLMHIP:
             mm(act, ly["wd"], q8.get("wd"), x, h, self.I, residual=xm)
             if layer_hook is not None:                                        # ORCA deep injection on the new rows of every sequence
                 layer_hook(li, x)
-        proj(x, self.norm, self.head, self.head8 if fp8 else None, logits, self.V, ldc=self.Vp)
+        proj(x, self.norm, self.head, self.head4 if mx else self.head8 if fp8 else None, logits, self.V, ldc=self.Vp)
         return logits
 
     def decode_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, layer_hook=None) -> torch.Tensor:
@@ -2579,10 +2603,12 @@ class DeSTA25AudioModel:
         return self
 
     def set_decode_weights(self, kind: str) -> None:
-        """Weights the LLM's KV-cached decode steps stream: "bf16" (default) or "fp8" (weight-only OCP e4m3, per-row power-of-two
-        scales; `CausalLMHIP.set_decode_weights`).  `generate`, `_generate_step` and the trainer's evaluate use whatever is set."""
-        if kind not in CausalLMHIP.DECODE_WEIGHT_KINDS:
-            raise ValueError(f"decode_weights must be one of {CausalLMHIP.DECODE_WEIGHT_KINDS}, got {kind!r}")
+        """Weights the LLM's KV-cached decode steps stream: "bf16" (default), "fp8" (weight-only OCP e4m3, per-row power-of-two
+        scales) or "mxfp4" (weight-only OCP MXFP4: e2m1 nibbles, one e8m0 scale per 32 elements; `CausalLMHIP.set_decode_weights`).
+        `generate`, `_generate_step` and the trainer's evaluate use whatever is set."""
+        kinds = CausalLMHIP.DECODE_WEIGHT_KINDS + CausalLMHIP.DECODE_WEIGHT_KINDS_MX
+        if kind not in kinds:
+            raise ValueError(f"decode_weights must be one of {kinds}, got {kind!r}")
         self.llm.set_decode_weights(kind)
 
     def set_kv_cache(self, kind: str) -> None:

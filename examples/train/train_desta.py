@@ -161,12 +161,13 @@ def create_training_args(cfg: Cfg):
                          if cfg.dataset.train_ds.get("synthetic", False) else None))
 
 
-DECODE_WEIGHTS = ("bf16", "fp8")
+DECODE_WEIGHTS = ("bf16", "fp8", "mxfp4")
 
 
 def decode_weights_kind(cfg: Cfg) -> str:
     """trainer.decode_weights (this port's key; absent = "bf16"): what the KV-cached decode steps of evaluate / generate stream.
-    "fp8" = weight-only OCP e4m3 copies of the frozen LLM weights (`DeSTA25AudioModel.set_decode_weights`)."""
+    "fp8" = weight-only OCP e4m3 copies of the frozen LLM weights, "mxfp4" = OCP MXFP4 copies (e2m1 nibbles, one e8m0 scale per 32
+    elements; `DeSTA25AudioModel.set_decode_weights`)."""
     kind = str(cfg.trainer.get("decode_weights", "bf16"))
     if kind not in DECODE_WEIGHTS:
         raise ValueError(f"trainer.decode_weights={kind!r} is not supported (choose one of {', '.join(DECODE_WEIGHTS)})")

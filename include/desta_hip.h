@@ -156,6 +156,33 @@ int desta_quantize_rows_e4m3(const void* w_bf16, int rows, int cols, int64_t ld,
 int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Weight-only MXFP4 (W4A16) decode: the frozen LLM weights a second time as OCP e2m1 nibbles with one e8m0 scale per 32
+ * consecutive k, streamed by the projections of a KV-cached decode step (additive to ABI 8: no struct changes).
+ * Serves llm_model.generate, modeling_desta25.py:1419-1427 (the nn.Linear calls of
+ * TF:models/llama/modeling_llama.py:163-176 (MLP), 230-281 (attention projections), 480 (lm_head)) when the caller opts in;
+ * the default path keeps the bf16 weights.
+ *
+ * Format.  q [rows, K/2] bytes, row stride ldq bytes (a multiple of 16): byte j of a row holds element k = 2j in bits 3..0 and
+ *   k = 2j + 1 in bits 7..4.  A code is e2m1: bit 3 the sign, codes 0..7 the magnitudes 0 0.5 1 1.5 2 3 4 6.
+ *   s [rows, K/32] bytes, row stride lds bytes: e8m0, byte b = 2^(b - 127), one per block of 32 consecutive k; 255 is never written.
+ * desta_quantize_rows_mxfp4: w [rows, cols] bf16 (row stride ld elements, a multiple of 8; cols a multiple of 32) -> q, s.  Per block
+ *   e is the smallest integer with amax * 2^-e <= 7 (from the bits of amax; an all-zero block gets byte 127), elements are
+ *   w * 2^-e rounded to the nearest grid value, ties to the even code, the magnitude saturating at 6 ((6, 7] -> 6).  Covered:
+ *   blocks with amax = 0 or 2^-100 <= amax < 2^100.  code * 2^e is exactly a bf16 value.  Nothing behind `cols` of a row is read.
+ * desta_gemm_w4a16_nt: C[M,N] = epilogue( A[M,K] . dequant(B, b_scale_e8m0)[N,K]^T ) for 1 <= M <= 64, batch 1, K % 64 == 0.
+ *   d->B points at the nibbles [N, K/2] ([2N, K/2] for act 4) and d->ldb counts BYTES (a multiple of 16); b_scale_e8m0 [N, K/32]
+ *   ([2N, ..] for act 4) with row stride ld_scale bytes.  Supported: act 0 and 4 (SwiGLU over concatenated gate|up rows), bf16 or
+ *   fp32 output, ldc, a bf16 residual, alpha, and for M <= 16 a_rms_weight / a_rms_eps under the conditions of
+ *   desta_gemm_bf16_nt; anything else returns DESTA_EINVAL.  Nibbles become bf16 in registers (exact) and feed the bf16 MFMA
+ *   with fp32 accumulation in a fixed order that depends on N and K only: results do not depend on the grid
+ *   (desta_gemm_set_option 3) or on M.  The K order is NOT that of desta_gemm_bf16_nt (128-element chunks, one scale block per
+ *   lane), so the result is held to the fp64 bound of the operation, not to bit-equality with the bf16 form.  Shapes with few
+ *   64-column tiles are cut into K-slices through desta_gemm_desc.workspace (slices * M * N * 4 bytes, 2N for act 4, plus 4096;
+ *   too small: DESTA_EINVAL) and the fix-up launch of desta_gemm_wide_nt. */
+int desta_quantize_rows_mxfp4(const void* w_bf16, int rows, int cols, int64_t ld, uint8_t* q, int64_t ldq, uint8_t* scale_e8m0, int64_t lds, void* stream);
+int desta_gemm_w4a16_nt(const desta_gemm_desc* d, const uint8_t* b_scale_e8m0, int64_t ld_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Decode at batch 17..64: the projections of a KV-cached decode step (llm_model.generate, modeling_desta25.py:1419-1427; the
  * nn.Linear calls of TF:models/llama/modeling_llama.py:163-176 (MLP), 230-281 (attention projections), 480 (lm_head)) as one
  * weight-streaming launch that reads every weight byte once for up to 64 rows (additive to ABI 8: no struct changes).

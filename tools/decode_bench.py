@@ -4,12 +4,14 @@ rate of the decode GEMMs (bytes of frozen LLM weights read per token / token tim
 
   python tools/decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 8] [--ctx 64] [--prompt-tail 16] [--new 64]
                                [--do-sample --temperature T --top-p P --top-k K --min-p M --repetition-penalty R]
-                               [--weights {bf16,fp8}] [--ab [--rounds R]] [--attn-ab [--rounds R]] [--kv {bf16,fp8}] [--kv-ab [--rounds R]]
+                               [--weights {bf16,fp8,mxfp4}] [--ab [--rounds R]] [--attn-ab [--rounds R]] [--kv {bf16,fp8}] [--kv-ab [--rounds R]]
                                [--prefill-chunk N[,N...]] [--prefill-ab [--rounds R]]
 Without --do-sample the decode is greedy (with --repetition-penalty, through the full-chain sampler kernel).
---weights: what the decode steps stream (`set_decode_weights`; fp8 = weight-only OCP e4m3, half the bytes).  --ab alternates
-bf16 and fp8 in ONE process on one model (R rounds of bf16, fp8) and prints one line per leg and round plus a summary with the
-spread over the rounds: the bf16 leg of the same process is the yardstick, never a number from another box.
+--weights: what the decode steps stream (`set_decode_weights`; fp8 = weight-only OCP e4m3, half the bytes; mxfp4 = OCP MXFP4,
+0.266 of the bytes).  --ab alternates bf16, fp8 and mxfp4 in ONE process on one model (R rounds of bf16, fp8, mxfp4) and prints one
+line per leg and round plus a summary with the spread over the rounds: the legs of the same process are the yardstick, never a
+number from another box.  "X faster than Y beyond the spread": the worst pairing's margin (min of Y - max of X) exceeds the two
+legs' summed spreads.
 --kv: what the LLM's KV cache holds (`set_kv_cache`; fp8 = e4m3 bytes + per-head scales, 0.516 of the bytes).  --kv-ab alternates
 the two cache kinds for the chosen --weights in ONE process, R rounds, same report, plus the bytes each kind's slabs allocate
 (`torch.cuda.memory_allocated` deltas around the first allocation).
@@ -46,8 +48,8 @@ def main():
     ap.add_argument("--top-k", type=int, default=None)
     ap.add_argument("--min-p", type=float, default=None)
     ap.add_argument("--repetition-penalty", type=float, default=None)
-    ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16")
-    ap.add_argument("--ab", action="store_true", help="alternate bf16 / fp8 decode weights in this process")
+    ap.add_argument("--weights", choices=("bf16", "fp8", "mxfp4"), default="bf16")
+    ap.add_argument("--ab", action="store_true", help="alternate bf16 / fp8 / mxfp4 decode weights in this process")
     ap.add_argument("--attn-ab", action="store_true", help="alternate split-KV / forward-kernel decode attention in this process")
     ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16")
     ap.add_argument("--kv-ab", action="store_true", help="alternate bf16 / fp8 KV cache in this process")
@@ -184,7 +186,7 @@ def main():
             res.append(best)
         prompt_ms = res[0] * 1e3
         tok_ms = (res[1] - res[0]) * 1e3 / (a.new - 1)
-        wbytes = welems * (1 if kind == "fp8" else 2)
+        wbytes = welems * 17 // 32 if kind == "mxfp4" else welems * (1 if kind == "fp8" else 2)     # mxfp4: 4 bits + one scale byte per 32
         r = {"workload": f"{a.config} generate B={B} prompt={S} new={a.new} {mode}", "decode_weights": kind, "kv_cache": model.llm.kv_cache_kind, "prefill_chunk": model.llm.prefill_chunk,
              "prompt_ms": round(prompt_ms, 2),
              "ms_per_token_step": round(tok_ms, 3), "tokens_per_s": round(B / tok_ms * 1e3, 1),
@@ -254,23 +256,37 @@ def main():
     if not a.ab:
         leg(a.weights)
         return
-    leg("fp8")                                                               # warm-up: quantise once, touch both paths
-    runs = {"bf16": [], "fp8": []}
+    leg("fp8")                                                               # warm-up: quantise once, touch every path
+    leg("mxfp4")
+    runs = {"bf16": [], "fp8": [], "mxfp4": []}
     for _ in range(a.rounds):
-        for kind in ("bf16", "fp8"):
+        for kind in runs:
+            model.set_decode_weights(kind)                                   # (the copies another leg freed are re-made outside the timed region)
             if kind == "fp8":
-                model.set_decode_weights("fp8")
-                model.llm._fp8_decode_weights()                              # (re-made after the bf16 leg freed them: outside the timed region)
+                model.llm._fp8_decode_weights()
+            elif kind == "mxfp4":
+                model.llm._mxfp4_decode_weights()
             runs[kind].append(leg(kind)["ms_per_token_step"])
+    model.set_decode_weights("bf16")
     lo = {k: min(v) for k, v in runs.items()}
     hi = {k: max(v) for k, v in runs.items()}
     med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def faster(x, y):                                                        # x beats y in the worst pairing by more than both spreads
+        return bool(lo[y] - hi[x] > (hi[x] - lo[x]) + (hi[y] - lo[y]))
     print(json.dumps({"ab": f"{a.config} B={B} prompt={S} new={a.new} {mode}", "rounds": a.rounds,
-                      "bf16_ms_per_step": runs["bf16"], "fp8_ms_per_step": runs["fp8"],
+                      "bf16_ms_per_step": runs["bf16"], "fp8_ms_per_step": runs["fp8"], "mxfp4_ms_per_step": runs["mxfp4"],
                       "spread_ms": {k: round(hi[k] - lo[k], 3) for k in runs},
+                      "tokens_per_s": {k: round(B / med[k] * 1e3, 1) for k in runs},
                       "median_speedup": round(med["bf16"] / med["fp8"], 3),
+                      "median_speedup_mxfp4_vs_bf16": round(med["bf16"] / med["mxfp4"], 3),
+                      "median_speedup_mxfp4_vs_fp8": round(med["fp8"] / med["mxfp4"], 3),
                       "margin_ms_worst_case": round(lo["bf16"] - hi["fp8"], 3),
-                      "fp8_faster_beyond_spread": bool(lo["bf16"] - hi["fp8"] > max(hi[k] - lo[k] for k in runs))}))
+                      "margin_ms_worst_case_mxfp4_vs_bf16": round(lo["bf16"] - hi["mxfp4"], 3),
+                      "margin_ms_worst_case_mxfp4_vs_fp8": round(lo["fp8"] - hi["mxfp4"], 3),
+                      "fp8_faster_beyond_spread": bool(lo["bf16"] - hi["fp8"] > max(hi[k] - lo[k] for k in ("bf16", "fp8"))),
+                      "mxfp4_faster_than_bf16_beyond_spread": faster("mxfp4", "bf16"),
+                      "mxfp4_faster_than_fp8_beyond_spread": faster("mxfp4", "fp8")}))
 
 if __name__ == "__main__":
     main()
