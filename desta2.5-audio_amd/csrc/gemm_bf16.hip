@@ -1380,6 +1380,45 @@ struct SkinnyCursor { int tile, grp; };
 #define SKINNY_W8_U 2                                                   // pipeline depth of the weight-only FP8 form (2 or 4; option 11 overrides for act 0)
 #endif
 
+// silu(gate) * up with the rounding points of the unfused path (projection rounded to bf16, then swiglu_fwd)
+__device__ __forceinline__ u16x4 swiglu4_bf16(const f32x4& gs, const f32x4& us, float alpha) {
+    u16x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float gt = bf2f(f2bf(gs[e] * alpha)), uu = bf2f(f2bf(us[e] * alpha));
+        o[e] = f2bf(bf2f(f2bf(gt / (1.0f + __expf(-gt)))) * uu);
+    }
+    return o;
+}
+
+// The RMS prologue of the 16-row and MXFP4 kernels: RMSNorm of the p.M rows at A (row stride p.lda) into the LDS image xs, one
+// wave per row in the summation order of rmsnorm_fwd_k; row m is p.K * 2 bytes, its 16-byte slot c >> 3 sits at (c >> 3) ^ m.
+// Ends with the barrier after which every wave may read every row.
+__device__ __forceinline__ void rms_rows_to_lds(const GemmArgs& p, const bf16_t* A, char* xs, int wave, int lane) {
+    for (int m = wave; m < p.M; m += 8) {
+        const bf16_t* xr = A + (long)m * p.lda;
+        float q = 0.f;
+#pragma unroll 4
+        for (int c = lane * 8; c < p.K; c += 512) {
+            const u16x8 v = *(const u16x8*)(xr + c);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float f = bf2f(v[e]); q += f * f; }
+        }
+        const float rstd = rsqrtf(wave_sum(q) / (float)p.K + p.rms_eps);
+#pragma unroll 2
+        for (int c = lane * 8; c < p.K; c += 512) {
+            const u16x8 v = *(const u16x8*)(xr + c);
+            const float4 w0 = *(const float4*)(p.rms_w + c), w1 = *(const float4*)(p.rms_w + c + 4);
+            const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+            u16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = f2bf(wv[e] * bf2f(f2bf(bf2f(v[e]) * rstd)));
+            *(u16x8*)(xs + m * (p.K * 2) + (((c >> 3) ^ m) << 4)) = o;
+        }
+    }
+    __syncthreads();
+}
+
 template <int COLS, int U, bool SWIGLU, bool RMS, bool W8 = false>
 __global__ __launch_bounds__(512, (COLS == 16 && (U == 2 || W8)) ? 2 : 1) void gemm_bf16_nt_skinny_kernel(GemmArgs p, int ntiles) {
     static_assert(!SWIGLU || COLS == 16, "SwiGLU pairing uses one 16-row weight tile");
@@ -1488,13 +1527,10 @@ __global__ __launch_bounds__(512, (COLS == 16 && (U == 2 || W8)) ? 2 : 1) void g
             }
             if (SWIGLU) {
                 // lane groups 0,1 hold gate columns n0+4g.., groups 2,3 the matching up columns: fetch up from lane+32
-                u16x4 o;
+                f32x4 up;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float up = __shfl(sum[e], (lane + 32) & 63, 64);
-                    const float gt = bf2f(f2bf(sum[e] * p.alpha)), uu = bf2f(f2bf(up * p.alpha));
-                    o[e] = f2bf(bf2f(f2bf(gt / (1.0f + __expf(-gt)))) * uu);
-                }
+                for (int e = 0; e < 4; ++e) up[e] = __shfl(sum[e], (lane + 32) & 63, 64);
+                const u16x4 o = swiglu4_bf16(sum, up, p.alpha);
                 const int n = n0 + g * 4;
                 if (mok && g < 2 && n < p.N) *(u16x4*)((bf16_t*)p.C + (long)z * p.sC + (long)r * p.ldc + n) = o;
             } else {
@@ -1505,30 +1541,7 @@ __global__ __launch_bounds__(512, (COLS == 16 && (U == 2 || W8)) ? 2 : 1) void g
     };
 
     if (G > 0) SK_LOAD(sa)
-    if (RMS) {
-        for (int m = wave; m < p.M; m += 8) {                            // one wave per row, same summation order as rmsnorm_fwd_k
-            const bf16_t* xr = p.A + (long)z * p.sA + (long)m * p.lda;
-            float q = 0.f;
-#pragma unroll 4
-            for (int c = lane * 8; c < p.K; c += 512) {
-                const u16x8 v = *(const u16x8*)(xr + c);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = bf2f(v[e]); q += f * f; }
-            }
-            const float rstd = rsqrtf(wave_sum(q) / (float)p.K + p.rms_eps);
-#pragma unroll 2
-            for (int c = lane * 8; c < p.K; c += 512) {
-                const u16x8 v = *(const u16x8*)(xr + c);
-                const float4 w0 = *(const float4*)(p.rms_w + c), w1 = *(const float4*)(p.rms_w + c + 4);
-                const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-                u16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = f2bf(wv[e] * bf2f(f2bf(bf2f(v[e]) * rstd)));
-                *(u16x8*)(smem + 2 * RED_BYTES + m * rowb + (((c >> 3) ^ m) << 4)) = o;
-            }
-        }
-        __syncthreads();
-    }
+    if (RMS) rms_rows_to_lds(p, p.A + (long)z * p.sA, smem + 2 * RED_BYTES, wave, lane);
     for (int gi = 0; gi < G; gi += 2) {
         if (gi + 1 < G) SK_LOAD(sb)
         SK_MMA(sa)
@@ -1562,18 +1575,102 @@ struct WideStage<MF, true> {
     u32x4 wq[4];
     bf16x8 x0[MF], x1[MF];
 };
-struct WideCursor { int item, grp, tile, slice; };
 
-// silu(gate) * up with the rounding points of the unfused path (projection rounded to bf16, then swiglu_fwd)
-__device__ __forceinline__ u16x4 swiglu4_bf16(const f32x4& gs, const f32x4& us, float alpha) {
-    u16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float gt = bf2f(f2bf(gs[e] * alpha)), uu = bf2f(f2bf(us[e] * alpha));
-        o[e] = f2bf(bf2f(f2bf(gt / (1.0f + __expf(-gt)))) * uu);
+// ---- what the two 64-row kernels (wide and MXFP4) share: the item walk, and the reduction and epilogue of a finished item ----
+// The walk: item = (K-slice, tile), a block takes items blockIdx.x, + gridDim.x, ..; an item is gpt groups of one chunk per wave.
+struct WideCursor { int item, grp, tile, slice; };
+template <bool SWIGLU>
+struct WideWalk {
+    int N, ntiles, ks, cps, nchunks;
+    int ntot, gpt, G;                                                    // weight rows = columns of the partial slab; groups per item; groups of this block
+    __device__ WideWalk(int N_, int ntiles_, int ks_, int cps_, int nchunks_) : N(N_), ntiles(ntiles_), ks(ks_), cps(cps_), nchunks(nchunks_) {
+        ntot = SWIGLU ? 2 * N : N;
+        gpt = (cps + 7) >> 3;
+        const int items = ntiles * ks;
+        const int my_items = ((int)blockIdx.x < items) ? (items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
+        G = my_items * gpt;
     }
-    return o;
-}
+    __device__ WideCursor first() const { return {(int)blockIdx.x, 0, (int)blockIdx.x % ntiles, (int)blockIdx.x / ntiles}; }
+    __device__ void advance(WideCursor& c) const {
+        if (++c.grp == gpt) { c.grp = 0; c.item += (int)gridDim.x; c.tile = c.item % ntiles; c.slice = c.item / ntiles; }
+    }
+    // the chunk of this wave at the cursor, and the end of the cursor's K-slice
+    __device__ int chunk(const WideCursor& c, int wave) const { return c.slice * cps + wave + c.grp * 8; }
+    __device__ int chunk_end(const WideCursor& c) const { return min((c.slice + 1) * cps, nchunks); }
+    // weight row of MFMA tile t, row q of it (clamped: absent rows are computed, never stored); ok = it exists
+    __device__ int wrow(int tile, int t, int q, bool& ok) const {
+        if (SWIGLU) {
+            const int n = tile * 32 + (t & 1) * 16 + q;
+            ok = n < N;
+            return (t >= 2 ? N : 0) + min(n, N - 1);
+        }
+        const int n = tile * 64 + t * 16 + q;
+        ok = n < N;
+        return min(n, N - 1);
+    }
+};
+
+// the scale step of a reduced sum: ON = the e4m3 weight row's fp32 scale, before any rounding or activation; otherwise the identity
+template <bool ON>
+struct RowScale {
+    const float* s;
+    __device__ f32x4 operator()(f32x4 sum, int row) const {
+        if constexpr (ON) {
+            const float4 v = *(const float4*)(s + row);
+            sum[0] *= v.x; sum[1] *= v.y; sum[2] *= v.z; sum[3] *= v.w;
+        }
+        return sum;
+    }
+};
+
+// The finish of an item: park the accumulators in red[wave][t * MF + f][lane], reduce them and store the raw slab of the K-slice
+// (ks > 1; the fix-up launch finishes it), the SwiGLU pair, or epilogue4.  A function object that binds the kernel's state by
+// reference once, as the lambda it replaces did: in that form both kernels compile to the registers they had, while a function
+// taking the same state as arguments moved two instantiations across the 128-VGPR line.
+template <int MF, bool SWIGLU, class Scale>
+struct WideFinish {
+    const GemmArgs& p; const WideWalk<SWIGLU>& wk; f32x4 (*const& red)[4 * MF][64]; f32x4 (&acc)[4][MF];
+    const int& lane; const int& wave; const int& r; const int& g; float* const& part; Scale scaled;
+    // the 8 waves' partial tiles, summed in wave order
+    __device__ f32x4 reduced(int t, int f) const {
+        f32x4 sum = red[0][t * MF + f][lane];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) sum += red[w][t * MF + f][lane];
+        return sum;
+    }
+    __device__ void operator()(int tile, int slice) const {
+        constexpr int T = 4;
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+#pragma unroll
+            for (int f = 0; f < MF; ++f) { red[wave][t * MF + f][lane] = acc[t][f]; acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        __syncthreads();
+        if (wk.ks > 1) {                                                 // raw sums of this K-slice
+            for (int u = wave; u < T * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int row = wk.wrow(tile, t, g * 4, ok);             // N % 4 == 0: the four rows exist together
+                if (ok && m < p.M) *(f32x4*)(part + ((long)slice * p.M + m) * wk.ntot + row) = reduced(t, f);
+            }
+        } else if (SWIGLU) {
+            for (int u = wave; u < 2 * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int n = wk.wrow(tile, t, g * 4, ok);
+                if (ok && m < p.M)
+                    *(u16x4*)((bf16_t*)p.C + (long)m * p.ldc + n) = swiglu4_bf16(scaled(reduced(t, f), n), scaled(reduced(t + 2, f), p.N + n), p.alpha);
+            }
+        } else {
+            for (int u = wave; u < T * MF; u += 8) {
+                const int t = u / MF, f = u % MF, m = f * 16 + r;
+                bool ok;
+                const int n = wk.wrow(tile, t, g * 4, ok);
+                if (ok && m < p.M) epilogue4(p, 0, m, n, scaled(reduced(t, f), n));
+            }
+        }
+        __syncthreads();                                                 // red is free again before the next item's partial tiles land
+    }
+};
 
 template <int MF, bool SWIGLU, bool W8>
 __global__ __launch_bounds__(512) void gemm_bf16_nt_skinny_wide_kernel(GemmArgs p, int ntiles, int ks, int cps, float* part) {
@@ -1582,46 +1679,29 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_skinny_wide_kernel(GemmArgs 
     f32x4 (*red)[T * MF][64] = (f32x4 (*)[T * MF][64])smem;              // red[wave][t * MF + f][lane]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
-    const int ntot = SWIGLU ? 2 * p.N : p.N;                             // weight rows = columns of the partial slab
     const bf16_t* Bz = p.B + g * 16;
     const char* Bq = (const char*)p.B + g * 16;                          // W8: one byte per element
     const bf16_t* ap[MF];
 #pragma unroll
     for (int f = 0; f < MF; ++f) ap[f] = p.A + (long)min(f * 16 + r, p.M - 1) * p.lda + g * 16;
-    const int nchunks = p.K >> 6;
-    const int gpt = (cps + 7) >> 3;                                      // groups (one chunk per wave) per item
-    const int items = ntiles * ks;
-    const int my_items = ((int)blockIdx.x < items) ? (items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-    const int G = my_items * gpt;
+    const WideWalk<SWIGLU> wk(p.N, ntiles, ks, cps, p.K >> 6);
+    const int G = wk.G;
     f32x4 acc[T][MF];
 #pragma unroll
     for (int t = 0; t < T; ++t)
 #pragma unroll
         for (int f = 0; f < MF; ++f) acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f};
     WideStage<MF, W8> sa, sb;
-    WideCursor lc = {(int)blockIdx.x, 0, (int)blockIdx.x % ntiles, (int)blockIdx.x / ntiles}, mc = lc;
+    WideCursor lc = wk.first(), mc = lc;
+    const WideFinish<MF, SWIGLU, RowScale<W8>> finish_item{p, wk, red, acc, lane, wave, r, g, part, {p.b_scale}};
 
-    auto advance = [&](WideCursor& c) {
-        if (++c.grp == gpt) { c.grp = 0; c.item += (int)gridDim.x; c.tile = c.item % ntiles; c.slice = c.item / ntiles; }
-    };
-    // weight row of MFMA tile t, row q of it; ok = it exists
-    auto wrow = [&](int tile, int t, int q, bool& ok) -> int {
-        if (SWIGLU) {
-            const int n = tile * 32 + (t & 1) * 16 + q;
-            ok = n < p.N;
-            return (t >= 2 ? p.N : 0) + min(n, p.N - 1);
-        }
-        const int n = tile * 64 + t * 16 + q;
-        ok = n < p.N;
-        return min(n, p.N - 1);
-    };
 #define WD_LOAD(S)                                                                          \
     {                                                                                       \
-        const int cc = lc.slice * cps + wave + lc.grp * 8;                                  \
-        if (cc < min((lc.slice + 1) * cps, nchunks)) {                                      \
+        const int cc = wk.chunk(lc, wave);                                                  \
+        if (cc < wk.chunk_end(lc)) {                                                        \
             _Pragma("unroll") for (int t = 0; t < T; ++t) {                                 \
                 bool ok;                                                                    \
-                const long row = wrow(lc.tile, t, r, ok);                                   \
+                const long row = wk.wrow(lc.tile, t, r, ok);                                \
                 if constexpr (W8) {                                                         \
                     S.wq[t] = *(const u32x4*)(Bq + row * p.ldb + (long)cc * 64);            \
                 } else {                                                                    \
@@ -1634,12 +1714,12 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_skinny_wide_kernel(GemmArgs 
                 S.x1[f] = *(const bf16x8*)(ap[f] + (long)cc * 64 + 8);                      \
             }                                                                               \
         }                                                                                   \
-        advance(lc);                                                                        \
+        wk.advance(lc);                                                                     \
     }
 #define WD_MMA(S)                                                                           \
     {                                                                                       \
-        const int cc = mc.slice * cps + wave + mc.grp * 8;                                  \
-        if (cc < min((mc.slice + 1) * cps, nchunks)) {                                      \
+        const int cc = wk.chunk(mc, wave);                                                  \
+        if (cc < wk.chunk_end(mc)) {                                                        \
             _Pragma("unroll") for (int t = 0; t < T; ++t) {                                 \
                 bf16x8 w0, w1;                                                              \
                 if constexpr (W8) e4m3x16_to_bf16(S.wq[t], w0, w1);                         \
@@ -1650,54 +1730,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt_skinny_wide_kernel(GemmArgs 
                 }                                                                           \
             }                                                                               \
         }                                                                                   \
-        if (mc.grp == gpt - 1) finish_item(mc.tile, mc.slice);                              \
-        advance(mc);                                                                        \
+        if (mc.grp == wk.gpt - 1) finish_item(mc.tile, mc.slice);                           \
+        wk.advance(mc);                                                                     \
     }
-    // the 8 waves' partial tiles, summed in wave order
-    auto reduced = [&](int t, int f) -> f32x4 {
-        f32x4 sum = red[0][t * MF + f][lane];
-#pragma unroll
-        for (int w = 1; w < 8; ++w) sum += red[w][t * MF + f][lane];
-        return sum;
-    };
-    auto scaled = [&](f32x4 sum, int row) -> f32x4 {                     // W8: the weight row's scale, before any rounding or activation
-        if constexpr (W8) {
-            const float4 s = *(const float4*)(p.b_scale + row);
-            sum[0] *= s.x; sum[1] *= s.y; sum[2] *= s.z; sum[3] *= s.w;
-        }
-        return sum;
-    };
-    auto finish_item = [&](int tile, int slice) {
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int f = 0; f < MF; ++f) { red[wave][t * MF + f][lane] = acc[t][f]; acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        __syncthreads();
-        if (ks > 1) {                                                    // raw sums of this K-slice; the fix-up launch finishes them
-            for (int u = wave; u < T * MF; u += 8) {
-                const int t = u / MF, f = u % MF, m = f * 16 + r;
-                bool ok;
-                const int row = wrow(tile, t, g * 4, ok);                // N % 4 == 0: the four rows exist together
-                if (ok && m < p.M) *(f32x4*)(part + ((long)slice * p.M + m) * ntot + row) = reduced(t, f);
-            }
-        } else if (SWIGLU) {
-            for (int u = wave; u < 2 * MF; u += 8) {
-                const int t = u / MF, f = u % MF, m = f * 16 + r;
-                bool ok;
-                const int n = wrow(tile, t, g * 4, ok);
-                if (ok && m < p.M)
-                    *(u16x4*)((bf16_t*)p.C + (long)m * p.ldc + n) = swiglu4_bf16(scaled(reduced(t, f), n), scaled(reduced(t + 2, f), p.N + n), p.alpha);
-            }
-        } else {
-            for (int u = wave; u < T * MF; u += 8) {
-                const int t = u / MF, f = u % MF, m = f * 16 + r;
-                bool ok;
-                const int n = wrow(tile, t, g * 4, ok);
-                if (ok && m < p.M) epilogue4(p, 0, m, n, scaled(reduced(t, f), n));
-            }
-        }
-        __syncthreads();                                                 // red is free again before the next item's partial tiles land
-    };
 
     if (G > 0) WD_LOAD(sa)
     for (int gi = 0; gi < G; gi += 2) {
@@ -1938,27 +1973,43 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
     return DESTA_OK;
 }
 
-// Weight-only FP8 form of the decode projections: the skinny kernel above with W8 = true.  Everything the bf16 entry point
-// offers beyond what a decode step asks for (bias, GELU, pre-activation copies, dropout, transposed operands, rotary epilogue,
-// batches) is rejected, not ignored.
-extern "C" int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scale, void* stream) {
-    DESTA_CHECK_ARG(d && d->A && d->B && d->C, "gemm_w8: null operand");
-    DESTA_CHECK_ARG(b_scale, "gemm_w8: null scale pointer");
-    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm_w8: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
-    DESTA_CHECK_ARG(d->M <= 16, "gemm_w8: M=%d, the weight-only FP8 kernel is the decode path (M <= 16)", d->M);
-    DESTA_CHECK_ARG(d->act == 0 || d->act == 4, "gemm_w8: act %d unsupported (0, or 4 = SwiGLU over concatenated gate|up rows)", d->act);
-    DESTA_CHECK_ARG(d->K % BK == 0, "gemm_w8: K=%d must be a multiple of %d", d->K, BK);
-    DESTA_CHECK_ARG(d->N % 4 == 0, "gemm_w8: N=%d must be a multiple of 4", d->N);
-    DESTA_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 16 == 0 && d->ldc % 4 == 0, "gemm_w8: lda must be a multiple of 8, ldb (e4m3 elements) of 16, ldc of 4");
-    DESTA_CHECK_ARG(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0) && ((uintptr_t)b_scale % 16 == 0),
-                    "gemm_w8: operands and scales must be 16-byte aligned");
-    DESTA_CHECK_ARG(d->batch == 1, "gemm_w8: batch %d unsupported (1)", d->batch);
+// ---- what the weight-only decode entry points (desta_gemm_w8a16_nt, desta_gemm_wide_nt, desta_gemm_w4a16_nt) share on the host ----
+// Everything the bf16 entry point offers beyond what a decode step asks for (bias, GELU, pre-activation copies, dropout,
+// transposed operands, rotary epilogue, batches) is rejected, not ignored; the rest is what the entry point's kernel takes.
+struct DecodeLimits {
+    int m_min, m_max;                  // rows the kernel takes
+    int ldb_mult; long ldb_min;        // ldb, in the storage units of the weight format
+    bool scale_required; int scale_align;
+    bool out_f32, res_f32;             // fp32 output / fp32 residual allowed
+    int rms_max_m;                     // a_rms_weight allowed up to this M (0: never)
+};
+static int decode_check_args(const char* name, const desta_gemm_desc* d, const void* scale, const DecodeLimits& lim) {
+    DESTA_CHECK_ARG(d && d->A && d->B && d->C, "%s: null operand", name);
+    DESTA_CHECK_ARG(scale || !lim.scale_required, "%s: null scale pointer", name);
+    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "%s: bad shape M=%d N=%d K=%d", name, d->M, d->N, d->K);
+    DESTA_CHECK_ARG(d->M >= lim.m_min && d->M <= lim.m_max, "%s: M=%d, this weight-streaming decode kernel takes %d <= M <= %d", name, d->M, lim.m_min, lim.m_max);
+    DESTA_CHECK_ARG(d->act == 0 || d->act == 4, "%s: act %d unsupported (0, or 4 = SwiGLU over concatenated gate|up rows)", name, d->act);
+    DESTA_CHECK_ARG(d->K % BK == 0, "%s: K=%d must be a multiple of %d", name, d->K, BK);
+    DESTA_CHECK_ARG(d->N % 4 == 0, "%s: N=%d must be a multiple of 4", name, d->N);
+    DESTA_CHECK_ARG(d->lda % 8 == 0 && d->ldb % lim.ldb_mult == 0 && d->ldb >= lim.ldb_min && d->ldc % 4 == 0,
+                    "%s: lda must be a multiple of 8, ldb a multiple of %d and >= %ld, ldc a multiple of 4", name, lim.ldb_mult, lim.ldb_min);
+    DESTA_CHECK_ARG(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0) && ((uintptr_t)scale % lim.scale_align == 0),
+                    "%s: operands and scales must be 16-byte aligned", name);
+    DESTA_CHECK_ARG(d->batch == 1, "%s: batch %d unsupported (1)", name, d->batch);
     DESTA_CHECK_ARG(!d->bias && !d->preact && !d->aux && d->dropout_p == 0.f && !d->trans_a && !d->trans_b && !d->rope_cos_sin,
-                    "gemm_w8: bias, preact, aux, dropout, transposed operands and the rotary epilogue are unsupported");
-    DESTA_CHECK_ARG(!d->residual || d->ldr % 4 == 0, "gemm_w8: ldr must be a multiple of 4");
-    DESTA_CHECK_ARG(d->act != 4 || (!d->out_f32 && !d->residual), "gemm_w8: act 4 needs a bf16 output and no residual");
-    DESTA_CHECK_ARG(!d->a_rms_weight || ((size_t)d->M * 2 * (size_t)d->K <= (size_t)SKINNY_XS_BYTES && d->K % 512 == 0),
-                    "gemm_w8: a_rms_weight (fused RMSNorm of A) needs M*2K <= %d bytes of LDS and K %% 512 == 0", SKINNY_XS_BYTES);
+                    "%s: bias, preact, aux, dropout, transposed operands and the rotary epilogue are unsupported", name);
+    DESTA_CHECK_ARG(lim.out_f32 || !d->out_f32, "%s: fp32 output is unsupported", name);
+    DESTA_CHECK_ARG(!d->residual || d->ldr % 4 == 0, "%s: ldr must be a multiple of 4", name);
+    DESTA_CHECK_ARG(!d->residual || lim.res_f32 || !d->residual_f32, "%s: the residual is bf16", name);
+    DESTA_CHECK_ARG(d->act != 4 || (!d->out_f32 && !d->residual), "%s: act 4 needs a bf16 output and no residual", name);
+    DESTA_CHECK_ARG(!d->a_rms_weight || lim.rms_max_m > 0, "%s: a_rms_weight is unsupported", name);
+    DESTA_CHECK_ARG(!d->a_rms_weight || (d->M <= lim.rms_max_m && (size_t)d->M * 2 * (size_t)d->K <= (size_t)SKINNY_XS_BYTES && d->K % 512 == 0),
+                    "%s: a_rms_weight (fused RMSNorm of A) needs M <= %d, M*2K <= %d bytes of LDS and K %% 512 == 0", name, lim.rms_max_m, SKINNY_XS_BYTES);
+    return DESTA_OK;
+}
+
+// the GemmArgs of a checked decode call; b_scale = the fp32 row scales of e4m3 weights or null
+static GemmArgs decode_gemm_args(const desta_gemm_desc* d, const float* b_scale) {
     GemmArgs a = {};
     a.A = (const bf16_t*)d->A; a.B = (const bf16_t*)d->B; a.C = d->C;
     a.M = d->M; a.N = d->N; a.K = d->K;
@@ -1966,9 +2017,42 @@ extern "C" int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scal
     a.res = d->residual; a.ldr = d->ldr; a.res_f32 = d->residual_f32;
     a.act = d->act; a.out_f32 = d->out_f32; a.alpha = d->alpha; a.drop_scale = 1.0f;
     a.rms_w = d->a_rms_weight; a.rms_eps = d->a_rms_eps; a.b_scale = b_scale;
+    return a;
+}
+
+// The item grid of the 64-row kernels.  K-slices: enough items for one block per CU, at least min_chunks_per_slice chunks each,
+// at most 8.  A function of the tile and chunk counts alone, so every M, every weight kind and act 4 against its plain 2N-row
+// form sum in the same order.  cps = chunks per slice; part = the slab [ks][M][ntot] at the head of the workspace (ks > 1), whose
+// last 4 KiB belong to the tile kernels' tickets and queue counters.
+struct WidePlan { int ks, cps; float* part; dim3 grid; };
+static int wide_plan(const char* name, const desta_gemm_desc* d, int ntiles, int nchunks, int min_chunks_per_slice, long ntot, WidePlan* pl) {
+    int ks = 256 / ntiles;
+    if (ks > nchunks / min_chunks_per_slice) ks = nchunks / min_chunks_per_slice;
+    if (ks > 8) ks = 8;
+    if (ks < 1) ks = 1;
+    const size_t need = (size_t)ks * d->M * ntot * sizeof(float) + 4096;
+    const bool ws_ok = d->workspace && ((uintptr_t)d->workspace % 16) == 0 && need <= d->workspace_bytes;
+    DESTA_CHECK_ARG(ks == 1 || ws_ok, "%s: N=%d K=%d is cut into %d K-slices and needs %zu workspace bytes", name, d->N, d->K, ks, need);
+    pl->ks = ks;
+    pl->cps = (nchunks + ks - 1) / ks;
+    pl->part = ks > 1 ? (float*)d->workspace : nullptr;
+    const int items = ntiles * ks, blocks = g_skinny_blocks > 1 ? g_skinny_blocks / 2 : 1;     // one block per CU where the 16-row kernel has two
+    pl->grid = dim3(items < blocks ? items : blocks);
+    return DESTA_OK;
+}
+// adds the K-slice slabs and runs the epilogue; b_scale = null where the sums in the slab are already scaled
+static void wide_fixup_launch(const GemmArgs& a, const WidePlan& pl, const float* b_scale, hipStream_t st) {
+    const dim3 fgrid((unsigned)(((long)a.M * (a.N / 4) + 255) / 256));
+    if (a.act == 4) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<true>), fgrid, dim3(256), 0, st, a, pl.ks, pl.part, b_scale);
+    else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<false>), fgrid, dim3(256), 0, st, a, pl.ks, pl.part, b_scale);
+}
+
+// Weight-only FP8 form of the decode projections: the skinny kernel above with W8 = true.
+extern "C" int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scale, void* stream) {
+    if (const int e = decode_check_args("gemm_w8", d, b_scale, DecodeLimits{1, 16, 16, 0, true, 16, true, true, 16})) return e;
+    const GemmArgs a = decode_gemm_args(d, b_scale);
     const int u = d->act != 4 && g_skinny_w8 ? g_skinny_w8 % 10 : SKINNY_W8_U;
     const int ntiles = d->act == 4 ? (d->N + 7) / 8 : (d->N + 15) / 16;
-    a.tilesM = 1; a.tilesN = ntiles; a.full_tiles = ntiles; a.split = 1;
     const dim3 grid(ntiles < g_skinny_blocks ? ntiles : g_skinny_blocks, 1);
     hipStream_t st = (hipStream_t)stream;
     const bool rms = a.rms_w != nullptr;
@@ -1986,64 +2070,28 @@ extern "C" int desta_gemm_w8a16_nt(const desta_gemm_desc* d, const float* b_scal
 
 // Decode projections at batch 17..64: the wide skinny kernel.  b_scale == NULL: B is bf16; otherwise B holds e4m3 bytes and b_scale
 // one power-of-two scale per weight row (2N rows for act 4).  One path per M: M <= 16 belongs to desta_gemm_bf16_nt /
-// desta_gemm_w8a16_nt, and nothing beyond what a decode step asks for is accepted.
+// desta_gemm_w8a16_nt.
 extern "C" int desta_gemm_wide_nt(const desta_gemm_desc* d, const float* b_scale, void* stream) {
-    DESTA_CHECK_ARG(d && d->A && d->B && d->C, "gemm_wide: null operand");
-    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm_wide: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
-    DESTA_CHECK_ARG(d->M > 16 && d->M <= 64, "gemm_wide: M=%d, the wide weight-streaming kernel takes 17 <= M <= 64 (M <= 16: desta_gemm_bf16_nt / desta_gemm_w8a16_nt)", d->M);
-    DESTA_CHECK_ARG(d->act == 0 || d->act == 4, "gemm_wide: act %d unsupported (0, or 4 = SwiGLU over concatenated gate|up rows)", d->act);
-    DESTA_CHECK_ARG(d->K % BK == 0, "gemm_wide: K=%d must be a multiple of %d", d->K, BK);
-    DESTA_CHECK_ARG(d->N % 4 == 0, "gemm_wide: N=%d must be a multiple of 4", d->N);
-    DESTA_CHECK_ARG(d->lda % 8 == 0 && d->ldb % (b_scale ? 16 : 8) == 0 && d->ldc % 4 == 0,
-                    "gemm_wide: lda must be a multiple of 8, ldb of 8 (bf16) or 16 (e4m3), ldc of 4");
-    DESTA_CHECK_ARG(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0) && ((uintptr_t)b_scale % 16 == 0),
-                    "gemm_wide: operands and scales must be 16-byte aligned");
-    DESTA_CHECK_ARG(d->batch == 1, "gemm_wide: batch %d unsupported (1)", d->batch);
-    DESTA_CHECK_ARG(!d->bias && !d->preact && !d->aux && d->dropout_p == 0.f && !d->trans_a && !d->trans_b && !d->rope_cos_sin &&
-                    !d->out_f32 && !d->a_rms_weight,
-                    "gemm_wide: bias, preact, aux, dropout, transposed operands, the rotary epilogue, fp32 output and a_rms_weight are unsupported");
-    DESTA_CHECK_ARG(!d->residual || (d->ldr % 4 == 0 && !d->residual_f32), "gemm_wide: the residual is bf16 and ldr a multiple of 4");
-    DESTA_CHECK_ARG(d->act != 4 || !d->residual, "gemm_wide: act 4 takes no residual");
-    GemmArgs a = {};
-    a.A = (const bf16_t*)d->A; a.B = (const bf16_t*)d->B; a.C = d->C;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
-    a.res = d->residual; a.ldr = d->ldr;
-    a.act = d->act; a.alpha = d->alpha; a.drop_scale = 1.0f;
-    a.b_scale = b_scale;
-    // K-slices: enough items for one block per CU, at least 16 chunks (two per wave) each.  A function of the tile and chunk counts
-    // alone, so every M, both weight kinds and act 4 against its plain 2N-row form sum in the same order.
-    const int swiglu = d->act == 4;
-    const int ntiles = swiglu ? (d->N + 31) / 32 : (d->N + 63) / 64, nchunks = d->K / BK;
-    const long ntot = swiglu ? 2L * d->N : d->N;
-    int ks = 256 / ntiles;
-    if (ks > nchunks / 16) ks = nchunks / 16;
-    if (ks > 8) ks = 8;
-    if (ks < 1) ks = 1;
-    // the last 4 KiB of the workspace belong to the tile kernels' tickets and queue counters
-    const bool ws_ok = d->workspace && ((uintptr_t)d->workspace % 16) == 0 && (size_t)ks * d->M * ntot * sizeof(float) + 4096 <= d->workspace_bytes;
-    DESTA_CHECK_ARG(ks == 1 || ws_ok, "gemm_wide: N=%d K=%d is cut into %d K-slices and needs %zu workspace bytes", d->N, d->K, ks,
-                    (size_t)ks * d->M * ntot * sizeof(float) + 4096);
-    const int cps = (nchunks + ks - 1) / ks;
-    float* part = ks > 1 ? (float*)d->workspace : nullptr;
-    const int items = ntiles * ks, blocks = g_skinny_blocks > 1 ? g_skinny_blocks / 2 : 1;     // one block per CU where the 16-row kernel has two
-    const dim3 grid(items < blocks ? items : blocks);
+    if (const int e = decode_check_args("gemm_wide", d, b_scale, DecodeLimits{17, 64, b_scale ? 16 : 8, 0, false, 16, false, false, 0})) return e;
+    const GemmArgs a = decode_gemm_args(d, b_scale);
+    const bool swiglu = d->act == 4;
+    const int ntiles = swiglu ? (d->N + 31) / 32 : (d->N + 63) / 64;
+    WidePlan pl;                                                         // 64-k chunks, at least 16 (two per wave) a slice
+    if (const int e = wide_plan("gemm_wide", d, ntiles, d->K / BK, 16, swiglu ? 2L * d->N : d->N, &pl)) return e;
     hipStream_t st = (hipStream_t)stream;
     const int mf = (d->M + 15) / 16;
 #define WD_LAUNCH(MF_) \
-    do { if (swiglu && b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, true, true>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); \
-         else if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, true, false>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); \
-         else if (b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, false, true>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); \
-         else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, false, false>), grid, dim3(512), 0, st, a, ntiles, ks, cps, part); } while (0)
+    do { if (swiglu && b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, true, true>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); \
+         else if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, true, false>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); \
+         else if (b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, false, true>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); \
+         else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_kernel<MF_, false, false>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); } while (0)
     if (mf == 2) WD_LAUNCH(2);
     else if (mf == 3) WD_LAUNCH(3);
     else WD_LAUNCH(4);
 #undef WD_LAUNCH
     DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny_wide");
-    if (ks > 1) {
-        const dim3 fgrid((unsigned)(((long)d->M * (d->N / 4) + 255) / 256));
-        if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<true>), fgrid, dim3(256), 0, st, a, ks, part, b_scale);
-        else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<false>), fgrid, dim3(256), 0, st, a, ks, part, b_scale);
+    if (pl.ks > 1) {
+        wide_fixup_launch(a, pl, b_scale, st);
         DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny_wide_fixup");
     }
     g_last_kernel = 3;
@@ -2100,7 +2148,6 @@ __global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const ui
     f32x4 (*red)[T * MF][64] = (f32x4 (*)[T * MF][64])smem;              // red[wave][t * MF + f][lane]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, g = lane >> 4;
-    const int ntot = SWIGLU ? 2 * p.N : p.N;                             // weight rows = columns of the partial slab
     const char* Bq = (const char*)p.B + g * 16;                          // two elements per byte: 32 k of this lane group
     const uint8_t* Sq = bsc + g;
     const bf16_t* ap[MF];
@@ -2112,11 +2159,8 @@ __global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const ui
     }
     const int rr = xok[0] ? r : 0;
     const char* xrow = smem + RED_BYTES + rr * (p.K * 2);                // this lane's fragment row in LDS (RMS only)
-    const int nchunks = (p.K + 127) >> 7;
-    const int gpt = (cps + 7) >> 3;                                      // groups (one chunk per wave) per item
-    const int items = ntiles * ks;
-    const int my_items = ((int)blockIdx.x < items) ? (items - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
-    const int G = my_items * gpt;
+    const WideWalk<SWIGLU> wk(p.N, ntiles, ks, cps, (p.K + 127) >> 7);
+    const int G = wk.G;
     f32x4 acc[T][MF];
 #pragma unroll
     for (int t = 0; t < T; ++t)
@@ -2124,26 +2168,13 @@ __global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const ui
         for (int f = 0; f < MF; ++f) acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f};
     W4Stage sa, sb;
     bf16x8 xa[MF][4], xb[MF][4];
-    WideCursor lc = {(int)blockIdx.x, 0, (int)blockIdx.x % ntiles, (int)blockIdx.x / ntiles}, mc = lc;
+    WideCursor lc = wk.first(), mc = lc;
+    const WideFinish<MF, SWIGLU, RowScale<false>> finish_item{p, wk, red, acc, lane, wave, r, g, part, {nullptr}};   // sums arrive scaled
 
-    auto advance = [&](WideCursor& c) {
-        if (++c.grp == gpt) { c.grp = 0; c.item += (int)gridDim.x; c.tile = c.item % ntiles; c.slice = c.item / ntiles; }
-    };
-    // weight row of MFMA tile t, row q of it; ok = it exists
-    auto wrow = [&](int tile, int t, int q, bool& ok) -> int {
-        if (SWIGLU) {
-            const int n = tile * 32 + (t & 1) * 16 + q;
-            ok = n < p.N;
-            return (t >= 2 ? p.N : 0) + min(n, p.N - 1);
-        }
-        const int n = tile * 64 + t * 16 + q;
-        ok = n < p.N;
-        return min(n, p.N - 1);
-    };
     // this lane's 32 k of the cursor's chunk lie inside the K-slice and inside K
     auto chunk_of = [&](const WideCursor& c, bool& live) -> int {
-        const int cc = c.slice * cps + wave + c.grp * 8;
-        live = cc < min((c.slice + 1) * cps, nchunks) && cc * 128 + g * 32 < p.K;
+        const int cc = wk.chunk(c, wave);
+        live = cc < wk.chunk_end(c) && cc * 128 + g * 32 < p.K;
         return cc;
     };
 #define W4_XLOAD(X, CUR)                                                                    \
@@ -2164,7 +2195,7 @@ __global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const ui
         const int cc = chunk_of(lc, live);                                                  \
         _Pragma("unroll") for (int t = 0; t < T; ++t) {                                     \
             bool ok;                                                                        \
-            const long row = wrow(lc.tile, t, r, ok);        /* clamped rows: computed, never stored */ \
+            const long row = wk.wrow(lc.tile, t, r, ok);     /* clamped rows: computed, never stored */ \
             if (live) {                                                                     \
                 S.wq[t] = *(const u32x4*)(Bq + row * p.ldb + (long)cc * 64);                \
                 S.sc[t] = Sq[row * ldsc + cc * 4];                                          \
@@ -2174,7 +2205,7 @@ __global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const ui
             }                                                                               \
         }                                                                                   \
         if (XS) W4_XLOAD(X, lc)                                                             \
-        advance(lc);                                                                        \
+        wk.advance(lc);                                                                     \
     }
 #define W4_MMA(S, X)                                                                        \
     {                                                                                       \
@@ -2192,72 +2223,11 @@ __global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const ui
                     acc[t][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, X[f][j], acc[t][f], 0, 0, 0); \
             }                                                                               \
         }                                                                                   \
-        if (mc.grp == gpt - 1) finish_item(mc.tile, mc.slice);                              \
-        advance(mc);                                                                        \
+        if (mc.grp == wk.gpt - 1) finish_item(mc.tile, mc.slice);                           \
+        wk.advance(mc);                                                                     \
     }
-    // the 8 waves' partial tiles, summed in wave order
-    auto reduced = [&](int t, int f) -> f32x4 {
-        f32x4 sum = red[0][t * MF + f][lane];
-#pragma unroll
-        for (int w = 1; w < 8; ++w) sum += red[w][t * MF + f][lane];
-        return sum;
-    };
-    auto finish_item = [&](int tile, int slice) {
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-#pragma unroll
-            for (int f = 0; f < MF; ++f) { red[wave][t * MF + f][lane] = acc[t][f]; acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        __syncthreads();
-        if (ks > 1) {                                                    // raw sums of this K-slice; the fix-up launch finishes them
-            for (int u = wave; u < T * MF; u += 8) {
-                const int t = u / MF, f = u % MF, m = f * 16 + r;
-                bool ok;
-                const int row = wrow(tile, t, g * 4, ok);                // N % 4 == 0: the four rows exist together
-                if (ok && m < p.M) *(f32x4*)(part + ((long)slice * p.M + m) * ntot + row) = reduced(t, f);
-            }
-        } else if (SWIGLU) {
-            for (int u = wave; u < 2 * MF; u += 8) {
-                const int t = u / MF, f = u % MF, m = f * 16 + r;
-                bool ok;
-                const int n = wrow(tile, t, g * 4, ok);
-                if (ok && m < p.M) *(u16x4*)((bf16_t*)p.C + (long)m * p.ldc + n) = swiglu4_bf16(reduced(t, f), reduced(t + 2, f), p.alpha);
-            }
-        } else {
-            for (int u = wave; u < T * MF; u += 8) {
-                const int t = u / MF, f = u % MF, m = f * 16 + r;
-                bool ok;
-                const int n = wrow(tile, t, g * 4, ok);
-                if (ok && m < p.M) epilogue4(p, 0, m, n, reduced(t, f));
-            }
-        }
-        __syncthreads();                                                 // red is free again before the next item's partial tiles land
-    };
-
     if (G > 0) W4_LOAD(sa, xa)
-    if (RMS) {
-        for (int m = wave; m < p.M; m += 8) {                            // one wave per row, same summation order as rmsnorm_fwd_k
-            const bf16_t* xr = p.A + (long)m * p.lda;
-            float q = 0.f;
-#pragma unroll 4
-            for (int c = lane * 8; c < p.K; c += 512) {
-                const u16x8 v = *(const u16x8*)(xr + c);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = bf2f(v[e]); q += f * f; }
-            }
-            const float rstd = rsqrtf(wave_sum(q) / (float)p.K + p.rms_eps);
-#pragma unroll 2
-            for (int c = lane * 8; c < p.K; c += 512) {
-                const u16x8 v = *(const u16x8*)(xr + c);
-                const float4 w0 = *(const float4*)(p.rms_w + c), w1 = *(const float4*)(p.rms_w + c + 4);
-                const float wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
-                u16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = f2bf(wv[e] * bf2f(f2bf(bf2f(v[e]) * rstd)));
-                *(u16x8*)(smem + RED_BYTES + m * (p.K * 2) + (((c >> 3) ^ m) << 4)) = o;
-            }
-        }
-        __syncthreads();
-    }
+    if (RMS) rms_rows_to_lds(p, p.A, smem + RED_BYTES, wave, lane);
     for (int gi = 0; gi < G; gi += 2) {
         if (!XS && !RMS) W4_XLOAD(xa, mc)
         if (gi + 1 < G) W4_LOAD(sb, xb)
@@ -2278,52 +2248,17 @@ __global__ __launch_bounds__(512) void gemm_w4a16_nt_kernel(GemmArgs p, const ui
 // Weight-only MXFP4 form of the decode projections, 1 <= M <= 64 in one entry point: gemm_w4a16_nt_kernel with MF = ceil(M / 16).
 // What a decode step does not ask for is rejected by name, as desta_gemm_wide_nt does.
 extern "C" int desta_gemm_w4a16_nt(const desta_gemm_desc* d, const uint8_t* b_scale_e8m0, int64_t ld_scale, void* stream) {
-    DESTA_CHECK_ARG(d && d->A && d->B && d->C, "gemm_w4: null operand");
-    DESTA_CHECK_ARG(b_scale_e8m0, "gemm_w4: null scale pointer");
-    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "gemm_w4: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
-    DESTA_CHECK_ARG(d->M <= 64, "gemm_w4: M=%d, the weight-only MXFP4 kernel is the decode path (M <= 64)", d->M);
-    DESTA_CHECK_ARG(d->act == 0 || d->act == 4, "gemm_w4: act %d unsupported (0, or 4 = SwiGLU over concatenated gate|up rows)", d->act);
-    DESTA_CHECK_ARG(d->K % BK == 0, "gemm_w4: K=%d must be a multiple of %d", d->K, BK);
-    DESTA_CHECK_ARG(d->N % 4 == 0, "gemm_w4: N=%d must be a multiple of 4", d->N);
-    DESTA_CHECK_ARG(d->lda % 8 == 0 && d->ldb % 16 == 0 && d->ldb >= d->K / 2 && d->ldc % 4 == 0 && ld_scale >= d->K / 32,
-                    "gemm_w4: lda must be a multiple of 8, ldb (bytes) a multiple of 16 and >= K / 2, ldc a multiple of 4, ld_scale >= K / 32");
-    DESTA_CHECK_ARG(((uintptr_t)d->A % 16 == 0) && ((uintptr_t)d->B % 16 == 0) && ((uintptr_t)d->C % 16 == 0), "gemm_w4: operands must be 16-byte aligned");
-    DESTA_CHECK_ARG(d->batch == 1, "gemm_w4: batch %d unsupported (1)", d->batch);
-    DESTA_CHECK_ARG(!d->bias && !d->preact && !d->aux && d->dropout_p == 0.f && !d->trans_a && !d->trans_b && !d->rope_cos_sin,
-                    "gemm_w4: bias, preact, aux, dropout, transposed operands and the rotary epilogue are unsupported");
-    DESTA_CHECK_ARG(!d->residual || (d->ldr % 4 == 0 && !d->residual_f32), "gemm_w4: the residual is bf16 and ldr a multiple of 4");
-    DESTA_CHECK_ARG(d->act != 4 || (!d->out_f32 && !d->residual), "gemm_w4: act 4 needs a bf16 output and no residual");
-    DESTA_CHECK_ARG(!d->a_rms_weight || (d->M <= 16 && (size_t)d->M * 2 * (size_t)d->K <= (size_t)SKINNY_XS_BYTES && d->K % 512 == 0),
-                    "gemm_w4: a_rms_weight (fused RMSNorm of A) needs M <= 16, M*2K <= %d bytes of LDS and K %% 512 == 0", SKINNY_XS_BYTES);
-    GemmArgs a = {};
-    a.A = (const bf16_t*)d->A; a.B = (const bf16_t*)d->B; a.C = d->C;
-    a.M = d->M; a.N = d->N; a.K = d->K;
-    a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
-    a.res = d->residual; a.ldr = d->ldr;
-    a.act = d->act; a.out_f32 = d->out_f32; a.alpha = d->alpha; a.drop_scale = 1.0f;
-    a.rms_w = d->a_rms_weight; a.rms_eps = d->a_rms_eps;
-    // K-slices: enough items for one block per CU, at least 8 chunks of 128 (one per wave) each.  A function of the tile and chunk
-    // counts alone, so every M and act 4 against its plain 2N-row form sum in the same order.
-    const int swiglu = d->act == 4;
-    const int ntiles = swiglu ? (d->N + 31) / 32 : (d->N + 63) / 64, nchunks = (d->K + 127) / 128;
-    const long ntot = swiglu ? 2L * d->N : d->N;
-    int ks = 256 / ntiles;
-    if (ks > nchunks / W4_SLICE_CHUNKS) ks = nchunks / W4_SLICE_CHUNKS;
-    if (ks > 8) ks = 8;
-    if (ks < 1) ks = 1;
-    // the last 4 KiB of the workspace belong to the tile kernels' tickets and queue counters
-    const bool ws_ok = d->workspace && ((uintptr_t)d->workspace % 16) == 0 && (size_t)ks * d->M * ntot * sizeof(float) + 4096 <= d->workspace_bytes;
-    DESTA_CHECK_ARG(ks == 1 || ws_ok, "gemm_w4: N=%d K=%d is cut into %d K-slices and needs %zu workspace bytes", d->N, d->K, ks,
-                    (size_t)ks * d->M * ntot * sizeof(float) + 4096);
-    const int cps = (nchunks + ks - 1) / ks;
-    float* part = ks > 1 ? (float*)d->workspace : nullptr;
+    if (const int e = decode_check_args("gemm_w4", d, b_scale_e8m0, DecodeLimits{1, 64, 16, d ? d->K / 2 : 0, true, 1, true, false, 16})) return e;
+    DESTA_CHECK_ARG(ld_scale >= d->K / 32, "gemm_w4: ld_scale must be >= K / 32");
+    const GemmArgs a = decode_gemm_args(d, nullptr);
+    const bool swiglu = d->act == 4;
+    const int ntiles = swiglu ? (d->N + 31) / 32 : (d->N + 63) / 64;
+    WidePlan pl;                                                         // 128-k chunks, at least W4_SLICE_CHUNKS a slice
+    if (const int e = wide_plan("gemm_w4", d, ntiles, (d->K + 127) / 128, W4_SLICE_CHUNKS, swiglu ? 2L * d->N : d->N, &pl)) return e;
     const int mf = (d->M + 15) / 16;
-    // one block per CU (every form holds more than 128 VGPRs or more than 80 KiB of LDS) where the 16-row bf16 kernel has two
-    const int items = ntiles * ks, blocks = g_skinny_blocks > 1 ? g_skinny_blocks / 2 : 1;
-    const dim3 grid(items < blocks ? items : blocks);
     hipStream_t st = (hipStream_t)stream;
 #define W4_LAUNCH(MF_, SW_, RMS_) \
-    hipLaunchKernelGGL((gemm_w4a16_nt_kernel<MF_, SW_, RMS_>), grid, dim3(512), 0, st, a, b_scale_e8m0, (long)ld_scale, ntiles, ks, cps, part)
+    hipLaunchKernelGGL((gemm_w4a16_nt_kernel<MF_, SW_, RMS_>), pl.grid, dim3(512), 0, st, a, b_scale_e8m0, (long)ld_scale, ntiles, pl.ks, pl.cps, pl.part)
 #define W4_LAUNCH_MF(MF_) do { if (swiglu) W4_LAUNCH(MF_, true, false); else W4_LAUNCH(MF_, false, false); } while (0)
     if (mf == 1 && a.rms_w) { if (swiglu) W4_LAUNCH(1, true, true); else W4_LAUNCH(1, false, true); }
     else if (mf == 1) W4_LAUNCH_MF(1);
@@ -2333,10 +2268,8 @@ extern "C" int desta_gemm_w4a16_nt(const desta_gemm_desc* d, const uint8_t* b_sc
 #undef W4_LAUNCH_MF
 #undef W4_LAUNCH
     DESTA_CHECK_LAUNCH("gemm_w4a16_nt");
-    if (ks > 1) {                                                        // the sums in the slab are already scaled: no b_scale
-        const dim3 fgrid((unsigned)(((long)d->M * (d->N / 4) + 255) / 256));
-        if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<true>), fgrid, dim3(256), 0, st, a, ks, part, (const float*)nullptr);
-        else hipLaunchKernelGGL((gemm_bf16_nt_skinny_wide_fixup_kernel<false>), fgrid, dim3(256), 0, st, a, ks, part, (const float*)nullptr);
+    if (pl.ks > 1) {                                                     // the sums in the slab are already scaled: no b_scale
+        wide_fixup_launch(a, pl, nullptr, st);
         DESTA_CHECK_LAUNCH("gemm_w4a16_nt_fixup");
     }
     g_last_kernel = 3;

@@ -123,6 +123,28 @@ def rms_fusable(M: int, K: int) -> bool:
     return M <= 16 and M * 2 * K <= 8 * 4096 * 2 and K % 512 == 0
 
 
+def _decode_desc(A, B, out, M, N, K, lda, ldb, ldc, residual, ldr, act, alpha, a_rms_weight=None, a_rms_eps=0.0, workspace=False):
+    """The GemmDesc of a weight-only decode projection (`gemm_w8`, `gemm_wide`, `gemm_w4`): batch 1, ldb in the weight format's
+    units, and the stream's GEMM workspace where the kernel cuts K into slices."""
+    d = GemmDesc()
+    d.A, d.B, d.C = p(A), p(B), p(out)
+    d.M, d.N, d.K, d.batch = M, N, K, 1
+    d.lda = K if lda is None else lda
+    d.ldb = K if ldb is None else ldb
+    d.ldc = N if ldc is None else ldc
+    d.residual = p(residual)
+    d.ldr = N if ldr is None else ldr
+    d.residual_f32 = int(residual is not None and residual.dtype == torch.float32)
+    d.act = act
+    d.out_f32 = int(out.dtype == torch.float32)
+    d.ldp = N
+    d.alpha = alpha
+    d.a_rms_weight, d.a_rms_eps = p(a_rms_weight), a_rms_eps
+    if workspace:
+        d.workspace, d.workspace_bytes = _workspace(A.device, stream()).data_ptr(), GEMM_WS_BYTES
+    return d
+
+
 _quantize_rows_e4m3 = _sig("desta_quantize_rows_e4m3", vp, i32, i32, i64, vp, vp, vp)
 _gemm_w8 = _sig("desta_gemm_w8a16_nt", C.POINTER(GemmDesc), vp, vp)
 GEMM_W8_CALLS = 0                  # weight-only FP8 projections issued by this process (tests assert which path a projection took)
@@ -147,20 +169,7 @@ def gemm_w8(A, B8, scale, out, M, N, K, *, lda=None, ldb=None, ldc=None, residua
     stored as OCP e4m3fn bytes with one power-of-two fp32 scale per row (`quantize_rows_e4m3`).  act 4: B8 / scale hold the
     concatenated gate|up rows [2N].  Same bits as `gemm` on the dequantised weight bf16(B8 * scale)."""
     global GEMM_W8_CALLS
-    d = GemmDesc()
-    d.A, d.B, d.C = p(A), p(B8), p(out)
-    d.M, d.N, d.K, d.batch = M, N, K, 1
-    d.lda = K if lda is None else lda
-    d.ldb = K if ldb is None else ldb
-    d.ldc = N if ldc is None else ldc
-    d.residual = p(residual)
-    d.ldr = N if ldr is None else ldr
-    d.residual_f32 = int(residual is not None and residual.dtype == torch.float32)
-    d.act = act
-    d.out_f32 = int(out.dtype == torch.float32)
-    d.ldp = N
-    d.alpha = alpha
-    d.a_rms_weight, d.a_rms_eps = p(a_rms_weight), a_rms_eps
+    d = _decode_desc(A, B8, out, M, N, K, lda, ldb, ldc, residual, ldr, act, alpha, a_rms_weight, a_rms_eps)
     check(_gemm_w8(C.byref(d), p(scale), stream()), "desta_gemm_w8a16_nt")
     GEMM_W8_CALLS += 1
     return out
@@ -177,20 +186,7 @@ def gemm_wide(A, B, out, M, N, K, *, scale=None, lda=None, ldb=None, ldc=None, r
     (`quantize_rows_e4m3`), same bits as the bf16 form on bf16(B * scale).  act 4: B (and scale) hold the concatenated gate|up
     rows [2N].  bf16 output, bf16 residual; K-slice partial sums go through the stream's GEMM workspace."""
     global GEMM_WIDE_CALLS
-    d = GemmDesc()
-    d.A, d.B, d.C = p(A), p(B), p(out)
-    d.M, d.N, d.K, d.batch = M, N, K, 1
-    d.lda = K if lda is None else lda
-    d.ldb = K if ldb is None else ldb
-    d.ldc = N if ldc is None else ldc
-    d.residual = p(residual)
-    d.ldr = N if ldr is None else ldr
-    d.residual_f32 = int(residual is not None and residual.dtype == torch.float32)
-    d.act = act
-    d.out_f32 = int(out.dtype == torch.float32)
-    d.ldp = N
-    d.alpha = alpha
-    d.workspace, d.workspace_bytes = _workspace(A.device, stream()).data_ptr(), GEMM_WS_BYTES
+    d = _decode_desc(A, B, out, M, N, K, lda, ldb, ldc, residual, ldr, act, alpha, workspace=True)
     check(_gemm_wide(C.byref(d), p(scale), stream()), "desta_gemm_wide_nt")
     GEMM_WIDE_CALLS += 1
     return out
@@ -225,21 +221,9 @@ def gemm_w4(A, B4, s, out, M, N, K, *, lda=None, ldb=None, ldc=None, ld_scale=No
     [2N].  fp32 accumulation in a fixed order of its own (128-element K chunks): held to the fp64 bound of the operation, not
     bit-equal to `gemm` on the dequantised weight.  K-slice partial sums go through the stream's GEMM workspace."""
     global GEMM_W4_CALLS
-    d = GemmDesc()
-    d.A, d.B, d.C = p(A), p(B4), p(out)
-    d.M, d.N, d.K, d.batch = M, N, K, 1
-    d.lda = K if lda is None else lda
-    d.ldb = (B4.stride(0) if B4 is not None and B4.dim() == 2 else K // 2) if ldb is None else ldb
-    d.ldc = N if ldc is None else ldc
-    d.residual = p(residual)
-    d.ldr = N if ldr is None else ldr
-    d.residual_f32 = int(residual is not None and residual.dtype == torch.float32)
-    d.act = act
-    d.out_f32 = int(out.dtype == torch.float32)
-    d.ldp = N
-    d.alpha = alpha
-    d.a_rms_weight, d.a_rms_eps = p(a_rms_weight), a_rms_eps
-    d.workspace, d.workspace_bytes = _workspace(A.device, stream()).data_ptr(), GEMM_WS_BYTES
+    if ldb is None:
+        ldb = B4.stride(0) if B4 is not None and B4.dim() == 2 else K // 2
+    d = _decode_desc(A, B4, out, M, N, K, lda, ldb, ldc, residual, ldr, act, alpha, a_rms_weight, a_rms_eps, workspace=True)
     if ld_scale is None:
         ld_scale = s.stride(0) if s is not None and s.dim() == 2 else K // 32
     check(_gemm_w4(C.byref(d), p(s), ld_scale, stream()), "desta_gemm_w4a16_nt")

@@ -80,10 +80,11 @@ def test_hot_kernels_use_no_scratch():
     res = mod.kernel_resources()
     assert len(res) > 100
     hot = ("gemm_bf16_nt_256_kernel", "gemm_bf16_nt_256p_kernel", "gemm_bf16_nt_kernel", "gemm_bf16_nt_ring_kernel", "gemm_bf16_nt_skinny_kernel",
+           "gemm_bf16_nt_skinny_wide_kernel", "gemm_bf16_nt_skinny_wide_fixup_kernel", "gemm_w4a16_nt_kernel",
            "attn_fwd8_k", "attn_bwd_dq8_k", "attn_bwd_dkdv_k", "swiglu", "rmsnorm", "layernorm", "af_apply", "af_stats")
     seen = 0
     for name, r in res.items():
         if any(h in name for h in hot):
             seen += 1
             assert r["scratch"] == 0 and r["spill"] == 0, (name, r)
-    assert seen >= 30
+    assert seen >= 107
