@@ -1169,7 +1169,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256_kernel(GemmArgs p) {
 // until theirs is empty.  Same K loop (k256_loop_2phase), same item -> (tile, K-slice) map and slab layout as the one-tile-per-block
 // kernel, so every item is computed by one block in the same K order with the same epilogue arithmetic: bit-identical results.
 //   * Queues.  Queue x (x = blockIdx.x & 7: blocks dealt round-robin over the XCDs share one) holds the contiguous L range xcd_remap
-//     gives XCD x in the one-tile-per-block grid, in the same order, then the split-K items j = x, x + 8, ... of the tail (slab j).
+//     gives XCD x in the one-tile-per-block grid, in the same order, and the split-K items j = x, x + 8, ... of the tail (slab j).
 //     A ticket is a relaxed agent-scope fetch_add on the queue's counter.  No stealing from other queues.
 //   * Ticket ahead.  Thread 0 draws the NEXT item's ticket in front of the last two K-tiles of the current one (the atomic's latency
 //     hides behind them), and hands it to the block through LDS after the loop's final vmcnt(0).
@@ -1179,9 +1179,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256_kernel(GemmArgs p) {
 //   * Counters.  queue[0..7] = tickets, queue[8] = departures; the last block to depart (every block has drawn its final, empty
 //     ticket) zeroes all nine for the next launch on the stream.  They sit in the last 64 bytes of the caller's workspace, which is
 //     handed over zeroed once (desta_hip.h).
-// EPI: the epilogue instance (k256_epilogue); every instance but act 2 / act 3 also writes raw K-slice slabs.
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, int* queue) {
+//   * Split-K tails.  A queue's K-slice items come behind its whole tiles, or with `flags & P256_SLICES_FIRST` in front of them (their
+//     slab stores then run under the next item's prologue and K loop, and nothing of the tail is left for the end of the launch).
+//     Same items, same slabs: only the ticket -> item map differs.  Neither order wins in the step: behind is the default.
+// EPI: the epilogue instance (k256_epilogue).  TAIL: the grid has a split-K tail (every instance but act 2 / act 3); without one
+// the slices, the slab stores and `flags` compile away, which keeps the per-item path of the short-K grids
+// (Whisper, K = 1280: 20 K-tiles per item) free of them: with one instance for both, those grids measured 6 % slower.
+constexpr int P256_SLICES_FIRST = 1;
+template <int EPI, bool TAIL>
+__global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, int* queue, int flags_) {
+    static_assert(!TAIL || (EPI != E256_SWIGLU_FWD && EPI != E256_SWIGLU_BWD), "the SwiGLU epilogues need whole tiles");
+    const int flags = TAIL ? flags_ : 0;
     __shared__ __attribute__((aligned(16))) char lds[2 * 4 * HT + 16];     // [buf][A0,A1,B0,B1] + the ticket hand-off (one array: see
                                                                             // cdna_hip_programming.md on a second __shared__ object beside glds)
     int* s_ticket = (int*)(lds + 2 * 4 * HT);
@@ -1191,24 +1199,27 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, i
     constexpr int GROUP_M = GEMM_GROUP_M;              // the fix-up / persistent kernels must map L -> tile like the main kernel
     const int nk_all = p.K / BK;
 
-    // this block's queue: whole tiles [lo, lo + n_full) of the L order, then split items j = xq + 8 u
+    // this block's queue: whole tiles [lo, lo + n_full) of the L order and the split items j = xq + 8 u (slices first or last)
     const int xq = blockIdx.x & 7;
     const int F = p.full_tiles, q8 = F >> 3, r8 = F & 7;
     const int lo = (xq < r8) ? xq * (q8 + 1) : r8 * (q8 + 1) + (xq - r8) * q8;
     const int n_full = q8 + (xq < r8 ? 1 : 0);
-    const int n_split_items = p.split > 1 ? (p.tilesM * p.tilesN - F) * p.split : 0;
-    const int n_items = n_full + (n_split_items > xq ? (n_split_items - xq + 7) >> 3 : 0);
+    const int n_split_items = TAIL ? (p.tilesM * p.tilesN - F) * p.split : 0;
+    const int n_slices = n_split_items > xq ? (n_split_items - xq + 7) >> 3 : 0;
+    const int n_items = n_full + n_slices;
+    const int s_lo = (flags & P256_SLICES_FIRST) ? 0 : n_full;       // tickets [s_lo, s_lo + n_slices) are the slices,
+    const int w_lo = (flags & P256_SLICES_FIRST) ? n_slices : 0;     // [w_lo, w_lo + n_full) the whole tiles
     int* counter = queue + xq;
 
     int brow, bcol, kt0, nk, slab;
     bool partial;
     auto geometry = [&](int tk) {                        // ticket -> tile origin, K range, slab
         int L, slice = 0;
-        partial = tk >= n_full;
+        partial = tk >= s_lo && tk < s_lo + n_slices;
         if (!partial) {
-            L = lo + tk;
+            L = lo + tk - w_lo;
         } else {
-            slab = xq + 8 * (tk - n_full);
+            slab = xq + 8 * (tk - s_lo);
             L = F + slab / p.split;
             slice = slab % p.split;
         }
@@ -1280,7 +1291,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_nt_256p_kernel(GemmArgs p, i
 #pragma unroll
             for (int j = 0; j < 7; ++j) st.stage(j);
         }
-        if constexpr (EPI != E256_SWIGLU_FWD && EPI != E256_SWIGLU_BWD) {
+        if constexpr (TAIL) {
             if (cur_partial) {
                 k256_store_slab(p.ws + (long)cur_slab * (256 * 256), wm, wn, fr, fq, acc);
                 continue;
@@ -1771,9 +1782,12 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_skinny_wide_fixup_kernel(Gem
 
 static int g_last_kernel = 0;      // kernel family of the most recent launch: 1 = 128x128, 2 = 256x256 (+ split-K fix-up), 3 = skinny
 extern "C" int desta_gemm_last_kernel(void) { return g_last_kernel; }
+static desta_gemm_plan g_last_plan = {};   // what the most recent desta_gemm_bf16_nt call launched
 static int g_force_variant = 0;   // 0 auto, 1 = 128x128, 2 = 256x256 lockstep, 3 = staggered, 4 / 8 = persistent tile queue (tuning / tests)
 extern "C" int desta_gemm_force_variant(int v) { g_force_variant = v; return DESTA_OK; }
-static int g_persistent = 1;      // option 0: 0 = never the persistent tile-queue kernel, 1 = for multi-round grids without a split-K tail (default), 2 = also with one
+static int g_persistent = 1;      // option 0: 0 = never the persistent tile-queue kernel, 1 = for multi-round grids of more than 256 tiles, split-K tail or not (default), 2 = for every grid of more than 256 items
+static int g_slices_first = 0;    // option 12: a split-tail grid on the tile queue runs its K-slices behind the whole tiles (0, default) or in front of them (1: neither wins in the step)
+static int g_slice_floor8 = 0;    // option 14: grids that can take the tile queue cut their tail into slices of >= 8 K-tiles (1) instead of >= 16 (0, default: another split sums in another order)
 static int g_stagger = 1;         // automatic choice uses the staggered schedule
 static int g_inkernel_splitk = 0; // option 5: K-slices of tail tiles reduced inside the GEMM launch instead of by the fix-up launch (measured: no gain)
 static int g_small_ring = 1;      // option 6: 0 never, 1 the four-slot ring form of the 128x128 kernel when its grid leaves one block per CU, 2 always (A/B runs)
@@ -1797,6 +1811,8 @@ extern "C" int desta_gemm_set_option(int option, int value) {
     else if (option == 5) g_inkernel_splitk = value;
     else if (option == 6) g_small_ring = value;
     else if (option == 10) g_tail_skip = value;
+    else if (option == 12) g_slices_first = value;
+    else if (option == 14) g_slice_floor8 = value;
     else if (option == 11) {
         if (value != 0 && value != 162 && value != 164) { desta_set_error("gemm_set_option: FP8 skinny variant %d unknown (162 164)", value); return DESTA_EINVAL; }
         g_skinny_w8 = value;
@@ -1806,6 +1822,73 @@ extern "C" int desta_gemm_set_option(int option, int value) {
         g_skinny_blocks = value;
     }
     else { desta_set_error("gemm_set_option: unknown option %d", option); return DESTA_EINVAL; }
+    return DESTA_OK;
+}
+
+// The tile choice of desta_gemm_bf16_nt under the current options and force variant: host arithmetic only (desta_gemm_plan_query).
+// The 256x256 kernels run ONE block per CU, so the tile grid executes in rounds of 256; a partial last round leaves CUs idle
+// (M=5120 x N=4096: 320 tiles = 1.25 rounds).  Those tail tiles are cut into `split` K-slices (<= 256 items, each 1/split long:
+// "1 + 1/split" rounds instead of 2), partial sums go to the caller's workspace and are reduced in fixed order by the fix-up launch
+// (or, option 5, inside the one-tile-per-block launch).  The 128x128 kernel (2 blocks/CU) covers small shapes and calls without a workspace.
+static void gemm_plan(const desta_gemm_desc* d, desta_gemm_plan* pl) {
+    constexpr int NCU = 256;
+    const int tM = (d->M + 255) / 256, tN = (d->N + 255) / 256, nk = d->K / BK;
+    const long T = (long)tM * tN;
+    // the persistent tile-queue kernel needs batch 1 and a workspace to hold its queue counters
+    const bool can_persist = d->batch == 1 && d->workspace && d->workspace_bytes >= 4096 && ((uintptr_t)d->workspace % 16) == 0;
+    int split = 1, full = (int)T;
+    if (d->batch == 1 && d->workspace && nk >= 8 && d->act != 2 && d->act != 3) {      // (the SwiGLU epilogues need the whole accumulator tile in registers: no K-slices)
+        const int rem = (int)(T % NCU);
+        if (rem > 0 && rem <= NCU / 2) {
+            // >= 16 K-tiles per slice, or the 7-half-tile prologue dominates; the queue kernel hides that prologue under the previous
+            // item's epilogue, so option 14 lowers the floor to 8 for the grids that can take it (whichever kernel then runs them)
+            const int floor = (g_slice_floor8 && can_persist && T > NCU) ? 8 : 16;
+            int sp = NCU / rem;
+            if (sp > 8) sp = 8;
+            if (sp > nk / floor) sp = nk / floor;
+            if (sp >= 2 && (size_t)rem * sp * 256 * 256 * sizeof(float) + 4096 <= d->workspace_bytes) { split = sp; full = (int)(T - rem); }
+        }
+    }
+    *pl = desta_gemm_plan{};
+    pl->split = 1;
+    if (d->act == 4 || (d->M <= 16 && g_force_variant == 0 && !d->trans_a && !d->trans_b && d->act != 2 && d->act != 3)) {          // decode-time projections: weight streaming
+        pl->kernel = 3;
+        return;
+    }
+    bool big = false;
+    if (d->M >= 128 && d->N >= 128 && d->K >= 512) {
+        const double rounds = (double)full * d->batch / NCU + (split > 1 ? 1.0 / split : 0.0);
+        const double ideal = (double)T * d->batch / NCU;
+        const double eff = ideal / (split > 1 ? rounds : ceil(rounds));      // fraction of CU-time doing work
+        big = eff >= 0.78;
+    }
+    if (g_force_variant == 1) big = false;
+    if (g_force_variant >= 2) big = true;
+    if (d->trans_a || d->trans_b) big = false;                          // transposed-storage operands: 128x128 kernel only
+    if (!big) {
+        pl->kernel = 1;
+        return;
+    }
+    const int items = full + (int)(T - full) * split;
+    // The tile-queue kernel (staggered two-phase schedule): by default for every grid of more than one round of whole tiles, with a
+    // split-K tail or without (option 0 = 1; 2 = any grid of more than 256 items, 0 = never).
+    const bool persistent = can_persist && (g_force_variant == 4 || g_force_variant == 8 ||
+                                            (g_force_variant == 0 && g_stagger && g_phases2 &&
+                                             ((g_persistent == 1 && T > NCU) || (g_persistent == 2 && items > NCU))));
+    pl->kernel = persistent ? 4 : 2;
+    pl->split = split;
+    pl->full_tiles = full;
+    pl->slices_first = persistent && split > 1 && g_slices_first;
+    // Only the one-tile-per-block kernels carry option 5's in-kernel reduce.
+    pl->inkernel = split > 1 && g_inkernel_splitk && !persistent;
+    pl->fixup_launch = split > 1 && !pl->inkernel;
+    pl->items = items;
+}
+extern "C" int desta_gemm_plan_query(const desta_gemm_desc* d, desta_gemm_plan* out) {
+    DESTA_CHECK_ARG(out, "gemm_plan_query: null plan");
+    if (!d) { *out = g_last_plan; return DESTA_OK; }
+    DESTA_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0 && d->K % BK == 0 && d->batch >= 1, "gemm_plan_query: bad shape M=%d N=%d K=%d batch=%d", d->M, d->N, d->K, d->batch);
+    gemm_plan(d, out);
     return DESTA_OK;
 }
 
@@ -1844,24 +1927,12 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
     DESTA_CHECK_ARG(d->act != 3 || d->ldc % 8 == 0, "gemm: act 3 needs ldc (2N-wide rows) to be a multiple of 8");
     DESTA_CHECK_ARG((d->act != 2 && d->act != 3) || (d->N % 64 == 0 && d->ldc % 8 == 0 && d->batch == 1 && !d->trans_a && !d->trans_b && d->dropout_p == 0.f),
                     "gemm: the SwiGLU epilogues work on whole 64-column blocks (N %% 64 == 0), row-major operands, batch 1");
-    // Tile choice.  The 256x256 8-phase kernel runs ONE block per CU, so the tile grid executes in rounds
-    // of 256; a partial last round leaves CUs idle (M=5120 x N=4096: 320 tiles = 1.25 rounds).  Those tail
-    // tiles are cut into `split` K-slices (<= 256 items, each 1/split long: "1 + 1/split" rounds instead
-    // of 2), partial sums go to the caller's workspace and a fix-up launch reduces them in fixed order.
-    // The 128x128 kernel (2 blocks/CU) covers small shapes and calls without a workspace.
     constexpr int NCU = 256;
-    const int tM = (d->M + 255) / 256, tN = (d->N + 255) / 256, nk = d->K / BK;
+    const int tM = (d->M + 255) / 256, tN = (d->N + 255) / 256;
     const long T = (long)tM * tN;
-    int split = 1, full = (int)T;
-    if (d->batch == 1 && d->workspace && nk >= 8 && d->act != 2 && d->act != 3) {      // (the SwiGLU epilogues need the whole accumulator tile in registers: no K-slices)
-        const int rem = (int)(T % NCU);
-        if (rem > 0 && rem <= NCU / 2) {
-            int sp = NCU / rem;
-            if (sp > 8) sp = 8;
-            if (sp > nk / 16) sp = nk / 16;              // >= 16 K-tiles per slice, or the 7-half-tile prologue dominates
-            if (sp >= 2 && (size_t)rem * sp * 256 * 256 * sizeof(float) + 4096 <= d->workspace_bytes) { split = sp; full = (int)(T - rem); }
-        }
-    }
+    desta_gemm_plan pl;
+    gemm_plan(d, &pl);
+    const int split = pl.split, full = pl.full_tiles;
     a.rope_cs = d->rope_cos_sin; a.rope_pos = d->rope_pos; a.rope_cols = d->rope_cols; a.rope_hd = d->rope_head_dim;
     if (d->rope_cos_sin)
         DESTA_CHECK_ARG(d->rope_pos && (d->rope_head_dim == 64 || d->rope_head_dim == 128) && d->rope_cols > 0 && d->rope_cols <= d->N &&
@@ -1873,7 +1944,7 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
         DESTA_CHECK_ARG(d->M <= 16 && (size_t)d->M * 2 * (size_t)d->K <= (size_t)SKINNY_XS_BYTES && d->K % 512 == 0 &&
                         (d->act == 0 || d->act == 4) && g_force_variant == 0,
                         "gemm: a_rms_weight (fused RMSNorm of A) needs M <= 16, M*2K <= %d bytes of LDS, K %% 512 == 0, act 0 or 4", SKINNY_XS_BYTES);
-    if (d->act == 4 || (d->M <= 16 && g_force_variant == 0 && !d->trans_a && !d->trans_b && d->act != 2 && d->act != 3)) {          // decode-time projections: weight streaming
+    if (pl.kernel == 3) {                                               // decode-time projections: weight streaming
         DESTA_CHECK_ARG(d->act != 4 || (d->M <= 16 && !d->out_f32 && !d->bias && !d->residual && !d->preact && d->dropout_p == 0.f),
                         "gemm: act 4 (SwiGLU over concatenated gate|up rows) is the decode path: M <= 16, bf16 out, no other epilogue");
         // 16 columns x 8 K-slices per tile measured fastest on every decode shape (tools/skinny_bench.py; wider
@@ -1896,32 +1967,18 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
 #undef SK_LAUNCH
         DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny");
         g_last_kernel = 3;
+        g_last_plan = pl;
         return DESTA_OK;
     }
-    bool big = false;
-    if (d->M >= 128 && d->N >= 128 && d->K >= 512) {
-        const double rounds = (double)full * d->batch / NCU + (split > 1 ? 1.0 / split : 0.0);
-        const double ideal = (double)T * d->batch / NCU;
-        const double eff = ideal / (split > 1 ? rounds : ceil(rounds));      // fraction of CU-time doing work
-        big = eff >= 0.78;
-    }
-    if (g_force_variant == 1) big = false;
-    if (g_force_variant >= 2) big = true;
-    if (d->trans_a || d->trans_b) big = false;                          // transposed-storage operands: 128x128 kernel only
+    const bool big = pl.kernel != 1;
     if (big) {
         a.tilesM = tM; a.tilesN = tN;
         a.full_tiles = full; a.split = split; a.ws = (float*)d->workspace;
         const int items = full + (int)(T - full) * split;
-        // The persistent tile-queue kernel (staggered two-phase schedule; batch 1, a workspace to hold its queue counters): by default
-        // for grids of more than one round of whole tiles without a split-K tail (option 0 = 1; 2 = split-tail grids too, 0 = never).
-        const bool can_persist = d->batch == 1 && d->workspace && d->workspace_bytes >= 4096 && ((uintptr_t)d->workspace % 16) == 0;
-        const bool persistent = can_persist && (g_force_variant == 4 || g_force_variant == 8 ||
-                                                (g_force_variant == 0 && g_stagger && g_phases2 &&
-                                                 ((g_persistent == 1 && split == 1 && T > NCU) || (g_persistent == 2 && items > NCU))));
+        const bool persistent = pl.kernel == 4, inkernel = pl.inkernel != 0;
         // tickets: the last 4 KiB of the workspace (<= 128 split tiles: its first 1 KiB); zero at first use (the caller hands over a
         // zeroed workspace once) and self-resetting afterwards.  Only the one-tile-per-block kernels carry the in-kernel reduce.
         // The persistent kernel's nine queue counters are the last 64 bytes, self-resetting the same way.
-        const bool inkernel = split > 1 && g_inkernel_splitk && !persistent;
         a.tickets = inkernel ? (int*)((char*)d->workspace + d->workspace_bytes - 4096) : nullptr;
         hipStream_t st = (hipStream_t)stream;
         if (persistent) {
@@ -1931,9 +1988,11 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
             const int mode = (d->bias ? 1 : 0) | (d->act == 1 ? 2 : 0) | (d->rope_cos_sin ? 4 : 0) | (d->residual ? 8 : 0) | (d->preact ? 16 : 0);
             const bool f32_stream = d->out_f32 && d->bias && d->residual && d->residual_f32 && !d->preact && d->act == 0 && a.drop_thresh == 0;
             const dim3 grid(NCU), blk(512);
-#define P256_LAUNCH(E_) hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<E_>), grid, blk, 0, st, a, queue)
-            if (d->act == 2) P256_LAUNCH(E256_SWIGLU_FWD);
-            else if (d->act == 3) P256_LAUNCH(E256_SWIGLU_BWD);
+            const int flags = pl.slices_first ? P256_SLICES_FIRST : 0;
+#define P256_LAUNCH(E_) do { if (split > 1) hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<E_, true>), grid, blk, 0, st, a, queue, flags); \
+                             else hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<E_, false>), grid, blk, 0, st, a, queue, flags); } while (0)
+            if (d->act == 2) hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<E256_SWIGLU_FWD, false>), grid, blk, 0, st, a, queue, 0);
+            else if (d->act == 3) hipLaunchKernelGGL((gemm_bf16_nt_256p_kernel<E256_SWIGLU_BWD, false>), grid, blk, 0, st, a, queue, 0);
             else if (wide && mode == 0) P256_LAUNCH(0);                // plain
             else if (wide && mode == 8) P256_LAUNCH(8);                // residual
             else if (wide && mode == 4) P256_LAUNCH(4);                // rotary
@@ -1950,7 +2009,7 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
         else if (g_force_variant == 6 || g_force_variant == 4 || g_force_variant == 8 || (g_force_variant == 0 && g_phases2)) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 2>), dim3(items, d->batch), dim3(512), 0, st, a);
         else if (g_force_variant == 7) hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<false, 2>), dim3(items, d->batch), dim3(512), 0, st, a);
         else hipLaunchKernelGGL((gemm_bf16_nt_256_kernel<true, 4>), dim3(items, d->batch), dim3(512), 0, st, a);
-        if (split > 1 && !inkernel)
+        if (pl.fixup_launch)
             hipLaunchKernelGGL(gemm_splitk_fixup_kernel, dim3((unsigned)(T - full) * 64, d->batch), dim3(256), 0, (hipStream_t)stream, a);
     } else {
         a.tilesM = (d->M + BM - 1) / BM; a.tilesN = (d->N + BN - 1) / BN;
@@ -1970,6 +2029,7 @@ extern "C" int desta_gemm_bf16_nt(const desta_gemm_desc* d, void* stream) {
     }
     DESTA_CHECK_LAUNCH("gemm_bf16_nt");
     g_last_kernel = big ? 2 : 1;
+    g_last_plan = pl;
     return DESTA_OK;
 }
 

@@ -118,6 +118,32 @@ def gemm(A, B, out, M, N, K, *, lda=None, ldb=None, ldc=None, bias=None, residua
     return out
 
 
+class GemmPlan(C.Structure):
+    _fields_ = [(n, i32) for n in ("kernel", "split", "full_tiles", "items", "slices_first", "inkernel", "fixup_launch")]
+
+
+_gemm_plan = _sig("desta_gemm_plan_query", C.POINTER(GemmDesc), C.POINTER(GemmPlan)) if hasattr(lib, "desta_gemm_plan_query") else None   # (an A/B library of an earlier tree, DESTA_HIP_LIB)
+GEMM_PLAN_KERNELS = {1: "128", 2: "256", 3: "skinny", 4: "256p"}
+
+
+def gemm_plan(M=None, N=None, K=None, *, batch=1, act=0, trans_a=False, trans_b=False, workspace=True) -> dict:
+    """What `gemm` launches for this shape under the current options (host arithmetic in the library, no device needed);
+    without a shape: what the most recent `gemm` call launched."""
+    pl = GemmPlan()
+    if M is None:
+        check(_gemm_plan(None, C.byref(pl)), "desta_gemm_plan_query")
+    else:
+        d = GemmDesc()
+        d.M, d.N, d.K, d.batch, d.act = M, N, K, batch, act
+        d.trans_a, d.trans_b = int(trans_a), int(trans_b)
+        if workspace:                                            # (only tested against NULL and for alignment)
+            d.workspace, d.workspace_bytes = 1 << 20, GEMM_WS_BYTES
+        check(_gemm_plan(C.byref(d), C.byref(pl)), "desta_gemm_plan_query")
+    out = {n: getattr(pl, n) for n, _ in GemmPlan._fields_}
+    out["kernel"] = GEMM_PLAN_KERNELS[pl.kernel]
+    return out
+
+
 def rms_fusable(M: int, K: int) -> bool:
     """True when `gemm(..., a_rms_weight=)` can normalise the M rows of A in LDS (decode path)."""
     return M <= 16 and M * 2 * K <= 8 * 4096 * 2 and K % 512 == 0

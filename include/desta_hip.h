@@ -123,15 +123,32 @@ int desta_gemm_force_variant(int variant);
 /* kernel family the most recent desta_gemm_bf16_nt call launched: 1 = 128x128, 2 = 256x256 (+ split-K fix-up), 3 = skinny
  * (bench.py attributes its HIP-event timings to the dominant kernel with this) */
 int desta_gemm_last_kernel(void);
+/* What desta_gemm_bf16_nt launches for `d` under the current options and force variant, without launching anything (host
+ * arithmetic only: no device needed; of the descriptor it reads the shape, batch, act, trans_*, workspace and workspace_bytes).
+ * d == NULL: the plan of the most recent desta_gemm_bf16_nt call. */
+typedef struct desta_gemm_plan {
+    int kernel;          /* 1 = 128x128, 2 = 256x256 one tile per block, 3 = skinny, 4 = 256x256 persistent tile queue */
+    int split;           /* K-slices per tail tile (1 = no split-K tail) */
+    int full_tiles;      /* whole tiles in front of the tail (256x256 kernels) */
+    int items;           /* work items of the main launch: whole tiles + K-slices */
+    int slices_first;    /* tile queue: the K-slices precede the whole tiles in every queue (option 12) */
+    int inkernel;        /* one tile per block: slabs reduced inside the launch (option 5) */
+    int fixup_launch;    /* a gemm_splitk_fixup launch follows */
+} desta_gemm_plan;
+int desta_gemm_plan_query(const desta_gemm_desc* d, desta_gemm_plan* out);
 int desta_gemm_set_persistent(int on);   /* = desta_gemm_set_option(0, on) */
-/* A/B switches of the automatic choice: option 0 = persistent tile-queue 256x256 kernel (0 never; 1, default: batch 1, a workspace,
- * more than one round of 256 whole tiles and no split-K tail; 2: also grids with a split-K tail), 1 = staggered, 2 = skinny (M <= 16) kernel variant
+/* A/B switches of the automatic choice: option 0 = persistent tile-queue 256x256 kernel (0 never; 1, default: batch 1, a workspace
+ * and more than 256 tiles, with a split-K tail or without; 2: every such grid of more than 256 work items), 1 = staggered, 2 = skinny (M <= 16) kernel variant
  * (0 auto, else COLS*10 + U: 162 164 322 641), 3 = persistent grid size of the skinny kernel (default 512 = 2 blocks per CU),
  * 4 = two-phase schedule of the 256x256 kernel (default 1; 0 = the four-phase schedule), 5 = K-slices of tail tiles reduced inside
  * the GEMM launch instead of by the fix-up launch (default 0), 6 = four-slot software-pipelined ring form of the 128x128 kernel:
  * 0 never, 1 (default) when the grid leaves one block per CU (<= 256 tiles), 2 always; 10 = the two-phase 256x256 kernel stops its
  * half-tile stream at the last K-tile (default 1; 0 = re-load dead slots as rounds 1-3 did); bit-identical results in every setting.
  * 11 = pipeline depth of the weight-only FP8 skinny kernel (0 auto, else 162 / 164; act 0 only; same bits either way).
+ * Split-K tails on the tile queue: 12 = the K-slices run in front of a queue's whole tiles (default 0: behind them); same bits
+ * either way.  14 = grids that CAN take the tile queue (batch 1, a workspace, more than 256 tiles) cut their tail into slices of
+ * >= 8 K-tiles instead of >= 16, whichever kernel then runs them (default 0; another split adds the slices in another order, so
+ * this one changes low-order bits).  Option 13 (round 27's reduce inside the queue launch, measured slower) returns DESTA_EINVAL.
  * Options 7, 8 (round 3's de-synchronised start) and 9 (round 4's polynomial GELU) were removed and return DESTA_EINVAL. */
 int desta_gemm_set_option(int option, int value);
 
