@@ -309,22 +309,71 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_k(const bf16_t* __restrict__ 
 // NORM: 0 = plain rope; 1 = fwd (rmsnorm with weight then rope); 2 = bwd of (1) given saved pre-norm x.
 // KV-cache append (generate()): with kv.dst the grid also covers the V heads that follow K in `buf`; rotated K heads and
 // plain V heads of row (b, s) are ALSO written to kv.dst + b*bs + (slot0 + s)*rs + (head - n_q)*HD (the K|V slab).
+// BIAS (Qwen2 / Qwen2.5, TF:models/qwen2/modeling_qwen2.py attention: q_proj, k_proj, v_proj = nn.Linear(bias=True)): the
+// projection GEMM stays bias-free on every path and leaves bf16(x W^T); the kernel that rotates adds the fp32 bias
+// [(n_q + 2 n_kv) * HD] to the row, rotates q and k in fp32 and rounds once, and rounds v as bf16(v + b).  So a BIAS grid always
+// covers the n_kv V heads, cache or not, which the bias-free forms touch only to copy them into a cache.
+// No q/k-norm (no model has both), no backward (d(pre-bias) = d(post-bias), the bias itself is frozen).  With a zero bias the
+// q|k bits are the bias-free ones: x + 0 = x (an input of -0 would come out as +0; a GEMM output is not -0).
 struct RopeKV { bf16_t* dst; long bs, rs; int slot0; int n_v; };
-// Forward rotation of lane j's 2 x 8 elements of the head at p, position pos (NORM == 1: RMSNorm with weight w first, rounded to
-// bf16 twice as HF does).  Every lane of a head group has to get here: the norm's sum is a shuffle over the group.
-template <int HD, int NORM>
-__device__ __forceinline__ void rope_fwd_rotate(const bf16_t* p, int j, int pos, const float* __restrict__ cs, const float* __restrict__ w,
-                                                float eps, float (&oa)[8], float (&ob)[8]) {
+// Thread -> (head group, lane j of its G = HD/16) -> (row, head) over rows x all_heads heads.  Lanes past the end keep row 0,
+// head 0 with active = false: a head is G adjacent lanes, and the norm and the FP8 amax shuffle over the whole group.
+struct RopeLane { int j, row, head; bool active; };
+template <int HD>
+__device__ __forceinline__ RopeLane rope_lane(int rows, int n_heads, int n_v) {
+    constexpr int G = HD / 16;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const long grp = gid / G;
+    RopeLane t;
+    t.j = (int)(gid % G);
+    const int all_heads = n_heads + n_v;
+    t.active = grp < (long)rows * all_heads;
+    t.row = t.active ? (int)(grp / all_heads) : 0;
+    t.head = t.active ? (int)(grp % all_heads) : 0;
+    return t;
+}
+// position_ids: arange(S) for every row in training (H7); generate() passes a per-sequence shift
+// (-left_pad for the prompt, cache_length - left_pad for a decode step) as HF derives them from the mask
+// sm_batch > 0: the token grid is stored position-major (row = s * batch + b), else batch-major (row = b * S + s)
+__device__ __forceinline__ int rope_pos(int row, int S, int sm_batch, const int* pos_shift) {
+    const int spos = sm_batch ? row / sm_batch : row % S, bidx = sm_batch ? row % sm_batch : row / S;
+    return pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
+}
+// Where K or V head `head` of batch-major row (b, s) goes in a cache laid out [batch: bs][slot: rs][n_kv K heads | n_kv V heads] with
+// W elements per head: the K|V slab (W = HD) and the FP8 cache's scales (W = 1).
+template <int W, typename T>
+__device__ __forceinline__ T* rope_slot(T* dst, long bs, long rs, int slot0, int row, int S, int head, int n_q) {
+    return dst + (long)(row / S) * bs + (long)(slot0 + row % S) * rs + (long)(head - n_q) * W;
+}
+// Lane j's 2 x 8 elements of the head at p, forward: load, BIAS: add bias[0..HD) in fp32, NORM == 1: RMSNorm with weight w
+// (rounded to bf16 twice as HF does), then the rotation at position pos, or rotate == false (a V head): pass through.  Every
+// lane of a head group has to get here: the norm's sum is a shuffle over the group.
+template <int HD, int NORM, bool BIAS>
+__device__ __forceinline__ void rope_head(const bf16_t* p, int j, bool rotate, int pos, const float* __restrict__ cs, const float* __restrict__ w,
+                                          float eps, const float* __restrict__ bias, float (&oa)[8], float (&ob)[8]) {
     constexpr int G = HD / 16, H2 = HD / 2;
-    float a[8], b[8], c[8], s[8];
+    float a[8], b[8];
     load8(p, 8 * j, 0, a);
     load8(p, H2 + 8 * j, 0, b);
+    if constexpr (BIAS) {
+        float ba[8], bb[8];
+        load8(bias, 8 * j, 1, ba);
+        load8(bias, H2 + 8 * j, 1, bb);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { a[e] += ba[e]; b[e] += bb[e]; }
+    }
+    if (!rotate) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { oa[e] = a[e]; ob[e] = b[e]; }
+        return;
+    }
+    float c[8], s[8];
     load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
     load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
     // The sums of two products are spelled as fmaf(x, y, u * v): under -ffp-contract=fast the compiler is free to fuse either
-    // product of "x * y + u * v", and which one it takes varies with the code around it, so the two kernels that inline this
-    // would not round alike.  These are the forms both kernels were compiled to before the rotation became one function.
-    if (NORM == 1) {
+    // product of "x * y + u * v", and which one it takes varies with the code around it, so the kernels that inline this
+    // would not round alike.  These are the forms the kernels were compiled to before the rotation became one function.
+    if constexpr (NORM == 1) {
         float q = 0.f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) q += fmaf(a[e], a[e], b[e] * b[e]);
@@ -343,38 +392,35 @@ __device__ __forceinline__ void rope_fwd_rotate(const bf16_t* p, int j, int pos,
 #pragma unroll
     for (int e = 0; e < 8; ++e) { oa[e] = fmaf(a[e], c[e], -(b[e] * s[e])); ob[e] = fmaf(b[e], c[e], a[e] * s[e]); }
 }
-template <int HD, int NORM, bool BWD>
+// n_heads = n_q + n_kv rotated heads, then the V heads: kv.n_v of them (0 without a cache), BIAS: always n_kv = n_heads - n_q.
+// kv.dst == nullptr: in place only (training / eval forward).  BIAS is instantiated for NORM == 0, BWD == false only.
+template <int HD, int NORM, bool BWD, bool BIAS>
 __global__ __launch_bounds__(256) void rope_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
                                               const float* __restrict__ cs, const float* __restrict__ wq,
                                               const float* __restrict__ wk, float eps, const bf16_t* __restrict__ pre,
-                                              long ld_pre, const int* __restrict__ pos_shift, RopeKV kv, int sm_batch) {
+                                              long ld_pre, const int* __restrict__ pos_shift, RopeKV kv, int sm_batch,
+                                              const float* __restrict__ bias) {
     constexpr int G = HD / 16, H2 = HD / 2;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long grp = gid / G;
-    const int j = (int)(gid % G);
-    const int all_heads = n_heads + kv.n_v;                              // kv.n_v = 0 without a cache
-    const bool active = grp < (long)rows * all_heads;
-    const int row = active ? (int)(grp / all_heads) : 0, head = active ? (int)(grp % all_heads) : 0;
-    if (!BWD && head >= n_heads) {                                       // V head: copy into the cache (no whole-wave op follows)
+    const RopeLane t = rope_lane<HD>(rows, n_heads, BIAS ? n_heads - n_q : kv.n_v);
+    const int j = t.j, row = t.row, head = t.head;
+    if constexpr (BIAS) {
+        if (!t.active) return;                                           // no whole-wave op follows
+    } else if (!BWD && head >= n_heads) {                                // V head: copy into the cache (no whole-wave op follows)
         const bf16_t* src = buf + (long)row * ld + (long)head * HD;
-        bf16_t* d = kv.dst + (long)(row / S) * kv.bs + (long)(kv.slot0 + row % S) * kv.rs + (long)(head - n_q) * HD;
+        bf16_t* d = rope_slot<HD>(kv.dst, kv.bs, kv.rs, kv.slot0, row, S, head, n_q);
         *(u16x8*)(d + 8 * j) = *(const u16x8*)(src + 8 * j);
         *(u16x8*)(d + H2 + 8 * j) = *(const u16x8*)(src + H2 + 8 * j);
         return;
     }
-    // position_ids: arange(S) for every row in training (H7); generate() passes a per-sequence shift
-    // (-left_pad for the prompt, cache_length - left_pad for a decode step) as HF derives them from the mask
-    // sm_batch > 0: the token grid is stored position-major (row = s * batch + b), else batch-major (row = b * S + s)
-    const int spos = sm_batch ? row / sm_batch : row % S, bidx = sm_batch ? row % sm_batch : row / S;
-    const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
+    const int pos = rope_pos(row, S, sm_batch, pos_shift);
     bf16_t* p = buf + (long)row * ld + (long)head * HD;
     if (!BWD) {
         float oa[8], ob[8];
-        rope_fwd_rotate<HD, NORM>(p, j, pos, cs, head < n_q ? wq : wk, eps, oa, ob);
-        if (active) {
+        rope_head<HD, NORM, BIAS>(p, j, !BIAS || head < n_heads, pos, cs, head < n_q ? wq : wk, eps, BIAS ? bias + (long)head * HD : nullptr, oa, ob);
+        if (t.active) {
             store8_bf16(p, 8 * j, oa); store8_bf16(p, H2 + 8 * j, ob);
-            if (kv.dst && head >= n_q) {
-                bf16_t* d = kv.dst + (long)(row / S) * kv.bs + (long)(kv.slot0 + row % S) * kv.rs + (long)(head - n_q) * HD;
+            if (kv.dst && head >= n_q) {                                 // cache rows are batch-major (the entry points pass sm_batch = 0)
+                bf16_t* d = rope_slot<HD>(kv.dst, kv.bs, kv.rs, kv.slot0, row, S, head, n_q);
                 store8_bf16(d, 8 * j, oa); store8_bf16(d, H2 + 8 * j, ob);
             }
         }
@@ -414,7 +460,7 @@ __global__ __launch_bounds__(256) void rope_k(bf16_t* __restrict__ buf, long ld,
 #pragma unroll
             for (int e = 0; e < 8; ++e) { ga[e] = rstd * (ga[e] - xa[e] * t); gb[e] = rstd * (gb[e] - xb[e] * t); }
         }
-        if (active) { store8_bf16(p, 8 * j, ga); store8_bf16(p, H2 + 8 * j, gb); }
+        if (t.active) { store8_bf16(p, 8 * j, ga); store8_bf16(p, H2 + 8 * j, gb); }
     }
 }
 
@@ -816,45 +862,41 @@ extern "C" int desta_rmsnorm_bwd(const void* dy, const void* x, const float* wei
 }
 
 namespace {
-// RoPE + QUANTISING KV-cache append (the opt-in FP8 cache of generate()): rope_k<128, NORM, false> with the cache written as
+// RoPE + QUANTISING KV-cache append (the opt-in FP8 cache of generate()): rope_k<128, NORM, false, BIAS> with the cache written as
 // OCP e4m3 bytes + one power-of-two fp32 scale per (row, slot, K-or-V head), the rule of desta_quantize_rows_e4m3 with "row"
 // = one head's 128 values.  q and k are rotated in place with the bits rope_k leaves; what is quantised is the bf16 value the
-// bf16 cache would hold.  A head is 8 adjacent lanes, so its amax is three xor shuffles.
+// bf16 cache would hold (BIAS: after the bias, k: after the rotation).  A head is 8 adjacent lanes, so its amax is three xor
+// shuffles.
 struct RopeKV8 { uint8_t* dst; float* scale; long bs, rs, sbs, srs; int slot0; int n_v; };
-template <int NORM>
+template <int NORM, bool BIAS>
 __global__ __launch_bounds__(256) void rope_kv8_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
                                                   const float* __restrict__ cs, const float* __restrict__ wq,
-                                                  const float* __restrict__ wk, float eps, const int* __restrict__ pos_shift, RopeKV8 kv) {
+                                                  const float* __restrict__ wk, float eps, const int* __restrict__ pos_shift, RopeKV8 kv,
+                                                  const float* __restrict__ bias) {
     constexpr int HD = 128, G = HD / 16, H2 = HD / 2;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long grp = gid / G;
-    const int j = (int)(gid % G);
-    const int all_heads = n_heads + kv.n_v;
-    const bool active = grp < (long)rows * all_heads;
-    const int row = active ? (int)(grp / all_heads) : 0, head = active ? (int)(grp % all_heads) : 0;
+    const RopeLane t = rope_lane<HD>(rows, n_heads, kv.n_v);
+    const int j = t.j, row = t.row, head = t.head;
     bf16_t* p = buf + (long)row * ld + (long)head * HD;
     u16x8 ca, cb;                                                        // the bf16 bits a bf16 cache would hold
-    if (head >= n_heads) {                                               // V head: as stored
+    if (!BIAS && head >= n_heads) {                                      // bias-free V head: as stored
         ca = *(const u16x8*)(p + 8 * j);
         cb = *(const u16x8*)(p + H2 + 8 * j);
     } else {
-        const int spos = row % S, bidx = row / S;
-        const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
+        const int pos = rope_pos(row, S, 0, pos_shift);
         float oa[8], ob[8];
-        rope_fwd_rotate<HD, NORM>(p, j, pos, cs, head < n_q ? wq : wk, eps, oa, ob);
+        rope_head<HD, NORM, BIAS>(p, j, !BIAS || head < n_heads, pos, cs, head < n_q ? wq : wk, eps, BIAS ? bias + (long)head * HD : nullptr, oa, ob);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { ca[e] = f2bf(oa[e]); cb[e] = f2bf(ob[e]); }
-        if (active) { *(u16x8*)(p + 8 * j) = ca; *(u16x8*)(p + H2 + 8 * j) = cb; }
+        if (t.active) { *(u16x8*)(p + 8 * j) = ca; *(u16x8*)(p + H2 + 8 * j) = cb; }
     }
     unsigned amax = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) amax = max(amax, max((unsigned)(ca[e] & 0x7fff), (unsigned)(cb[e] & 0x7fff)));
 #pragma unroll
     for (int o = 1; o < G; o <<= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, o, 64));
-    if (!active || head < n_q) return;
+    if (!t.active || head < n_q) return;
     const int ex = amax ? e4m3_row_exponent(amax) : 0;
-    const long b = row / S, slot = kv.slot0 + row % S;
-    uint8_t* d = kv.dst + b * kv.bs + slot * kv.rs + (long)(head - n_q) * HD;
+    uint8_t* d = rope_slot<HD>(kv.dst, kv.bs, kv.rs, kv.slot0, row, S, head, n_q);
     unsigned w[4];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -871,249 +913,137 @@ __global__ __launch_bounds__(256) void rope_kv8_k(bf16_t* __restrict__ buf, long
     }
     *(uint2*)(d + 8 * j) = make_uint2(w[0], w[1]);
     *(uint2*)(d + H2 + 8 * j) = make_uint2(w[2], w[3]);
-    if (j == 0) kv.scale[b * kv.sbs + slot * kv.srs + (head - n_q)] = pow2f(ex);
+    if (j == 0) *rope_slot<1>(kv.scale, kv.sbs, kv.srs, kv.slot0, row, S, head, n_q) = pow2f(ex);
 }
+
+// One call of any of the six rotary entry points: the arguments all of them take, then what only some do.
+struct RopeCall {
+    void* buf; int64_t ld; int rows, seq, n_q, n_kv, hd;
+    const float *cos_sin, *wq, *wk; float eps;
+    const int32_t* pos_shift; void* stream;
+    const void* pre = nullptr; int64_t ld_pre = 0; int backward = 0, sm_batch = 0;       // desta_rope, desta_rope_bias
+    bool has_bias = false; const float* bias = nullptr;                                  // the _bias forms
+    bool has_cache = false; void* cache = nullptr; int64_t kbs = 0, krs = 0; int slot0 = 0;    // the _kv_append forms
+    bool e4m3 = false; float* scale = nullptr; int64_t sbs = 0, srs = 0;                 // the _e4m3 forms
+};
 }  // namespace
 
-static int rope_launch(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
-                       const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
-                       const void* pre_norm, int64_t ld_pre, int backward, const int32_t* pos_shift, RopeKV kv, int sm_batch, void* stream) {
-    DESTA_CHECK_ARG(buf && cos_sin, "rope: null argument");
-    DESTA_CHECK_ARG(head_dim == 64 || head_dim == 128, "rope: head_dim %d unsupported (64 or 128)", head_dim);
-    DESTA_CHECK_ARG(ld % 8 == 0 && rows > 0 && seq > 0, "rope: bad shape");
-    const bool norm = q_norm_w != nullptr;
-    DESTA_CHECK_ARG(!norm || k_norm_w, "rope: q_norm without k_norm");
-    DESTA_CHECK_ARG(!(norm && backward) || pre_norm, "rope: backward with q/k norm needs the saved pre-norm q/k");
-    const int nh = n_q_heads + n_kv_heads;
-    const long nthreads = (long)rows * (nh + kv.n_v) * (head_dim / 16);
-    dim3 grid((unsigned)((nthreads + 255) / 256));
-    hipStream_t st = (hipStream_t)stream;
-#define ROPE_ARGS grid, dim3(256), 0, st, (bf16_t*)buf, (long)ld, rows, seq, nh, n_q_heads, cos_sin, q_norm_w, k_norm_w, eps, (const bf16_t*)pre_norm, (long)ld_pre, pos_shift, kv, sm_batch
-    if (head_dim == 128) {
-        if (!backward) { if (norm) hipLaunchKernelGGL((rope_k<128, 1, false>), ROPE_ARGS); else hipLaunchKernelGGL((rope_k<128, 0, false>), ROPE_ARGS); }
-        else { if (norm) hipLaunchKernelGGL((rope_k<128, 2, true>), ROPE_ARGS); else hipLaunchKernelGGL((rope_k<128, 0, true>), ROPE_ARGS); }
-    } else {
-        if (!backward) { if (norm) hipLaunchKernelGGL((rope_k<64, 1, false>), ROPE_ARGS); else hipLaunchKernelGGL((rope_k<64, 0, false>), ROPE_ARGS); }
-        else { if (norm) hipLaunchKernelGGL((rope_k<64, 2, true>), ROPE_ARGS); else hipLaunchKernelGGL((rope_k<64, 0, true>), ROPE_ARGS); }
+// The one argument check: every condition is a fact about memory the kernels touch (or a combination no kernel exists for), so
+// a form is held to it exactly when its kernel makes that access.  A cache or a bias makes the grid cover the V heads.
+static int rope_check(const char* who, const RopeCall& c) {
+    const bool covers_v = c.has_cache || c.has_bias;
+    DESTA_CHECK_ARG(c.buf && c.cos_sin && (!c.has_bias || c.bias), "%s: null argument", who);
+    DESTA_CHECK_ARG(!c.has_bias || (!c.wq && !c.wk), "%s: a q|k|v bias together with q/k-norm weights is not supported", who);
+    DESTA_CHECK_ARG(c.hd == 128 || (c.hd == 64 && !c.e4m3), "%s: head_dim %d unsupported (%s)", who, c.hd, c.e4m3 ? "128" : "64 or 128");
+    DESTA_CHECK_ARG(!c.wq == !c.wk, "%s: q_norm and k_norm come together", who);
+    DESTA_CHECK_ARG(!(c.wq && c.backward) || c.pre, "%s: backward with q/k norm needs the saved pre-norm q/k", who);
+    DESTA_CHECK_ARG(c.sm_batch >= 0 && (c.sm_batch == 0 || c.rows % c.sm_batch == 0), "%s: rows must be a multiple of s_major_batch", who);
+    DESTA_CHECK_ARG(c.rows > 0 && c.seq > 0 && (!covers_v || (c.n_q > 0 && c.n_kv > 0)), "%s: bad shape", who);
+    DESTA_CHECK_ARG(c.ld % 8 == 0 && (!covers_v || c.ld >= (int64_t)(c.n_q + 2 * c.n_kv) * c.hd),
+                    "%s: ld %lld is not a multiple of 8%s", who, (long long)c.ld, covers_v ? " that holds q|k|v" : "");
+    if (c.has_cache) {                                                   // slot (row / seq, slot0 + row % seq) of a batch-major grid
+        DESTA_CHECK_ARG(c.rows % c.seq == 0, "%s: rows must be a multiple of seq", who);
+        DESTA_CHECK_ARG(c.cache && c.krs % 8 == 0 && c.kbs % 8 == 0 && c.slot0 >= 0 && c.krs >= 2L * c.n_kv * c.hd && c.kbs >= 0 &&
+                        (!c.e4m3 || (c.scale && c.srs >= 2L * c.n_kv && c.sbs >= 0)), "%s: bad cache argument", who);
     }
-#undef ROPE_ARGS
-    DESTA_CHECK_LAUNCH("rope");
+    DESTA_CHECK_ARG((uintptr_t)c.buf % 16 == 0 && (uintptr_t)c.cos_sin % 16 == 0 && (uintptr_t)c.bias % 16 == 0 && (uintptr_t)c.cache % 16 == 0 &&
+                    (uintptr_t)c.scale % 4 == 0, "%s: buffers must be 16-byte aligned", who);
     return DESTA_OK;
 }
 
-extern "C" int desta_rope(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
-                          const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
-                          const void* pre_norm, int64_t ld_pre, int backward, const int32_t* pos_shift, int s_major_batch,
-                          void* stream) {
-    DESTA_CHECK_ARG(s_major_batch >= 0 && (s_major_batch == 0 || rows % s_major_batch == 0), "rope: rows must be a multiple of s_major_batch");
-    const RopeKV kv = {nullptr, 0, 0, 0, 0};
-    return rope_launch(buf, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, eps, pre_norm, ld_pre, backward,
-                       pos_shift, kv, s_major_batch, stream);
-}
-
-extern "C" int desta_rope_kv_append(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
-                                    const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
-                                    const int32_t* pos_shift, void* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
-                                    int slot0, void* stream) {
-    DESTA_CHECK_ARG(kv_cache && kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0 && slot0 >= 0, "rope_kv_append: bad cache argument");
-    DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0 && (uintptr_t)qkv % 16 == 0, "rope_kv_append: buffers must be 16-byte aligned");
-    const RopeKV kv = {(bf16_t*)kv_cache, (long)kv_batch_stride, (long)kv_row_stride, slot0, n_kv_heads};
-    return rope_launch(qkv, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, eps, nullptr, 0, 0, pos_shift, kv, 0, stream);
-}
-
-extern "C" int desta_rope_kv_append_e4m3(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
-                                         const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
-                                         const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
-                                         float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream) {
-    DESTA_CHECK_ARG(qkv && cos_sin, "rope_kv_append_e4m3: null argument");
-    DESTA_CHECK_ARG(head_dim == 128, "rope_kv_append_e4m3: head_dim %d unsupported (128)", head_dim);
-    DESTA_CHECK_ARG(ld % 8 == 0 && rows > 0 && seq > 0 && rows % seq == 0 && n_q_heads > 0 && n_kv_heads > 0, "rope_kv_append_e4m3: bad shape");
-    DESTA_CHECK_ARG(!q_norm_w == !k_norm_w, "rope_kv_append_e4m3: q_norm and k_norm come together");
-    DESTA_CHECK_ARG(kv_cache && kv_scale && kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0 && slot0 >= 0 &&
-                    kv_row_stride >= 2L * n_kv_heads * 128 && scale_row_stride >= 2L * n_kv_heads && scale_batch_stride >= 0,
-                    "rope_kv_append_e4m3: bad cache argument");
-    DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)kv_scale % 4 == 0,
-                    "rope_kv_append_e4m3: buffers must be 16-byte aligned");
-    const RopeKV8 kv = {kv_cache, kv_scale, (long)kv_batch_stride, (long)kv_row_stride, (long)scale_batch_stride, (long)scale_row_stride,
-                        slot0, n_kv_heads};
-    const int nh = n_q_heads + n_kv_heads;
-    const long nthreads = (long)rows * (nh + n_kv_heads) * 8;
+static int rope_launch(const char* who, const RopeCall& c) {             // rope_k: in place, or into the bf16 cache
+    const RopeKV kv = {(bf16_t*)c.cache, (long)c.kbs, (long)c.krs, c.slot0, c.has_cache || c.has_bias ? c.n_kv : 0};
+    const int nh = c.n_q + c.n_kv;
+    const long nthreads = (long)c.rows * (nh + kv.n_v) * (c.hd / 16);
     const dim3 grid((unsigned)((nthreads + 255) / 256));
-    hipStream_t st = (hipStream_t)stream;
-    if (q_norm_w) hipLaunchKernelGGL((rope_kv8_k<1>), grid, dim3(256), 0, st, (bf16_t*)qkv, (long)ld, rows, seq, nh, n_q_heads, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, kv);
-    else hipLaunchKernelGGL((rope_kv8_k<0>), grid, dim3(256), 0, st, (bf16_t*)qkv, (long)ld, rows, seq, nh, n_q_heads, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, kv);
-    DESTA_CHECK_LAUNCH("rope_kv_append_e4m3");
-    return DESTA_OK;
-}
-
-// ------------------------------------------------------------------------------------ RoPE with a q|k|v projection bias
-// Qwen2 / Qwen2.5 (TF:models/qwen2/modeling_qwen2.py attention: q_proj, k_proj, v_proj = nn.Linear(bias=True)).  The projection
-// GEMM stays bias-free on every path and leaves bf16(x W^T); the kernel that rotates reads that row, adds the fp32 bias
-// [(n_q + 2 n_kv) * HD], then rotates q and k in fp32 and rounds once, and rounds v as bf16(v + b).  So the grid always covers
-// the V heads, which the bias-free forms touch only to copy them into a cache.  No q/k-norm (no model has both), no backward
-// (d(pre-bias) = d(post-bias), the bias itself is frozen).  With a zero bias the q|k bits are rope_k's / rope_kv8_k's: the
-// rotation is spelled as in rope_fwd_rotate and x + 0 = x (an input of -0 would come out as +0; a GEMM output is not -0).
-namespace {
-template <int HD>
-__device__ __forceinline__ void rope_bias_head(const bf16_t* p, const float* __restrict__ bias, int head, int j, bool rotate, int pos,
-                                               const float* __restrict__ cs, float (&oa)[8], float (&ob)[8]) {
-    constexpr int H2 = HD / 2;
-    float a[8], b[8], ba[8], bb[8];
-    load8(p, 8 * j, 0, a);
-    load8(p, H2 + 8 * j, 0, b);
-    load8(bias, (long)head * HD + 8 * j, 1, ba);
-    load8(bias, (long)head * HD + H2 + 8 * j, 1, bb);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { a[e] += ba[e]; b[e] += bb[e]; }
-    if (rotate) {
-        float c[8], s[8];
-        load8(cs, ((long)pos * 2) * H2 + 8 * j, 1, c);
-        load8(cs, ((long)pos * 2 + 1) * H2 + 8 * j, 1, s);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { oa[e] = fmaf(a[e], c[e], -(b[e] * s[e])); ob[e] = fmaf(b[e], c[e], a[e] * s[e]); }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { oa[e] = a[e]; ob[e] = b[e]; }
-    }
-}
-// n_heads = n_q + n_kv rotated heads, then n_kv V heads; kv.dst == nullptr: in place only (training / eval forward).
-template <int HD>
-__global__ __launch_bounds__(256) void rope_bias_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
-                                                   const float* __restrict__ cs, const float* __restrict__ bias,
-                                                   const int* __restrict__ pos_shift, RopeKV kv, int sm_batch) {
-    constexpr int G = HD / 16, H2 = HD / 2;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long grp = gid / G;
-    const int j = (int)(gid % G);
-    const int all_heads = 2 * n_heads - n_q;
-    if (grp >= (long)rows * all_heads) return;                           // no whole-wave op follows
-    const int row = (int)(grp / all_heads), head = (int)(grp % all_heads);
-    const int spos = sm_batch ? row / sm_batch : row % S, bidx = sm_batch ? row % sm_batch : row / S;
-    const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
-    bf16_t* p = buf + (long)row * ld + (long)head * HD;
-    float oa[8], ob[8];
-    rope_bias_head<HD>(p, bias, head, j, head < n_heads, pos, cs, oa, ob);
-    store8_bf16(p, 8 * j, oa); store8_bf16(p, H2 + 8 * j, ob);
-    if (kv.dst && head >= n_q) {                                         // cache rows are batch-major (the entry point passes sm_batch = 0)
-        bf16_t* d = kv.dst + (long)(row / S) * kv.bs + (long)(kv.slot0 + row % S) * kv.rs + (long)(head - n_q) * HD;
-        store8_bf16(d, 8 * j, oa); store8_bf16(d, H2 + 8 * j, ob);
-    }
-}
-// rope_kv8_k with the bias: the per-head power-of-two scale is taken from the bf16 values AFTER the bias (k: after the rotation).
-__global__ __launch_bounds__(256) void rope_kv8_bias_k(bf16_t* __restrict__ buf, long ld, int rows, int S, int n_heads, int n_q,
-                                                       const float* __restrict__ cs, const float* __restrict__ bias,
-                                                       const int* __restrict__ pos_shift, RopeKV8 kv) {
-    constexpr int HD = 128, G = HD / 16, H2 = HD / 2;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    const long grp = gid / G;
-    const int j = (int)(gid % G);
-    const int all_heads = n_heads + kv.n_v;
-    const bool active = grp < (long)rows * all_heads;                    // a head is 8 adjacent lanes: a group is active or not as a whole
-    const int row = active ? (int)(grp / all_heads) : 0, head = active ? (int)(grp % all_heads) : 0;
-    bf16_t* p = buf + (long)row * ld + (long)head * HD;
-    const int spos = row % S, bidx = row / S;
-    const int pos = pos_shift ? max(0, spos + pos_shift[bidx]) : spos;
-    float oa[8], ob[8];
-    rope_bias_head<HD>(p, bias, head, j, head < n_heads, pos, cs, oa, ob);
-    u16x8 ca, cb;                                                        // the bf16 bits a bf16 cache would hold
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { ca[e] = f2bf(oa[e]); cb[e] = f2bf(ob[e]); }
-    if (active) { *(u16x8*)(p + 8 * j) = ca; *(u16x8*)(p + H2 + 8 * j) = cb; }
-    unsigned amax = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) amax = max(amax, max((unsigned)(ca[e] & 0x7fff), (unsigned)(cb[e] & 0x7fff)));
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, o, 64));
-    if (!active || head < n_q) return;
-    const int ex = amax ? e4m3_row_exponent(amax) : 0;
-    const long b = row / S, slot = kv.slot0 + row % S;
-    uint8_t* d = kv.dst + b * kv.bs + slot * kv.rs + (long)(head - n_q) * HD;
-    unsigned w[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const u16x8& v = h ? cb : ca;
-        float f[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = ldexpf(bf2f(v[e]), -ex);
-        int lo = 0, hi = 0;
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-        w[2 * h] = (unsigned)lo; w[2 * h + 1] = (unsigned)hi;
-    }
-    *(uint2*)(d + 8 * j) = make_uint2(w[0], w[1]);
-    *(uint2*)(d + H2 + 8 * j) = make_uint2(w[2], w[3]);
-    if (j == 0) kv.scale[b * kv.sbs + slot * kv.srs + (head - n_q)] = pow2f(ex);
-}
-}  // namespace
-
-static int rope_bias_launch(const char* who, void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
-                            const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
-                            const int32_t* pos_shift, RopeKV kv, int sm_batch, void* stream) {
-    DESTA_CHECK_ARG(buf && cos_sin && qkv_bias, "%s: null argument", who);
-    DESTA_CHECK_ARG(!q_norm_w && !k_norm_w, "%s: a q|k|v bias together with q/k-norm weights is not supported", who);
-    DESTA_CHECK_ARG(head_dim == 64 || head_dim == 128, "%s: head_dim %d unsupported (64 or 128)", who, head_dim);
-    DESTA_CHECK_ARG(rows > 0 && seq > 0 && n_q_heads > 0 && n_kv_heads > 0, "%s: bad shape", who);
-    DESTA_CHECK_ARG(ld % 8 == 0 && ld >= (int64_t)(n_q_heads + 2 * n_kv_heads) * head_dim, "%s: ld %lld does not hold q|k|v", who, (long long)ld);
-    DESTA_CHECK_ARG((uintptr_t)buf % 16 == 0 && (uintptr_t)qkv_bias % 16 == 0 && (uintptr_t)cos_sin % 16 == 0, "%s: buffers must be 16-byte aligned", who);
-    const int nh = n_q_heads + n_kv_heads;
-    const long nthreads = (long)rows * (nh + n_kv_heads) * (head_dim / 16);
-    const dim3 grid((unsigned)((nthreads + 255) / 256));
-    hipStream_t st = (hipStream_t)stream;
-    if (head_dim == 128)
-        hipLaunchKernelGGL((rope_bias_k<128>), grid, dim3(256), 0, st, (bf16_t*)buf, (long)ld, rows, seq, nh, n_q_heads, cos_sin, qkv_bias, pos_shift, kv, sm_batch);
-    else
-        hipLaunchKernelGGL((rope_bias_k<64>), grid, dim3(256), 0, st, (bf16_t*)buf, (long)ld, rows, seq, nh, n_q_heads, cos_sin, qkv_bias, pos_shift, kv, sm_batch);
+#define ROPE_GO(HD, NORM, BWD, BIAS)                                                                                                         \
+    hipLaunchKernelGGL((rope_k<HD, NORM, BWD, BIAS>), grid, dim3(256), 0, (hipStream_t)c.stream, (bf16_t*)c.buf, (long)c.ld, c.rows, c.seq, nh, \
+                       c.n_q, c.cos_sin, c.wq, c.wk, c.eps, (const bf16_t*)c.pre, (long)c.ld_pre, c.pos_shift, kv, c.sm_batch, c.bias)
+#define ROPE_HD(NORM, BWD, BIAS) do { if (c.hd == 128) ROPE_GO(128, NORM, BWD, BIAS); else ROPE_GO(64, NORM, BWD, BIAS); } while (0)
+    if (c.has_bias) ROPE_HD(0, false, true);
+    else if (!c.backward) { if (c.wq) ROPE_HD(1, false, false); else ROPE_HD(0, false, false); }
+    else { if (c.wq) ROPE_HD(2, true, false); else ROPE_HD(0, true, false); }
+#undef ROPE_HD
+#undef ROPE_GO
     DESTA_CHECK_LAUNCH(who);
     return DESTA_OK;
 }
 
+static int rope_kv8_launch(const char* who, const RopeCall& c) {         // rope_kv8_k: into the FP8 cache
+    const RopeKV8 kv = {(uint8_t*)c.cache, c.scale, (long)c.kbs, (long)c.krs, (long)c.sbs, (long)c.srs, c.slot0, c.n_kv};
+    const int nh = c.n_q + c.n_kv;
+    const long nthreads = (long)c.rows * (nh + c.n_kv) * 8;
+    const dim3 grid((unsigned)((nthreads + 255) / 256));
+#define ROPE8_GO(NORM, BIAS)                                                                                                            \
+    hipLaunchKernelGGL((rope_kv8_k<NORM, BIAS>), grid, dim3(256), 0, (hipStream_t)c.stream, (bf16_t*)c.buf, (long)c.ld, c.rows, c.seq, nh, \
+                       c.n_q, c.cos_sin, c.wq, c.wk, c.eps, c.pos_shift, kv, c.bias)
+    if (c.has_bias) ROPE8_GO(0, true);
+    else if (c.wq) ROPE8_GO(1, false);
+    else ROPE8_GO(0, false);
+#undef ROPE8_GO
+    DESTA_CHECK_LAUNCH(who);
+    return DESTA_OK;
+}
+
+static int rope_run(const char* who, const RopeCall& c) {
+    const int rc = rope_check(who, c);
+    return rc != DESTA_OK ? rc : c.e4m3 ? rope_kv8_launch(who, c) : rope_launch(who, c);
+}
+
+// The six exports (include/desta_hip.h): each fills a RopeCall.  The _bias forms take qkv_bias where the plain ones take eps.
+#define ROPE_COMMON(EPS) {buf, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, EPS, pos_shift, stream}
+extern "C" int desta_rope(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                          const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
+                          const void* pre_norm, int64_t ld_pre, int backward, const int32_t* pos_shift, int s_major_batch,
+                          void* stream) {
+    RopeCall c = ROPE_COMMON(eps);
+    c.pre = pre_norm; c.ld_pre = ld_pre; c.backward = backward; c.sm_batch = s_major_batch;
+    return rope_run("rope", c);
+}
 extern "C" int desta_rope_bias(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                                const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
                                const int32_t* pos_shift, int s_major_batch, void* stream) {
-    DESTA_CHECK_ARG(s_major_batch >= 0 && (s_major_batch == 0 || rows % s_major_batch == 0), "rope_bias: rows must be a multiple of s_major_batch");
-    const RopeKV kv = {nullptr, 0, 0, 0, 0};
-    return rope_bias_launch("rope_bias", buf, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, qkv_bias, pos_shift, kv,
-                            s_major_batch, stream);
+    RopeCall c = ROPE_COMMON(0.f);
+    c.sm_batch = s_major_batch; c.has_bias = true; c.bias = qkv_bias;
+    return rope_run("rope_bias", c);
 }
-
-extern "C" int desta_rope_kv_append_bias(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+extern "C" int desta_rope_kv_append(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                                    const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
+                                    const int32_t* pos_shift, void* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                                    int slot0, void* stream) {
+    RopeCall c = ROPE_COMMON(eps);
+    c.has_cache = true; c.cache = kv_cache; c.kbs = kv_batch_stride; c.krs = kv_row_stride; c.slot0 = slot0;
+    return rope_run("rope_kv_append", c);
+}
+extern "C" int desta_rope_kv_append_bias(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                                          const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
                                          const int32_t* pos_shift, void* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
                                          int slot0, void* stream) {
-    DESTA_CHECK_ARG(kv_cache && kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0 && slot0 >= 0 && head_dim > 0 &&
-                    kv_row_stride >= 2L * n_kv_heads * head_dim && kv_batch_stride >= 0, "rope_kv_append_bias: bad cache argument");
-    DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0, "rope_kv_append_bias: buffers must be 16-byte aligned");
-    DESTA_CHECK_ARG(rows > 0 && seq > 0 && rows % seq == 0, "rope_kv_append_bias: rows must be a multiple of seq");
-    const RopeKV kv = {(bf16_t*)kv_cache, (long)kv_batch_stride, (long)kv_row_stride, slot0, n_kv_heads};
-    return rope_bias_launch("rope_kv_append_bias", qkv, ld, rows, seq, n_q_heads, n_kv_heads, head_dim, cos_sin, q_norm_w, k_norm_w, qkv_bias,
-                            pos_shift, kv, 0, stream);
+    RopeCall c = ROPE_COMMON(0.f);
+    c.has_cache = true; c.cache = kv_cache; c.kbs = kv_batch_stride; c.krs = kv_row_stride; c.slot0 = slot0;
+    c.has_bias = true; c.bias = qkv_bias;
+    return rope_run("rope_kv_append_bias", c);
 }
-
-extern "C" int desta_rope_kv_append_e4m3_bias(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+extern "C" int desta_rope_kv_append_e4m3(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
+                                         const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
+                                         const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
+                                         float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream) {
+    RopeCall c = ROPE_COMMON(eps);
+    c.has_cache = true; c.cache = kv_cache; c.kbs = kv_batch_stride; c.krs = kv_row_stride; c.slot0 = slot0;
+    c.e4m3 = true; c.scale = kv_scale; c.sbs = scale_batch_stride; c.srs = scale_row_stride;
+    return rope_run("rope_kv_append_e4m3", c);
+}
+extern "C" int desta_rope_kv_append_e4m3_bias(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                                               const float* cos_sin, const float* q_norm_w, const float* k_norm_w, const float* qkv_bias,
                                               const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
                                               float* kv_scale, int64_t scale_batch_stride, int64_t scale_row_stride, int slot0, void* stream) {
-    DESTA_CHECK_ARG(qkv && cos_sin && qkv_bias, "rope_kv_append_e4m3_bias: null argument");
-    DESTA_CHECK_ARG(!q_norm_w && !k_norm_w, "rope_kv_append_e4m3_bias: a q|k|v bias together with q/k-norm weights is not supported");
-    DESTA_CHECK_ARG(head_dim == 128, "rope_kv_append_e4m3_bias: head_dim %d unsupported (128)", head_dim);
-    DESTA_CHECK_ARG(rows > 0 && seq > 0 && rows % seq == 0 && n_q_heads > 0 && n_kv_heads > 0, "rope_kv_append_e4m3_bias: bad shape");
-    DESTA_CHECK_ARG(ld % 8 == 0 && ld >= (int64_t)(n_q_heads + 2 * n_kv_heads) * 128, "rope_kv_append_e4m3_bias: ld %lld does not hold q|k|v", (long long)ld);
-    DESTA_CHECK_ARG(kv_cache && kv_scale && kv_row_stride % 8 == 0 && kv_batch_stride % 8 == 0 && slot0 >= 0 &&
-                    kv_row_stride >= 2L * n_kv_heads * 128 && scale_row_stride >= 2L * n_kv_heads && scale_batch_stride >= 0 && kv_batch_stride >= 0,
-                    "rope_kv_append_e4m3_bias: bad cache argument");
-    DESTA_CHECK_ARG((uintptr_t)kv_cache % 16 == 0 && (uintptr_t)qkv % 16 == 0 && (uintptr_t)kv_scale % 4 == 0 && (uintptr_t)qkv_bias % 16 == 0 &&
-                    (uintptr_t)cos_sin % 16 == 0, "rope_kv_append_e4m3_bias: buffers must be 16-byte aligned");
-    const RopeKV8 kv = {kv_cache, kv_scale, (long)kv_batch_stride, (long)kv_row_stride, (long)scale_batch_stride, (long)scale_row_stride,
-                        slot0, n_kv_heads};
-    const int nh = n_q_heads + n_kv_heads;
-    const long nthreads = (long)rows * (nh + n_kv_heads) * 8;
-    hipLaunchKernelGGL(rope_kv8_bias_k, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, (long)ld, rows, seq,
-                       nh, n_q_heads, cos_sin, qkv_bias, pos_shift, kv);
-    DESTA_CHECK_LAUNCH("rope_kv_append_e4m3_bias");
-    return DESTA_OK;
+    RopeCall c = ROPE_COMMON(0.f);
+    c.has_cache = true; c.cache = kv_cache; c.kbs = kv_batch_stride; c.krs = kv_row_stride; c.slot0 = slot0;
+    c.e4m3 = true; c.scale = kv_scale; c.sbs = scale_batch_stride; c.srs = scale_row_stride;
+    c.has_bias = true; c.bias = qkv_bias;
+    return rope_run("rope_kv_append_e4m3_bias", c);
 }
+#undef ROPE_COMMON
 
 extern "C" int desta_swiglu_fwd(const void* gate_up, void* act, int64_t rows, int inter, void* stream) {
     DESTA_CHECK_ARG(gate_up && act && rows > 0 && inter % 8 == 0, "swiglu_fwd: bad argument");

@@ -468,19 +468,24 @@ def colsum(x, rows, cols, ld, out, accumulate=False, tag="ws"):
     check(_colsum(p(x), rows, cols, ld, p(out), int(accumulate), p(ws), stream()), "desta_colsum_bf16")
 
 
+def _rope_call(plain, biased, head, eps, bias, tail):
+    """The call of the three rotary wrappers.  head = (buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w), the
+    arguments every entry point starts with; then the one slot in which an entry point and its _bias twin differ: eps in the
+    plain form, qkv_bias in the bias form; then `tail`, to which the stream is appended."""
+    buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w = head
+    fn, slot = (plain, eps) if bias is None else (biased, p(bias))
+    check(fn(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), slot, *tail, stream()), fn.__name__)
+
+
 @_profiled("rope", lambda buf, ld, rows, seq, n_q, n_kv, hd, *a, **k: 4 * rows * (n_q + n_kv) * hd)      # q|k read + written in place
 def rope(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w=None, k_norm_w=None, eps=1e-6, pre_norm=None,
          ld_pre=0, backward=False, pos_shift=None, s_major_batch=0, bias=None):
     """bias (fp32 [(n_q + 2 n_kv) * hd], forward only): the q|k|v projection bias, added in front of the rotation; the V heads
     that follow K in `buf` get theirs too (include/desta_hip.h, desta_rope_bias).  The backward takes none."""
-    if bias is not None:
-        if backward:
-            raise ValueError("rope: the backward takes no bias (d(pre-bias) = d(post-bias))")
-        check(_rope_bias(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), p(bias), p(pos_shift), s_major_batch,
-                         stream()), "desta_rope_bias")
-        return
-    check(_rope(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pre_norm), ld_pre,
-                int(backward), p(pos_shift), s_major_batch, stream()), "desta_rope")
+    if bias is not None and backward:
+        raise ValueError("rope: the backward takes no bias (d(pre-bias) = d(post-bias))")
+    _rope_call(_rope, _rope_bias, (buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w), eps, bias,
+               (p(pos_shift), s_major_batch) if bias is not None else (p(pre_norm), ld_pre, int(backward), p(pos_shift), s_major_batch))
 
 
 @_profiled("swiglu_fwd", lambda gu, act, rows, inter: 6 * rows * inter)                    # gate|up read, act written (bf16)
@@ -806,12 +811,8 @@ _rope_kv_bias = _sig("desta_rope_kv_append_bias", vp, i64, i32, i32, i32, i32, i
 def rope_kv_append(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w, eps, pos_shift, cache, kv_bs, kv_rs, slot0, bias=None):
     """Forward rope on a fused q|k|v buffer + append of the rotated K and the V heads to the KV cache slab.  bias (fp32
     [(n_q + 2 n_kv) * hd]): the q|k|v projection bias, added in front of the rotation (v: bf16(v + b), in place and in the cache)."""
-    if bias is not None:
-        check(_rope_kv_bias(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), p(bias), p(pos_shift), p(cache), kv_bs,
-                            kv_rs, slot0, stream()), "desta_rope_kv_append_bias")
-        return
-    check(_rope_kv(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pos_shift), p(cache), kv_bs,
-                   kv_rs, slot0, stream()), "desta_rope_kv_append")
+    _rope_call(_rope_kv, _rope_kv_bias, (buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w), eps, bias,
+               (p(pos_shift), p(cache), kv_bs, kv_rs, slot0))
 
 
 _rope_kv8 = _sig("desta_rope_kv_append_e4m3", vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, f32, vp, vp, i64, i64, vp, i64, i64, i32, vp)
@@ -824,12 +825,8 @@ def rope_kv_append_e4m3(buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_
                         scale, scale_bs, scale_rs, slot0, bias=None):
     """rope_kv_append into the FP8 cache: e4m3 bytes to `cache` (strides in bytes), one fp32 scale per head to `scale`.  bias: as
     in rope_kv_append; the scales are taken after it."""
-    if bias is not None:
-        check(_rope_kv8_bias(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), p(bias), p(pos_shift), p(cache), kv_bs,
-                             kv_rs, p(scale), scale_bs, scale_rs, slot0, stream()), "desta_rope_kv_append_e4m3_bias")
-        return
-    check(_rope_kv8(p(buf), ld, rows, seq, n_q, n_kv, hd, p(cos_sin), p(q_norm_w), p(k_norm_w), eps, p(pos_shift), p(cache), kv_bs,
-                    kv_rs, p(scale), scale_bs, scale_rs, slot0, stream()), "desta_rope_kv_append_e4m3")
+    _rope_call(_rope_kv8, _rope_kv8_bias, (buf, ld, rows, seq, n_q, n_kv, hd, cos_sin, q_norm_w, k_norm_w), eps, bias,
+               (p(pos_shift), p(cache), kv_bs, kv_rs, p(scale), scale_bs, scale_rs, slot0))
 
 
 _sample = _sig("desta_sample_top_p_bf16", vp, i64, i32, i32, f32, f32, C.c_uint64, C.c_uint32, vp, vp, vp)

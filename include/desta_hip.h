@@ -336,7 +336,12 @@ int desta_colsum_bf16(const void* x, int rows, int cols, int64_t ld, float* out,
  * pos_shift (int32 [rows/seq] or NULL): position = max(0, row % seq + pos_shift[row / seq]) — generate() derives
  * position_ids from the attention mask (prompt: -left_pad; decode step: cache_len - left_pad).
  * s_major_batch > 0: the token grid is stored position-major (row = s * s_major_batch + b) instead of batch-major
- * (row = b * seq + s) — the training layout, in which "all positions >= s0" is one contiguous row range. */
+ * (row = b * seq + s) — the training layout, in which "all positions >= s0" is one contiguous row range.
+ * The six rotary entry points (this one, desta_rope_kv_append, desta_rope_kv_append_e4m3 and their _bias forms) share one
+ * argument check; a call that fails it returns DESTA_EINVAL and launches nothing.  All six: buf and cos_sin 16-byte aligned
+ * (desta_rope checked neither before: an unaligned buf or cos_sin is newly rejected), ld a multiple of 8, q_norm_w and
+ * k_norm_w both or neither (desta_rope took a lone k_norm_w and ignored it: newly rejected).  ld need not hold the V heads
+ * here, which this form never touches. */
 int desta_rope(void* buf, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
                const void* pre_norm, int64_t ld_pre, int backward, const int32_t* pos_shift, int s_major_batch, void* stream);
@@ -651,7 +656,12 @@ int desta_sample_bf16(const void* logits, int64_t ld, int rows, int cols, const 
 /* desta_rope (forward) on a fused q|k|v projection [rows, ld] that ALSO appends the rotated K heads and the V heads of
  * row (b, s) to a KV cache slab: kv_cache + b*kv_batch_stride + (slot0 + s)*kv_row_stride, K heads then V heads.
  * This is what `DynamicCache.update` does inside `llm_model.generate` (modeling_desta25.py:1419) for the prompt
- * (seq = prompt length, slot0 = 0) and for every decode step (seq = 1, slot0 = cache length). */
+ * (seq = prompt length, slot0 = 0) and for every decode step (seq = 1, slot0 = cache length).
+ * The kernel reads the V heads out of `qkv` and writes kv_row_stride-spaced slots of batch rows / seq, so this form is held to
+ * what its _bias twin is held to; newly rejected (DESTA_EINVAL, nothing launched) are: rows not a multiple of seq (the last
+ * sequence's slots would lie behind the cache); an ld below (n_q_heads + 2 n_kv_heads) * head_dim (the V heads would be read
+ * out of the next row); n_q_heads or n_kv_heads <= 0; a kv_row_stride below 2 n_kv_heads * head_dim (slots would overlap) or a
+ * negative kv_batch_stride; an unaligned cos_sin; a lone k_norm_w. */
 int desta_rope_kv_append(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                          const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
                          const int32_t* pos_shift, void* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,
@@ -662,7 +672,10 @@ int desta_rope_kv_append(void* qkv, int64_t ld, int rows, int seq, int n_q_heads
  * and written as bytes to kv_cache + b*kv_batch_stride + (slot0 + s)*kv_row_stride and as scales to
  * kv_scale + b*scale_batch_stride + (slot0 + s)*scale_row_stride, K heads then V heads.  One launch; head_dim 128 only.
  * `DynamicCache.update` of a quantised cache inside `llm_model.generate` (modeling_desta25.py:1419), prompt (seq = prompt
- * length, slot0 = 0) and decode step (seq = 1, slot0 = cache length). */
+ * length, slot0 = 0) and decode step (seq = 1, slot0 = cache length).
+ * Held to what its _bias twin is held to; newly rejected (DESTA_EINVAL, nothing launched) are: an ld below
+ * (n_q_heads + 2 n_kv_heads) * head_dim (the V heads would be read out of the next row); a negative kv_batch_stride; an
+ * unaligned cos_sin. */
 int desta_rope_kv_append_e4m3(void* qkv, int64_t ld, int rows, int seq, int n_q_heads, int n_kv_heads, int head_dim,
                               const float* cos_sin, const float* q_norm_w, const float* k_norm_w, float eps,
                               const int32_t* pos_shift, uint8_t* kv_cache, int64_t kv_batch_stride, int64_t kv_row_stride,

@@ -217,3 +217,43 @@ def test_bad_arguments_return_einval_and_launch_nothing(hip):
     torch.cuda.synchronize()
     assert torch.equal(buf.cpu().view(torch.int16), qkv.view(torch.int16))   # nothing was launched
     assert bool((c16 == -3.0).all()) and bool((c8 == 0xAB).all()) and bool((sc == -7.0).all())
+
+
+def test_bias_free_cache_forms_reject_what_their_twins_reject(hip):
+    """The six entry points share one argument check: rope_kv_append and rope_kv_append_e4m3 read the V heads out of `buf` and write
+    kv_row_stride-spaced slots with or without a bias, so without one they return DESTA_EINVAL for the same calls."""
+    Hq, Hkv, hd, B, S, slot0 = 2, 2, 128, 3, 5, 3
+    Smax = S + 6
+    ld, qkv, _, shift, cs = _inputs(Hq, Hkv, hd, B, S)
+    buf, shift = qkv.cuda(), shift.cuda()
+    cs_pad = torch.zeros(cs.numel() + 4, device="cuda")
+    cs_pad[1:-3] = cs.reshape(-1)
+    cs_off = cs_pad[1:-3]                                                    # the table one float into an aligned allocation
+    cs = cs.cuda()
+    _, c16, c8, sc = _caches(B, Smax, Hkv, hd)
+    st = (c16.stride(0), c16.stride(1))
+    s8 = (sc, sc.stride(0), sc.stride(1))
+    M = B * S
+
+    def bf16(ld=ld, seq=S, cs=cs, rs=st[1], slot0=slot0):
+        hip.rope_kv_append(buf, ld, M, seq, Hq, Hkv, hd, cs, None, None, 1e-6, shift, c16, st[0], rs, slot0)
+
+    def e4m3(ld=ld, seq=S, cs=cs, rs=st[1], slot0=slot0):
+        hip.rope_kv_append_e4m3(buf, ld, M, seq, Hq, Hkv, hd, cs, None, None, 1e-6, shift, c8, st[0], rs, *s8, slot0)
+
+    bad = [("multiple of seq", dict(seq=4)), ("ld", dict(ld=(Hq + Hkv) * hd)), ("cache", dict(rs=Hkv * hd)), ("cache", dict(slot0=-1)),
+           ("aligned", dict(cs=cs_off))]
+    for form in (bf16, e4m3):
+        for name, kw in bad:
+            with pytest.raises(RuntimeError, match=name) as ei:
+                form(**kw)
+            assert "(-1)" in str(ei.value), (form.__name__, name)            # DESTA_EINVAL
+    torch.cuda.synchronize()
+    assert torch.equal(buf.cpu().view(torch.int16), qkv.view(torch.int16))   # nothing was launched
+    assert bool((c16 == -3.0).all()) and bool((c8 == 0xAB).all()) and bool((sc == -7.0).all())
+    bf16()
+    buf.copy_(qkv)
+    e4m3()
+    torch.cuda.synchronize()
+    assert not bool((c16[:, slot0:slot0 + S] == -3.0).all()) and not bool((c8[:, slot0:slot0 + S] == 0xAB).all())
+    assert not bool((sc[:, slot0:slot0 + S] == -7.0).all())

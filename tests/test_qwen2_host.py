@@ -107,11 +107,13 @@ def test_binding_declares_the_bias_forms_and_rejects_a_bias_in_the_backward():
 def test_new_rotary_kernels_use_no_scratch():
     import importlib.util
     import os
+    import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(root, "tools", "kernel_resources.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    res = {n: r for n, r in mod.kernel_resources().items() if "rope_bias_k" in n or "rope_kv8_bias_k" in n}
+    # the BIAS = true instantiations of rope_k<HD, NORM, BWD, BIAS> and rope_kv8_k<NORM, BIAS> (the last template argument, "Lb1E")
+    res = {n: r for n, r in mod.kernel_resources().items() if re.search(r"\d(rope_k|rope_kv8_k)I(Li\d+E)+(Lb[01]E)*Lb1EE", n)}
     assert len(res) == 3, sorted(res)                                                          # head_dim 64 and 128, and the e4m3 form
     for n, r in res.items():
         assert r["scratch"] == 0 and r["spill"] == 0, (n, r)
