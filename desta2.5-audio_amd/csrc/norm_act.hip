@@ -689,7 +689,7 @@ __device__ __forceinline__ float block_sum_1024(float v, float* red) {
     return t;
 }
 __global__ __launch_bounds__(1024) void sample_top_p_k(const bf16_t* __restrict__ x, long ld, int cols, float inv_temp, float top_p,
-                                                       unsigned seed_lo, unsigned seed_hi, unsigned step, long* __restrict__ out,
+                                                       unsigned seed_lo, unsigned seed_hi, unsigned step, int width, long* __restrict__ out,
                                                        unsigned char* __restrict__ keep_mask) {
     __shared__ float red[16];
     __shared__ float part[1024];
@@ -738,8 +738,12 @@ __global__ __launch_bounds__(1024) void sample_top_p_k(const bf16_t* __restrict_
     if (tid == 0) {                                                // 1024-entry serial scan by one lane: ~2 us, fixed order
         float tot = 0.f;
         for (int i = 0; i < 1024; ++i) tot += part[i];
-        const unsigned r = desta_rng32(seed_lo, seed_hi, ((unsigned long)step << 32) | blockIdx.x);
-        const float target = (float)(r >> 8) * (1.0f / 16777216.0f) * tot;
+        // row r = blockIdx.x is row j = r % width of sequence b = r / width (width 1, the one-row entry point: b = r, j = 0): the
+        // draw of emitted position step + j (a uint32 sum: it wraps) of sequence b, so the counter row is b, not r.  One lane
+        // divides, once; a (batch, width) grid without the division cost the row loops above 2.4 % (MI355X, 8 and 64 rows)
+        const unsigned b = blockIdx.x / (unsigned)width, j = blockIdx.x - b * (unsigned)width;
+        const unsigned u = desta_rng32(seed_lo, seed_hi, ((unsigned long)(step + j) << 32) | b);
+        const float target = (float)(u >> 8) * (1.0f / 16777216.0f) * tot;
         float run = 0.f;
         int t = 0;
         for (; t < 1023; ++t) {
@@ -1142,12 +1146,23 @@ extern "C" int desta_argmax_bf16(const void* x, int64_t ld, int rows, int cols, 
     return DESTA_OK;
 }
 
-extern "C" int desta_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int cols, float temperature, float top_p,
-                                       uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream) {
-    DESTA_CHECK_ARG(logits && out && rows > 0 && cols > 0, "sample_top_p: bad argument");
+static int sample_top_p_launch(const void* logits, int64_t ld, int batch, int width, int cols, float temperature, float top_p, uint64_t seed,
+                               uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream) {
+    DESTA_CHECK_ARG(logits && out && batch > 0 && cols > 0, "sample_top_p: bad argument");
+    DESTA_CHECK_ARG(width >= 1 && width <= 8, "sample_top_p: width %d out of range (1..8)", width);
     DESTA_CHECK_ARG(temperature > 0.f && top_p > 0.f && top_p <= 1.f, "sample_top_p: need temperature > 0 and 0 < top_p <= 1");
-    hipLaunchKernelGGL(sample_top_p_k, dim3(rows), dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
-                       1.0f / temperature, top_p, (unsigned)seed, (unsigned)(seed >> 32), step, (long*)out, keep_mask);
+    hipLaunchKernelGGL(sample_top_p_k, dim3(batch * width), dim3(1024), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
+                       1.0f / temperature, top_p, (unsigned)seed, (unsigned)(seed >> 32), step0, width, (long*)out, keep_mask);
     DESTA_CHECK_LAUNCH("sample_top_p");
     return DESTA_OK;
+}
+
+extern "C" int desta_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int cols, float temperature, float top_p,
+                                       uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream) {
+    return sample_top_p_launch(logits, ld, rows, 1, cols, temperature, top_p, seed, step, out, keep_mask, stream);
+}
+
+extern "C" int desta_sample_top_p_rows_bf16(const void* logits, int64_t ld, int batch, int width, int cols, float temperature, float top_p,
+                                            uint64_t seed, uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream) {
+    return sample_top_p_launch(logits, ld, batch, width, cols, temperature, top_p, seed, step0, out, keep_mask, stream);
 }

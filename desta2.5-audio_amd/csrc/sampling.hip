@@ -21,6 +21,7 @@ constexpr int SNT = 1024;                      // threads per row
 constexpr int SBINS = 4096;                    // bins of the first radix digit (key bits 31..20); later digits use 1024
 constexpr int PEN_MAX_COLS = 262144;           // LDS bitmap of penalised tokens: 32 KiB
 constexpr float MASS_ONE = 1099511627776.0f;   // 2^40: fixed-point scale of exp(t - t_max) <= 1
+constexpr int SAMPLE_ROWS_MAX_WIDTH = 8;       // rows per sequence of a grouped launch: a verify step's k + 1 <= SPEC_K_MAX + 1
 
 // monotone map of fp32 order onto u32; -0 maps onto +0 (they compare equal in torch)
 __device__ __forceinline__ unsigned f32_key(float v) {
@@ -101,14 +102,27 @@ __device__ __forceinline__ void select_bin(const u64* bins, u64* wred, u64* sel,
     __syncthreads();
 }
 
-// LDS bitmap of the distinct history tokens of row r (RepetitionPenaltyLogitsProcessor gathers from the original scores, so a
-// token that occurs several times is penalised once)
-__device__ __forceinline__ void build_penalty_bits(unsigned* pen_bits, int cols, const long* __restrict__ hist, long hist_ld, int hist_len) {
+// The grid is (batch, width): block (b, j) works on row r = b * width + j of the logits, row j of sequence b
+// (desta_sample_rows_bf16; width 1, the one-row entry point: r = b, j = 0): emitted position step + j of sequence b, whose history
+// is hist[b] followed by the j tokens tail[b][1 .. 1 + j)
+struct GroupRow {
+    int b, j, r;
+};
+__device__ __forceinline__ GroupRow group_row(int width) { return {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.x * width + (int)blockIdx.y}; }
+
+// LDS bitmap of the distinct history tokens of sequence g.b in front of its row g.j (RepetitionPenaltyLogitsProcessor gathers
+// from the original scores, so a token that occurs several times is penalised once)
+__device__ __forceinline__ void build_penalty_bits(unsigned* pen_bits, int cols, GroupRow g, const long* __restrict__ hist, long hist_ld,
+                                                   int hist_len, const long* __restrict__ tail, long tail_ld) {
     for (int i = threadIdx.x; i < (cols + 31) >> 5; i += SNT) pen_bits[i] = 0u;
     __syncthreads();
-    const long* h = hist + (long)blockIdx.x * hist_ld;
+    const long* h = hist + (long)g.b * hist_ld;
     for (int i = threadIdx.x; i < hist_len; i += SNT) {
         const long id = h[i];
+        if (id >= 0 && id < cols) atomicOr(&pen_bits[id >> 5], 1u << (id & 31));
+    }
+    if ((int)threadIdx.x < g.j) {                                            // g.j > 0 only with a tail (checked on the host)
+        const long id = tail[(long)g.b * tail_ld + 1 + threadIdx.x];
         if (id >= 0 && id < cols) atomicOr(&pen_bits[id >> 5], 1u << (id & 31));
     }
     __syncthreads();
@@ -122,14 +136,15 @@ __device__ __forceinline__ float penalised(const unsigned* pen_bits, bool pen, f
 
 // greedy (do_sample = 0): first index of the maximum penalised score, as torch.argmax
 __global__ __launch_bounds__(SNT) void sample_greedy_k(const bf16_t* __restrict__ x, long ld, int cols, const long* __restrict__ hist,
-                                                       long hist_ld, int hist_len, float penalty, long* __restrict__ out,
-                                                       unsigned char* __restrict__ keep_mask) {
+                                                       long hist_ld, int hist_len, const long* __restrict__ tail, long tail_ld, int width,
+                                                       float penalty, long* __restrict__ out, unsigned char* __restrict__ keep_mask) {
     __shared__ unsigned pen_bits[PEN_MAX_COLS / 32];
     __shared__ u64 wred[SNT / 64];
-    const int tid = threadIdx.x, r = blockIdx.x;
+    const GroupRow g = group_row(width);
+    const int tid = threadIdx.x, r = g.r;
     const bf16_t* row = x + (long)r * ld;
-    const bool pen = penalty != 1.0f && hist_len > 0;
-    if (pen) build_penalty_bits(pen_bits, cols, hist, hist_ld, hist_len);
+    const bool pen = penalty != 1.0f && hist_len + g.j > 0;
+    if (pen) build_penalty_bits(pen_bits, cols, g, hist, hist_ld, hist_len, tail, tail_ld);
     u64 best = 0;
     row_strided(row, cols, ((uintptr_t)row & 15) == 0, [&](int c, bf16_t b) {
         const u64 k = ((u64)f32_key(penalised(pen_bits, pen, penalty, c, b)) << 32) | (unsigned)(~(unsigned)c);
@@ -152,18 +167,20 @@ __global__ __launch_bounds__(SNT) void sample_greedy_k(const bf16_t* __restrict_
 }
 
 __global__ __launch_bounds__(SNT) void sample_chain_k(const bf16_t* __restrict__ x, long ld, int cols, const long* __restrict__ hist,
-                                                      long hist_ld, int hist_len, float penalty, float temp, int top_k, float top_p,
-                                                      float min_p, unsigned seed_lo, unsigned seed_hi, unsigned step,
-                                                      long* __restrict__ out, unsigned char* __restrict__ keep_mask) {
+                                                      long hist_ld, int hist_len, const long* __restrict__ tail, long tail_ld, int width,
+                                                      float penalty, float temp, int top_k, float top_p, float min_p, unsigned seed_lo,
+                                                      unsigned seed_hi, unsigned step, long* __restrict__ out,
+                                                      unsigned char* __restrict__ keep_mask) {
     __shared__ u64 bins[SBINS];
     __shared__ unsigned pen_bits[PEN_MAX_COLS / 32];
     __shared__ u64 wred[SNT / 64];
     __shared__ u64 sel[2];
-    const int tid = threadIdx.x, r = blockIdx.x;
+    const GroupRow g = group_row(width);
+    const int tid = threadIdx.x, r = g.r;
     const bf16_t* row = x + (long)r * ld;
     const bool vec = ((uintptr_t)row & 15) == 0;
-    const bool pen = penalty != 1.0f && hist_len > 0;
-    if (pen) build_penalty_bits(pen_bits, cols, hist, hist_ld, hist_len);
+    const bool pen = penalty != 1.0f && hist_len + g.j > 0;
+    if (pen) build_penalty_bits(pen_bits, cols, g, hist, hist_ld, hist_len, tail, tail_ld);
     auto score = [&](int c, bf16_t b) -> float { return penalised(pen_bits, pen, penalty, c, b); };
 
     auto tval = [&](int c, bf16_t b) -> float { return score(c, b) / temp; };   // TemperatureLogitsWarper: an fp32 division
@@ -275,7 +292,7 @@ __global__ __launch_bounds__(SNT) void sample_chain_k(const bf16_t* __restrict__
     __syncthreads();
     u64 target = 0;
     select_bin<1>(bins, wred, sel, [&](u64 total) {
-        const unsigned u = desta_rng32(seed_lo, seed_hi, ((unsigned long)step << 32) | (unsigned)r);
+        const unsigned u = desta_rng32(seed_lo, seed_hi, ((unsigned long)(step + (unsigned)g.j) << 32) | (unsigned)g.b);   // uint32 sum: wraps
         target = (u64)((double)(u >> 8) * (1.0 / 16777216.0) * (double)total);   // < total
         if (total == 0) sel[0] = 0, sel[1] = 0;                                   // no finite score: token 0 (below)
         return target;
@@ -296,27 +313,47 @@ __global__ __launch_bounds__(SNT) void sample_chain_k(const bf16_t* __restrict__
     }
 }
 
-}  // namespace
-
-extern "C" int desta_sample_bf16(const void* logits, int64_t ld, int rows, int cols, const int64_t* hist, int64_t hist_ld, int hist_len,
-                                 float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
-                                 uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream) {
-    DESTA_CHECK_ARG(logits && out && rows > 0 && cols > 0 && ld >= cols, "sample: bad argument");
+// the checks and the launch of both entry points: `batch` sequences of `width` rows each
+int sample_launch(const void* logits, int64_t ld, int batch, int width, int cols, const int64_t* hist, int64_t hist_ld, int hist_len,
+                  const int64_t* tail, int64_t tail_ld, float repetition_penalty, int do_sample, float temperature, int top_k, float top_p,
+                  float min_p, uint64_t seed, uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream) {
+    DESTA_CHECK_ARG(logits && out && batch > 0 && cols > 0 && ld >= cols, "sample: bad argument");
+    DESTA_CHECK_ARG(width >= 1 && width <= SAMPLE_ROWS_MAX_WIDTH, "sample: width %d out of range (1..%d)", width, SAMPLE_ROWS_MAX_WIDTH);
     DESTA_CHECK_ARG(temperature > 0.f, "sample: need temperature > 0");
     DESTA_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "sample: need 0 < top_p <= 1");
     DESTA_CHECK_ARG(top_k >= 0, "sample: need top_k >= 0");
     DESTA_CHECK_ARG(min_p >= 0.f && min_p <= 1.f, "sample: need 0 <= min_p <= 1");
     DESTA_CHECK_ARG(repetition_penalty > 0.f, "sample: need repetition_penalty > 0");
     DESTA_CHECK_ARG(hist_len >= 0 && (hist_len == 0 || (hist && hist_ld >= hist_len)), "sample: bad token history");
-    DESTA_CHECK_ARG(repetition_penalty == 1.f || hist_len == 0 || cols <= PEN_MAX_COLS,
+    DESTA_CHECK_ARG(width == 1 || repetition_penalty == 1.f || (tail && tail_ld >= width),
+                    "sample: a repetition penalty over %d rows per sequence needs the tail tokens", width);
+    DESTA_CHECK_ARG(repetition_penalty == 1.f || (hist_len == 0 && width == 1) || cols <= PEN_MAX_COLS,
                     "sample: a repetition penalty needs cols <= %d", PEN_MAX_COLS);
     if (!do_sample)
-        hipLaunchKernelGGL(sample_greedy_k, dim3(rows), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
-                           (const long*)hist, (long)hist_ld, hist_len, repetition_penalty, (long*)out, keep_mask);
+        hipLaunchKernelGGL(sample_greedy_k, dim3(batch, width), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
+                           (const long*)hist, (long)hist_ld, hist_len, (const long*)tail, (long)tail_ld, width, repetition_penalty,
+                           (long*)out, keep_mask);
     else
-        hipLaunchKernelGGL(sample_chain_k, dim3(rows), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
-                           (const long*)hist, (long)hist_ld, hist_len, repetition_penalty, temperature, top_k, top_p, min_p,
-                           (unsigned)seed, (unsigned)(seed >> 32), step, (long*)out, keep_mask);
+        hipLaunchKernelGGL(sample_chain_k, dim3(batch, width), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
+                           (const long*)hist, (long)hist_ld, hist_len, (const long*)tail, (long)tail_ld, width, repetition_penalty,
+                           temperature, top_k, top_p, min_p, (unsigned)seed, (unsigned)(seed >> 32), step0, (long*)out, keep_mask);
     DESTA_CHECK_LAUNCH("sample");
     return DESTA_OK;
+}
+
+}  // namespace
+
+extern "C" int desta_sample_bf16(const void* logits, int64_t ld, int rows, int cols, const int64_t* hist, int64_t hist_ld, int hist_len,
+                                 float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
+                                 uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream) {
+    return sample_launch(logits, ld, rows, 1, cols, hist, hist_ld, hist_len, nullptr, 0, repetition_penalty, do_sample, temperature, top_k,
+                         top_p, min_p, seed, step, out, keep_mask, stream);
+}
+
+extern "C" int desta_sample_rows_bf16(const void* logits, int64_t ld, int batch, int width, int cols, const int64_t* hist, int64_t hist_ld,
+                                      int hist_len, const int64_t* tail, int64_t tail_ld, float repetition_penalty, int do_sample,
+                                      float temperature, int top_k, float top_p, float min_p, uint64_t seed, uint32_t step0, int64_t* out,
+                                      uint8_t* keep_mask, void* stream) {
+    return sample_launch(logits, ld, batch, width, cols, hist, hist_ld, hist_len, tail, tail_ld, repetition_penalty, do_sample, temperature,
+                         top_k, top_p, min_p, seed, step0, out, keep_mask, stream);
 }

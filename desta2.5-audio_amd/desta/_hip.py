@@ -852,6 +852,36 @@ def sample(logits, ld, rows, cols, out, *, do_sample=True, temperature=1.0, top_
           "desta_sample_bf16")
 
 
+_sample_top_p_rows = _sig("desta_sample_top_p_rows_bf16", vp, i64, i32, i32, i32, f32, f32, C.c_uint64, C.c_uint32, vp, vp, vp)
+_sample_rows = _sig("desta_sample_rows_bf16", vp, i64, i32, i32, i32, vp, i64, i32, vp, i64, f32, i32, f32, i32, f32, f32, C.c_uint64,
+                    C.c_uint32, vp, vp, vp)
+SAMPLE_ROWS_CALLS = 0              # grouped chain / penalty sampler launches issued by this process
+SAMPLE_TOP_P_ROWS_CALLS = 0        # grouped top-p sampler launches issued by this process
+
+
+def sample_top_p_rows(logits, ld, batch, width, cols, temperature, top_p, seed, step0, out, keep_mask=None):
+    """`sample_top_p` over the batch * width rows (batch-major) of a verify step: row (b, j) is row b of a batch-row call at step
+    step0 + j (desta_sample_top_p_rows_bf16)."""
+    global SAMPLE_TOP_P_ROWS_CALLS
+    check(_sample_top_p_rows(p(logits), ld, batch, width, cols, temperature, top_p, seed & 0xFFFFFFFFFFFFFFFF, step0 & 0xFFFFFFFF, p(out),
+                             p(keep_mask), stream()), "desta_sample_top_p_rows_bf16")
+    SAMPLE_TOP_P_ROWS_CALLS += 1
+
+
+def sample_rows(logits, ld, batch, width, cols, out, *, do_sample=True, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0,
+                repetition_penalty=1.0, hist=None, hist_len=0, tail=None, seed=0, step0=0, keep_mask=None):
+    """`sample` over the batch * width rows (batch-major) of a verify step: row (b, j) is row b of a batch-row call at step
+    step0 + j whose history is hist[b, :hist_len] followed by tail[b, 1:1 + j] (tail int64 [batch, >= width]: the verify step's
+    input, last emitted token then the drafts) (desta_sample_rows_bf16)."""
+    global SAMPLE_ROWS_CALLS
+    assert hist is None or (hist.dtype == torch.int64 and hist.stride(1) == 1)
+    assert tail is None or (tail.dtype == torch.int64 and tail.stride(1) == 1 and tail.shape[0] >= batch and tail.shape[1] >= width)
+    check(_sample_rows(p(logits), ld, batch, width, cols, p(hist), 0 if hist is None else hist.stride(0), hist_len, p(tail),
+                       0 if tail is None else tail.stride(0), repetition_penalty, int(bool(do_sample)), temperature, top_k, top_p, min_p,
+                       seed & 0xFFFFFFFFFFFFFFFF, step0 & 0xFFFFFFFF, p(out), p(keep_mask), stream()), "desta_sample_rows_bf16")
+    SAMPLE_ROWS_CALLS += 1
+
+
 _spec_draft = _sig("desta_spec_ngram_draft", vp, i64, i32, i32, vp, i32, i32, i32, vp, vp)
 _spec_accept = _sig("desta_spec_accept", vp, vp, i32, i32, vp, vp, i32, i64, i32, vp, i64, i32, vp, vp, vp, i64, i32, vp)
 SPEC_DRAFT_CALLS = 0               # prompt-lookup launches issued by this process

@@ -476,6 +476,15 @@ def check_speculative_arg(k) -> None:
         raise ValueError(f"speculative must be None, 0 or an int in 1..{SPECULATIVE_MAX} draft tokens per step, got {k!r}")
 
 
+SPECULATIVE_SCOPES = ("greedy", "all")              # which generate() calls `set_speculative` covers
+
+
+def check_speculative_scope(scope) -> None:
+    """`set_speculative(k, scope=...)`: "greedy" (plain greedy calls only) or "all" (sampling, repetition penalty, logprobs too)."""
+    if not isinstance(scope, str) or scope not in SPECULATIVE_SCOPES:
+        raise ValueError(f"speculative scope must be one of {SPECULATIVE_SCOPES}, got {scope!r}")
+
+
 def prefill_chunks(S: int, C: int) -> List[Tuple[int, int]]:
     """Position ranges [c0, c1) of the chunked prompt pass: [0, S) in order, C positions each, a ragged last one."""
     return [(c0, min(c0 + C, S)) for c0 in range(0, S, C)]
@@ -1596,22 +1605,31 @@ class CausalLMHIP:
         self.prefill_chunk = None                   # `set_prefill_chunk`: positions per chunk of generate()'s lean prompt pass; None = `forward`
         self.kv_stage = self._pf = None
         self.speculative = None                     # `set_speculative`: draft tokens per verify step of greedy generate(); None = one token per step
+        self.spec_scope = "greedy"                  # `set_speculative(k, scope=...)`: "greedy" = plain greedy calls only, "all" = sampling, penalty and logprobs too
         self._step1 = self._spec = None             # `_step_alloc` sets of the plain step (`_gen_alloc`) and of the verify step (`_spec_alloc`)
         self.spec_stats = None
 
-    def set_speculative(self, k: Optional[int]) -> None:
-        """Greedy generate(): None or 0 (default) = one token per sequence per pass over the weights; an int k in 1..7 = draft and
+    def set_speculative(self, k: Optional[int], scope: str = "greedy") -> None:
+        """generate(): None or 0 (default) = one token per sequence per pass over the weights; an int k in 1..7 = draft and
         verify: k tokens proposed by looking the row's last tokens up in its own prompt and output (`H.spec_ngram_draft`), all k + 1
         rows per sequence checked by ONE pass (`verify_step`: the step body of `decode_step`, `_step_rows`, at width k + 1), and
         the longest run every unfinished row agrees on is emitted (`H.spec_accept`; acceptance is in lockstep, so the cache keeps
-        one length).  The tokens are those of the plain loop up to the rounding of a different row count.  Sampling, a repetition
-        penalty, `logprobs`, `forced_tokens`, a `layer_hook` (ORCA), the FP8 KV cache and B * (k + 1) > H.DECODE_MAX_ROWS run the
-        plain loop; `spec_stats` says which ran and why."""
+        one length).  The tokens are those of the plain loop up to the rounding of a different row count.
+        scope = "greedy" (default): only plain greedy calls speculate; sampling, a repetition penalty and `logprobs` run the plain
+        loop.  scope = "all": those three speculate too.  Row j of a sequence is picked by the sampler the plain loop would launch
+        for emitted position n + j, with that position's RNG counter and token history (`H.sample_rows`, `H.sample_top_p_rows`), so
+        the token is the sampler's own draw from the logits of the accepted prefix and a draft is accepted exactly when the draw
+        hits it: the plain loop's sampled tokens, with no rejection-resampling rule.  `logprobs` costs one `H.topk_logprobs` launch
+        over all rows per verify step.
+        Under both scopes `forced_tokens`, a `layer_hook` (ORCA), the FP8 KV cache and B * (k + 1) > H.DECODE_MAX_ROWS run the plain
+        loop; `spec_stats` says which ran and why."""
         check_speculative_arg(k)
+        check_speculative_scope(scope)
         k = k or None
-        if k != self.speculative:                                            # the verify buffers go with the setting
+        if k != self.speculative:                                            # the verify buffers go with k, not with the scope
             self._spec = None
         self.speculative = k
+        self.spec_scope = scope
 
     def set_prefill_chunk(self, n: Optional[int]) -> None:
         """Prompt pass of generate(): None (default) = the training `forward` with its per-layer save set; an int >= 16 = the
@@ -2158,13 +2176,15 @@ class CausalLMHIP:
         return self._step_rows(tokens, cur, kv_start)
 
     def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook) -> Optional[str]:
-        """Why a call with speculation on runs the plain loop all the same; None when it does not."""
-        if do_sample:
-            return "do_sample"
-        if use_pen:
-            return "repetition_penalty"
-        if logprobs is not None:
-            return "logprobs"
+        """Why a call with speculation on runs the plain loop all the same; None when it does not.  The first three hold under
+        scope "greedy" only."""
+        if getattr(self, "spec_scope", "greedy") != "all":
+            if do_sample:
+                return "do_sample"
+            if use_pen:
+                return "repetition_penalty"
+            if logprobs is not None:
+                return "logprobs"
         if forced_tokens is not None:
             return "forced_tokens"
         if layer_hook is not None:
@@ -2184,17 +2204,54 @@ class CausalLMHIP:
         done_at = hit.int().argmax(dim=1)
         return min(n_new, int(torch.where(hit.any(dim=1), done_at + 1, torch.full_like(done_at, n_new)).max()))
 
-    def _speculative_loop(self, logits, out, finished, eos, S: int, k: int, kv_start, pad_token_id: int, collect_logits: bool, draft_tokens, lookup_ids):
+    def _speculative_loop(self, logits, out, finished, eos, S: int, k: int, kv_start, pad_token_id: int, collect_logits: bool, draft_tokens, lookup_ids,
+                          pick: Optional[dict] = None, pen_hist: Optional[torch.Tensor] = None, logprobs: Optional[int] = None):
         """The decode loop of `generate_greedy` with k drafts per step, on its `out` [B, T] / `finished` / `eos`.  Token 0 is the
         prompt pass's; then, with n tokens emitted and the last of them (not yet in the cache) due at slot cur = S + n - 1: draft ->
-        `verify_step` on [last, drafts] -> argmax of all M rows -> `H.spec_accept`, which emits a >= 1 tokens for every row (the
+        `verify_step` on [last, drafts] -> the pick of all M rows -> `H.spec_accept`, which emits a >= 1 tokens for every row (the
         run all unfinished rows accept, the correction behind it included) and hands back a through a pinned int32: ONE host wait
-        per verify step."""
+        per verify step.
+        The pick is the plain loop's for emitted position n + j (`pick`, scope "all"): argmax for plain greedy (pick None);
+        `H.sample_rows` for the chain (repetition penalty, top_k, min_p; both do_sample modes) and `H.sample_top_p_rows` otherwise,
+        at step0 = n.  Two histories are kept apart.  The penalty's is HF's `input_ids`, `pen_hist` [B, Pp + T]: the prompt ids of a
+        text-only chat (left pads included), then the emitted tokens, pad for finished rows; `out` is its tail (a view), so the
+        accept kernel's store into `out` is the store into it, and row j adds the chunk's j drafts in front of it.  The lookup
+        history carries -1 at pads and audio slots and holds the spliced transcription; the accept kernel writes it as well.
+        logprobs = n: one `H.topk_logprobs` launch over the M rows per verify step, in front of the host wait; row (b, j) scores the
+        token it emits, -1 (0 / -1 / 0) on a row finished before the step or behind the first EOS of its run."""
         dev, w, (B, T) = self.dev, k + 1, out.shape
         sp = self._spec_alloc(B, k)
         pred, inp, draft, taken, taken_host, event = (sp[n] for n in ("pred", "inp", "draft", "taken", "taken_host", "event"))
         hist = row_start = None
         P = 0
+        Pp = 0 if pen_hist is None else int(pen_hist.shape[1]) - T
+
+        def first_pick():                                                    # the plain loop's launch at step 0
+            if pick is None:
+                H.argmax_bf16(logits, self.Vp, B, self.V, self.g_next)
+            elif pick["chain"]:
+                H.sample(logits, self.Vp, B, self.V, self.g_next, do_sample=pick["do_sample"], temperature=pick["temperature"], top_k=pick["top_k"],
+                         top_p=pick["top_p"], min_p=pick["min_p"], repetition_penalty=pick["repetition_penalty"], hist=pen_hist, hist_len=Pp,
+                         seed=pick["seed"], step=0)
+            else:
+                H.sample_top_p(logits, self.Vp, B, self.V, pick["temperature"], pick["top_p"], pick["seed"], 0, self.g_next)
+
+        def verify_pick(vl, n):                                              # row j: the plain loop's launch at step n + j
+            if pick is None:
+                H.argmax_bf16(vl, self.Vp, B * w, self.V, pred)
+            elif pick["chain"]:
+                H.sample_rows(vl, self.Vp, B, w, self.V, pred, do_sample=pick["do_sample"], temperature=pick["temperature"], top_k=pick["top_k"],
+                              top_p=pick["top_p"], min_p=pick["min_p"], repetition_penalty=pick["repetition_penalty"], hist=pen_hist,
+                              hist_len=Pp + n, tail=inp, seed=pick["seed"], step0=n)
+            else:
+                H.sample_top_p_rows(vl, self.Vp, B, w, self.V, pick["temperature"], pick["top_p"], pick["seed"], n, pred)
+        if logprobs is not None:
+            lp_tok = torch.zeros(B, T, dtype=F32, device=dev)
+            lp_ids = torch.full((B, T, logprobs), -1, dtype=torch.int32, device=dev)
+            lp_top = torch.zeros(B, T, logprobs, dtype=F32, device=dev)
+            st_tok = torch.empty(B * w, dtype=F32, device=dev)               # one verify step's rows, contiguous for the kernel
+            st_ids = torch.empty(B * w, logprobs, dtype=torch.int32, device=dev)
+            st_top = torch.empty(B * w, logprobs, dtype=F32, device=dev)
         if draft_tokens is not None:                                         # the proposal for emitted position t, -1 = none
             props = torch.full((B, T + k), -1, dtype=torch.int64, device=dev)
             props[:, :T] = draft_tokens.to(dev, torch.int64)[:, :T]
@@ -2205,10 +2262,13 @@ class CausalLMHIP:
                 hist[:, :P] = lookup_ids.to(dev, torch.int64)
             row_start = kv_start if P else torch.zeros(B, dtype=torch.int32, device=dev)
         steps_logits = [logits[:, :self.V].clone()] if collect_logits else None
-        H.argmax_bf16(logits, self.Vp, B, self.V, self.g_next)
+        first_pick()
         out[:, 0] = self.g_next
         if hist is not None:
             hist[:, P] = self.g_next
+        if logprobs is not None:
+            H.topk_logprobs(logits, self.Vp, self.g_next, B, self.V, logprobs, st_tok, st_ids, st_top)
+            lp_tok[:, 0], lp_ids[:, 0], lp_top[:, 0] = st_tok[:B], st_ids[:B], st_top[:B]
         if eos is not None:
             finished |= (self.g_next.unsqueeze(1) == eos.unsqueeze(0)).any(dim=1)
         n, steps = 1, 0
@@ -2221,22 +2281,37 @@ class CausalLMHIP:
             inp[:, 0] = self.g_next
             inp[:, 1:] = draft
             vl = self.verify_step(inp.clamp_min(0), cur, kv_start)          # a -1 draft is embedded as token 0 and can never be accepted
-            H.argmax_bf16(vl, self.Vp, B * w, self.V, pred)
+            verify_pick(vl, n)
+            if logprobs is not None:                                         # `finished` is still the state in front of this step
+                scored = torch.where(finished.unsqueeze(1), torch.full_like(pred, -1), pred)
+                if eos is not None:                                          # the EOS itself is scored, the padding behind it is not
+                    hit = (pred.unsqueeze(2) == eos.view(1, 1, -1)).any(dim=2).to(torch.int32)
+                    scored = torch.where(hit.cumsum(dim=1) - hit > 0, torch.full_like(pred, -1), scored)
             H.spec_accept(pred, inp, k, finished, eos, pad_token_id, T - n, out, n, self.g_next, taken, hist=hist, hist_col=P + n)
             taken_host.copy_(taken, non_blocking=True)
             event.record()
+            if logprobs is not None:                                         # an emitted token is the row's pick: columns [0, a) are read below
+                H.topk_logprobs(vl, self.Vp, scored.contiguous(), B * w, self.V, logprobs, st_tok, st_ids, st_top)
             if collect_logits:
                 rows = vl.view(B, w, self.Vp)[:, :, :self.V].transpose(0, 1).clone()      # [k + 1, B, V], before the wait
             event.synchronize()
             a = int(taken_host[0])
             if collect_logits:
                 steps_logits.extend(rows[:min(a, w)])                        # a > k + 1 only once every row is finished: trimmed below
+            if logprobs is not None:
+                m = min(a, w)
+                lp_tok[:, n:n + m] = st_tok.view(B, w)[:, :m]
+                lp_ids[:, n:n + m] = st_ids.view(B, w, logprobs)[:, :m]
+                lp_top[:, n:n + m] = st_top.view(B, w, logprobs)[:, :m]
             n += a
             steps += 1
         n_new = self._trim_after_eos(out, eos, n)
         self.spec_stats = dict(path="speculative", reason=None, verify_steps=steps, emitted=n_new, drafts_accepted=max(0, n_new - 1 - steps))
         out = out[:, :n_new]
-        return (out, torch.stack(steps_logits[:n_new])) if collect_logits else out
+        res = (out, torch.stack(steps_logits[:n_new])) if collect_logits else (out,)
+        if logprobs is not None:
+            res += (TokenLogprobs(token_logprobs=lp_tok[:, :n_new], top_ids=lp_ids[:, :n_new], top_logprobs=lp_top[:, :n_new]),)
+        return res if len(res) > 1 else out
 
     def generate_greedy(self, x0_filler, B: int, S: int, kv_start: torch.Tensor, max_new_tokens: int, pad_token_id: int,
                         eos_token_ids=None, forced_tokens: Optional[torch.Tensor] = None, collect_logits: bool = False,
@@ -2260,7 +2335,9 @@ class CausalLMHIP:
         top-k / top-p / min-p filters: HF's log_softmax(output_logits), not its processed output_scores.  The EOS token itself is
         scored; the padding behind it is not (0 / -1 / 0).  None: no launch, no allocation.
         speculate = k (1..7; None: the model's `set_speculative`, 0: off): draft-and-verify decoding, `_speculative_loop`; the
-        plain loop below runs instead, and `spec_stats["reason"]` says why, under the conditions `set_speculative` lists.  The
+        plain loop below runs instead, and `spec_stats["reason"]` says why, under the conditions `set_speculative` lists (its
+        scope "all" takes do_sample, repetition_penalty and logprobs off that list: the verify rows then go through the sampler
+        this loop would launch, row j at step n + j, and the result is this loop's).  The
         drafts come from a lookup in `lookup_ids` [B, S] (the prompt's token ids, -1 at left pads and audio positions) followed by
         the emitted tokens, or from `draft_tokens` [B, max_new_tokens] (int64; the proposal for emitted position t, -1 = none)."""
         assert max_new_tokens >= 1
@@ -2287,8 +2364,6 @@ class CausalLMHIP:
         out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
         eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
-        if spec_reason is None:
-            return self._speculative_loop(logits, out, finished, eos, S, spec_k, kv_start, int(pad_token_id), collect_logits, draft_tokens, lookup_ids)
         P = 0
         if chain:                                                            # token history = [prompt ids,] emitted tokens: out is its tail
             P = 0 if prompt_ids is None else int(prompt_ids.shape[1])
@@ -2296,6 +2371,13 @@ class CausalLMHIP:
             if P:
                 hist[:, :P] = prompt_ids.to(dev, torch.int64)
             out = hist[:, P:]
+        if spec_reason is None:
+            pick = None
+            if chain or do_sample:                                           # scope "all": the plain loop's sampler, one row per emitted position
+                pick = dict(chain=chain, do_sample=do_sample, temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p),
+                            min_p=float(min_p or 0.0), repetition_penalty=float(repetition_penalty) if use_pen else 1.0, seed=seed)
+            return self._speculative_loop(logits, out, finished, eos, S, spec_k, kv_start, int(pad_token_id), collect_logits, draft_tokens, lookup_ids,
+                                          pick=pick, pen_hist=hist if chain else None, logprobs=logprobs)
         steps_logits = []
         if logprobs is not None:
             lp_tok = torch.zeros(B, max_new_tokens, dtype=F32, device=dev)
@@ -2627,13 +2709,16 @@ class DeSTA25AudioModel:
         check_prefill_chunk(n)
         self.llm.set_prefill_chunk(n)
 
-    def set_speculative(self, k: Optional[int]) -> None:
-        """Greedy decoding of `generate` / `_generate_step` / the trainer's evaluate: None or 0 (default) = one token per step; an
+    def set_speculative(self, k: Optional[int], scope: str = "greedy") -> None:
+        """Decoding of `generate` / `_generate_step` / the trainer's evaluate: None or 0 (default) = one token per step; an
         int k in 1..7 = k draft tokens per step from a lookup in the row's own prompt (the spliced transcription included) and
         output, verified by one pass over the weights (`CausalLMHIP.set_speculative`, which lists what runs the plain loop
-        instead).  `model.llm.spec_stats` reports the path taken and the acceptance of the last call."""
+        instead).  scope = "greedy" (default): plain greedy calls only; scope = "all": sampled calls (the default of `generate`),
+        a repetition penalty and `logprobs` speculate too and return the plain loop's tokens.  A bad k or scope raises ValueError
+        and leaves the setting as it was.  `model.llm.spec_stats` reports the path taken and the acceptance of the last call."""
         check_speculative_arg(k)
-        self.llm.set_speculative(k)
+        check_speculative_scope(scope)
+        self.llm.set_speculative(k, scope)
 
     def eval(self):
         return self.train(False)
@@ -2841,7 +2926,9 @@ class DeSTA25AudioModel:
         logprobs = n: a `TokenLogprobs` becomes the last element of the result, (ids, lp) or (ids, logits, lp): every emitted
         token's log-probability and the n most likely tokens of its step under the model's own distribution, log_softmax of the
         raw logits (HF's output_logits, not the processed output_scores; see `CausalLMHIP.generate_greedy`).
-        With `set_speculative(k)` greedy calls decode by draft and verify; the drafts are looked up in the row's prompt ids (the
+        With `set_speculative(k)` greedy calls decode by draft and verify, and with `set_speculative(k, scope="all")` sampled,
+        penalised and `logprobs` calls do too, with the plain loop's tokens and `TokenLogprobs`.
+        The drafts are looked up in the row's prompt ids (the
         spliced transcription included, audio slots and pads never match) and its output, or taken from `draft_tokens`
         [B, max_new_tokens] (the proposal for emitted position t, -1 = none: tests and benchmarks)."""
         check_sampling_args(top_k, min_p, repetition_penalty)

@@ -207,6 +207,18 @@ def speculative(cfg: Cfg):
     return k or None
 
 
+SPECULATIVE_SCOPES = ("greedy", "all")
+
+
+def speculative_scope(cfg: Cfg) -> str:
+    """trainer.speculative_scope (this port's key; absent = "greedy"): which decoding calls `trainer.speculative` covers, "greedy"
+    (plain greedy only) or "all" (sampling, a repetition penalty and logprobs too; `DeSTA25AudioModel.set_speculative`)."""
+    scope = cfg.trainer.get("speculative_scope", "greedy")
+    if not isinstance(scope, str) or scope not in SPECULATIVE_SCOPES:
+        raise ValueError(f"trainer.speculative_scope={scope!r} is not supported (one of {', '.join(SPECULATIVE_SCOPES)}, or absent)")
+    return scope
+
+
 def load_pretrained_weights(model, path: str) -> None:
     """Lightning-style {'state_dict': ...} with a 'model.' prefix (reference :73-83); tensors only."""
     import torch
@@ -272,6 +284,7 @@ def main(argv=None):
     kv_cache = kv_cache_kind(cfg)
     chunk = prefill_chunk(cfg)
     spec = speculative(cfg)
+    spec_scope = speculative_scope(cfg)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
@@ -281,7 +294,7 @@ def main(argv=None):
     model.set_decode_weights(decode_weights)
     model.set_kv_cache(kv_cache)
     model.set_prefill_chunk(chunk)
-    model.set_speculative(spec)
+    model.set_speculative(spec, spec_scope)
     if cfg.get("init_from_pretrained_weights"):
         load_pretrained_weights(model, cfg.init_from_pretrained_weights)
     train_ds, eval_ds, collate, tok = create_datasets(cfg, model, rank)

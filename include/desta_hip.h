@@ -653,6 +653,30 @@ int desta_sample_bf16(const void* logits, int64_t ld, int rows, int cols, const 
                       float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
                       uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream);
 
+/* The two samplers over the rows of a verify step (additive since ABI 8; `CausalLMHIP._speculative_loop` under
+ * `set_speculative(k, scope="all")`): the logits hold batch * width rows, batch-major, row r = b * width + j, 1 <= width <= 8
+ * (k + 1).  Row (b, j) is DEFINED as what desta_sample_bf16 / desta_sample_top_p_bf16 return for row b of a `batch`-row launch at
+ * step = step0 + j (a uint32 sum: it wraps, as step does) — emitted position step0 + j of sequence b in the loop of
+ * `llm_model.generate` (modeling_desta25.py:1419-1427, :1703-1711), so a verify step picks what the token-by-token loop picks:
+ *   draw ............ desta_rng32(seed, ((uint64)(uint32)(step0 + j) << 32) | b): the counter row is b, not r;
+ *   penalty history . (desta_sample_rows_bf16) the distinct ids of hist[b*hist_ld + 0 .. hist_len) and of
+ *                     tail[b*tail_ld + 1 .. 1 + j): `tail` is the verify step's input [batch, k + 1], whose column 0 is the last
+ *                     emitted token (hist holds it at hist_len - 1) and whose columns 1..k are the drafts; ids outside [0, cols)
+ *                     are ignored, so a -1 draft is.  tail may be NULL when width == 1 or repetition_penalty == 1.
+ * Everything else is the one-row-per-sequence entry point's, both modes of do_sample included: processor order, fixed-point
+ * masses, index-order prefix sum, ties, -inf handling, token 0 for a row without a finite score; out [batch * width] and
+ * keep_mask [batch * width, cols] are indexed by r.  The kernels are the same ones (width = 1 there).  DESTA_EINVAL, nothing
+ * launched: what the one-row entry points reject, a width outside 1..8, and a NULL tail (or tail_ld < width) when width > 1
+ * and repetition_penalty != 1. */
+int desta_sample_rows_bf16(const void* logits, int64_t ld, int batch, int width, int cols,
+                           const int64_t* hist, int64_t hist_ld, int hist_len,
+                           const int64_t* tail, int64_t tail_ld,
+                           float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
+                           uint64_t seed, uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream);
+int desta_sample_top_p_rows_bf16(const void* logits, int64_t ld, int batch, int width, int cols,
+                                 float temperature, float top_p, uint64_t seed, uint32_t step0,
+                                 int64_t* out, uint8_t* keep_mask, void* stream);
+
 /* desta_rope (forward) on a fused q|k|v projection [rows, ld] that ALSO appends the rotated K heads and the V heads of
  * row (b, s) to a KV cache slab: kv_cache + b*kv_batch_stride + (slot0 + s)*kv_row_stride, K heads then V heads.
  * This is what `DynamicCache.update` does inside `llm_model.generate` (modeling_desta25.py:1419) for the prompt

@@ -12,11 +12,15 @@ tokens, no EOS):
   * the ORCA-hybrid model of tests/test_gpu_speculative.py::test_orca_model_falls_back (a `layer_hook`) and the LoRA model of
     tests/test_gpu_lora.py (merged q|k|v weights);
   * speculative: k in {3, 7} x drafts {none (all -1), perfect (the plain run's tokens), lookup} x decode weights {bf16, fp8};
-  * `verify_step` called directly after a prompt pass, per k, on the plain run's tokens: its logits and the cache over [0, S + k].
-Only entry points that both trees have are used.
+  * `verify_step` called directly after a prompt pass, per k, on the plain run's tokens: its logits and the cache over [0, S + k];
+  * speculative under scope "all" (`spec-all` lines, printed only by a tree whose `set_speculative` has the argument): {top-p,
+    chain, chain + penalty, greedy + penalty, logprobs} x k in {3, 7} x drafts {none, perfect (the plain loop's tokens under the same
+    settings), lookup}.
+Apart from the `spec-all` lines only entry points that both trees have are used.
   python tools/generate_bits.py"""
 import copy
 import hashlib
+import inspect
 import os
 import sys
 
@@ -31,6 +35,11 @@ from test_gpu_kv8_cache import _text_inputs
 from test_gpu_prefill_chunk import PADS, _model
 
 T = 12
+SCOPE_ALL_CASES = (("top_p", dict(do_sample=True, temperature=0.8, top_p=0.9, seed=3)),
+                   ("chain", dict(do_sample=True, temperature=0.8, top_p=0.9, top_k=40, min_p=0.02, seed=3)),
+                   ("penalty", dict(do_sample=True, temperature=0.8, top_p=0.9, top_k=40, min_p=0.02, repetition_penalty=1.3, seed=3)),
+                   ("greedy+penalty", dict(repetition_penalty=1.3)),
+                   ("logprobs", dict(logprobs=4)))
 
 
 def sha(*items):
@@ -98,6 +107,15 @@ def tiny_cases(g4):
                 torch.cuda.synchronize()
                 print(f"verify   {tag} weights {weights:4s} k {k}  {sha(vl, *[c[:, :S + k + 1] for c in llm.kv_cache])}", flush=True)
         model.set_decode_weights("bf16")
+        if "scope" in inspect.signature(model.set_speculative).parameters:  # a tree without the scope argument prints the lines above only
+            for name, kw in SCOPE_ALL_CASES:
+                own = gen(model, inputs, **kw)[0].clone()                    # the plain loop's tokens under these settings: the perfect drafts
+                for k in (3, 7):
+                    model.set_speculative(k, scope="all")
+                    for src, dr in (("none", torch.full_like(own, -1)), ("perfect", own), ("lookup", None)):
+                        res = gen(model, inputs, draft_tokens=dr, **kw)
+                        print(f"spec-all {tag} {name:14s} k {k} drafts {src:7s}  {digest(model, S, res)}", flush=True)
+                    model.set_speculative(None)
         if g4 or S != 61:
             continue
         forced = (plain["bf16"] + 1) % d.vocab                               # never the model's own pick

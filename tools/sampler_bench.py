@@ -4,7 +4,10 @@
 log-probability + top 5 of generate(logprobs=5)) beside the chain sampler it follows in a decode step.  Device-event timing over `--iters`
 back-to-back calls; for kernel times run it under `rocprofv3 --kernel-trace --stats`.
 
-  python tools/sampler_bench.py [--rows 8] [--vocab 128256 151936] [--iters 200] [--hist 256]
+--grouped adds the entry points of a verify step (`sample_rows`, `sample_top_p_rows`) at batch x width = 4, 8, 32 and 64 rows against
+the one-row entry points at the same row count (`grouped()` below).
+
+  python tools/sampler_bench.py [--rows 8] [--vocab 128256 151936] [--iters 200] [--hist 256] [--grouped] [--rounds 5]
 """
 import argparse
 import json
@@ -21,6 +24,8 @@ def main():
     ap.add_argument("--vocab", type=int, nargs="+", default=[128256, 151936])
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--hist", type=int, default=256, help="history length of the penalised cases")
+    ap.add_argument("--grouped", action="store_true", help="also time the grouped entry points at 4, 8, 32 and 64 rows against the one-row ones")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of the --grouped comparison")
     a = ap.parse_args()
     from desta import _hip as H
     dev = torch.device("cuda:0")
@@ -54,6 +59,56 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             print(json.dumps({"shape": [B, V], "case": name, "us_per_call": round(e0.elapsed_time(e1) * 1e3 / a.iters, 2)}), flush=True)
+        if a.grouped:
+            grouped(H, a, V, ld, dev, g)
+
+
+def grouped(H, a, V, ld, dev, g):
+    """The grouped entry points (`sample_rows`, `sample_top_p_rows`: batch x width rows of a verify step) against the one-row entry
+    points at the same row count, alternating in one process for --rounds rounds: medians, spreads (max - min over the rounds) and
+    the fold rule, grouped median <= one-row median + both spreads."""
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / a.iters
+
+    for rows in (4, 8, 32, 64):
+        for width in sorted({min(rows, 4), min(rows, 8)}):
+            batch = rows // width
+            logits = (torch.randn(rows, ld, device=dev, generator=g) * 3).to(torch.bfloat16)
+            hist = torch.randint(0, V, (rows, a.hist), device=dev, generator=g)
+            tail = torch.randint(0, V, (batch, width), device=dev, generator=g)
+            out = torch.zeros(rows, dtype=torch.int64, device=dev)
+            full = dict(temperature=0.7, top_k=50, top_p=0.9, min_p=0.05, repetition_penalty=1.2, hist_len=a.hist, seed=1)
+            pairs = {
+                "top_p": (lambda: H.sample_top_p(logits, ld, rows, V, 0.7, 0.9, 1, 0, out),
+                          lambda: H.sample_top_p_rows(logits, ld, batch, width, V, 0.7, 0.9, 1, 0, out)),
+                "chain top_p": (lambda: H.sample(logits, ld, rows, V, out, temperature=0.7, top_p=0.9, seed=1),
+                                lambda: H.sample_rows(logits, ld, batch, width, V, out, temperature=0.7, top_p=0.9, seed=1)),
+                "chain full": (lambda: H.sample(logits, ld, rows, V, out, hist=hist, **full),
+                               lambda: H.sample_rows(logits, ld, batch, width, V, out, hist=hist, tail=tail, **full)),
+                "greedy + penalty": (lambda: H.sample(logits, ld, rows, V, out, do_sample=False, repetition_penalty=1.2, hist=hist, hist_len=a.hist),
+                                     lambda: H.sample_rows(logits, ld, batch, width, V, out, do_sample=False, repetition_penalty=1.2, hist=hist,
+                                                           hist_len=a.hist, tail=tail)),
+            }
+            for name, (one, grp) in pairs.items():
+                for fn in (one, grp):
+                    for _ in range(10):
+                        fn()
+                torch.cuda.synchronize()
+                t1, tg = [], []
+                for _ in range(a.rounds):
+                    t1.append(timed(one))
+                    tg.append(timed(grp))
+                m1, mg = sorted(t1)[len(t1) // 2], sorted(tg)[len(tg) // 2]
+                s1, sg = max(t1) - min(t1), max(tg) - min(tg)
+                print(json.dumps({"rows": rows, "batch": batch, "width": width, "vocab": V, "case": name, "one_row_us": round(m1, 2),
+                                  "one_row_spread": round(s1, 2), "grouped_us": round(mg, 2), "grouped_spread": round(sg, 2),
+                                  "grouped_within_spreads": bool(mg - m1 <= s1 + sg)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """Draft-and-verify greedy decoding (`set_speculative`) against the plain loop at the full model size, on one MI355X.
 
   python tools/spec_decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 1,4,8,16] [--k 3,7] [--ctx 64] [--prompt-tail 16]
-                                    [--new 64] [--weights {bf16,fp8}] [--prefill-chunk N] [--rounds 3]
+                                    [--new 64] [--weights {bf16,fp8}] [--prefill-chunk N] [--rounds 3] [--sample] [--penalty 1.05]
+                                    [--no-greedy]
 The workload flags are those of tools/decode_bench.py (--batch and --k take comma-separated lists).  For every batch size the plain
 loop and, per k, three speculative legs alternate in ONE process for --rounds rounds after a warm-up of every leg; each run is
 timed with HIP events around `_generate_step`, and the time of a prompt-only run (one new token, same leg, same round) is taken
@@ -18,6 +19,10 @@ One JSON line per (batch, leg, round), one summary line per (batch, k) with medi
 break-even: a verify step costs `step_ms` (median over the accepted and rejected legs) and pays for itself once it emits
 step_ms / plain_ms_per_token tokens, i.e. that many minus one accepted drafts per step.  B * (k + 1) > H.DECODE_MAX_ROWS runs the plain
 loop (`spec_stats["reason"]`): the summary says so and reports no speculative figure.
+--sample and --penalty P add, per batch size, the same plain / accepted / rejected / lookup legs under `set_speculative(k, scope="all")`
+for sampled calls (temperature 0.7, top_p 0.9, the reference's defaults: `sample_top_p_rows` picks the verify rows) and for greedy
+calls with a repetition penalty (`sample_rows`); every line carries its `mode`.  `accepted` again takes the path's own output (the
+`rejected` leg's ids under the same mode) as drafts, and the plain leg of a mode is the plain loop with the same settings.
 """
 import argparse
 import json
@@ -43,6 +48,9 @@ def main():
     ap.add_argument("--weights", choices=("bf16", "fp8"), default="bf16")
     ap.add_argument("--prefill-chunk", type=int, default=None)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sample", action="store_true", help="add the sampled legs (temperature 0.7, top_p 0.9: the reference's defaults), scope \"all\"")
+    ap.add_argument("--penalty", type=float, default=None, help="add greedy legs with this repetition penalty (e.g. 1.05), scope \"all\"")
+    ap.add_argument("--no-greedy", action="store_true", help="leave the plain greedy legs out")
     a = ap.parse_args()
     batches, ks = [int(x) for x in a.batch.split(",")], [int(x) for x in a.k.split(",")]
     assert a.new >= 2 and a.rounds >= 1
@@ -56,6 +64,12 @@ def main():
     model.set_decode_weights(a.weights)
     model.set_prefill_chunk(a.prefill_chunk)
     llm = model.llm
+    modes = [] if a.no_greedy else [("greedy", dict(do_sample=False), "greedy")]
+    if a.sample:
+        modes.append(("sample", dict(do_sample=True, temperature=0.7, top_p=0.9, seed=1), "all"))
+    if a.penalty is not None:
+        modes.append((f"penalty {a.penalty}", dict(do_sample=False, repetition_penalty=a.penalty), "all"))
+    assert modes, "nothing to run"
 
     for B in batches:
         t = synthetic_inputs(cfg, B, a.ctx, a.prompt_tail, dev, seed=5)
@@ -65,69 +79,70 @@ def main():
                   "batch_transcription_ids": t["batch_transcription_ids"]}
         S = t["input_ids"].shape[1]
 
-        def timed(k, drafts, new):
-            """-> (ms of one `_generate_step` by HIP events, ids, spec_stats)"""
-            model.set_speculative(k)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            ids = model._generate_step(inputs, pad_token_id=0, max_new_tokens=new, do_sample=False, eos_token_id=[], draft_tokens=drafts)
-            e1.record()
-            e1.synchronize()
-            return e0.elapsed_time(e1), ids, dict(llm.spec_stats)
+        for mode, gen_kw, scope in modes:
+            def timed(k, drafts, new):
+                """-> (ms of one `_generate_step` by HIP events, ids, spec_stats)"""
+                model.set_speculative(k, scope=scope)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                ids = model._generate_step(inputs, pad_token_id=0, max_new_tokens=new, eos_token_id=[], draft_tokens=drafts, **gen_kw)
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1), ids, dict(llm.spec_stats)
 
-        def leg(name, k, drafts):
-            prompt_ms, _, _ = timed(k, None if drafts is None else drafts[:, :1], 1)
-            ms, ids, st = timed(k, drafts, a.new)
-            assert ids.shape == (B, a.new)
-            steps = st["verify_steps"]
-            r = {"B": B, "prompt": S, "new": a.new, "weights": a.weights, "leg": name, "k": k, "path": st["path"], "reason": st["reason"],
-                 "prompt_ms": round(prompt_ms, 3), "decode_ms": round(ms - prompt_ms, 3),
-                 "ms_per_emitted_token": round((ms - prompt_ms) / (a.new - 1), 4), "verify_steps": steps,
-                 "tokens_per_verify_step": round((a.new - 1) / steps, 3) if steps else None,
-                 "ms_per_verify_step": round((ms - prompt_ms) / steps, 4) if steps else None}
-            print(json.dumps(r), flush=True)
-            return r, ids
+            def leg(name, k, drafts):
+                prompt_ms, _, _ = timed(k, None if drafts is None else drafts[:, :1], 1)
+                ms, ids, st = timed(k, drafts, a.new)
+                assert ids.shape == (B, a.new)
+                steps = st["verify_steps"]
+                r = {"mode": mode, "B": B, "prompt": S, "new": a.new, "weights": a.weights, "leg": name, "k": k, "path": st["path"], "reason": st["reason"],
+                     "prompt_ms": round(prompt_ms, 3), "decode_ms": round(ms - prompt_ms, 3),
+                     "ms_per_emitted_token": round((ms - prompt_ms) / (a.new - 1), 4), "verify_steps": steps,
+                     "tokens_per_verify_step": round((a.new - 1) / steps, 3) if steps else None,
+                     "ms_per_verify_step": round((ms - prompt_ms) / steps, 4) if steps else None}
+                print(json.dumps(r), flush=True)
+                return r, ids
 
-        _, plain_ids = leg("plain", None, None)                             # warm-up
-        none = torch.full_like(plain_ids, -1)
-        legs = [("plain", None, None)]
-        for k in ks:                                                         # warm-up of every leg: buffers, workspaces, code objects
-            _, own = leg("rejected", k, none)                                # the verify path's own greedy output at this row count
-            legs += [("accepted", k, own), ("rejected", k, none), ("lookup", k, None)]
-            for name, _, dr in legs[-3:]:
-                r, ids = leg(name, k, dr)
-                if r["path"] == "speculative":
-                    print(json.dumps({"B": B, "k": k, "leg": name, "tokens_equal_to_rejected_leg": float((ids == own).float().mean()),
-                                      "tokens_equal_to_plain": float((ids == plain_ids).float().mean())}), flush=True)
-        runs = {(name, k): [] for name, k, _ in legs}
-        for _ in range(a.rounds):
-            for name, k, dr in legs:
-                runs[(name, k)].append(leg(name, k, dr)[0])
-        plain = [r["ms_per_emitted_token"] for r in runs[("plain", None)]]
-        for k in ks:
-            acc, rej, look = runs[("accepted", k)], runs[("rejected", k)], runs[("lookup", k)]
-            s = {"summary": f"{a.config} B={B} prompt={S} new={a.new} weights={a.weights} k={k}", "rounds": a.rounds,
-                 "plain_ms_per_token": plain, "plain_median": _median(plain), "plain_spread": round(max(plain) - min(plain), 4)}
-            if acc[0]["path"] != "speculative":
-                s["speculative"] = f"not run: {acc[0]['reason']}"
+            _, plain_ids = leg("plain", None, None)                             # warm-up
+            none = torch.full_like(plain_ids, -1)
+            legs = [("plain", None, None)]
+            for k in ks:                                                         # warm-up of every leg: buffers, workspaces, code objects
+                _, own = leg("rejected", k, none)                                # the verify path's own greedy output at this row count
+                legs += [("accepted", k, own), ("rejected", k, none), ("lookup", k, None)]
+                for name, _, dr in legs[-3:]:
+                    r, ids = leg(name, k, dr)
+                    if r["path"] == "speculative":
+                        print(json.dumps({"mode": mode, "B": B, "k": k, "leg": name, "tokens_equal_to_rejected_leg": float((ids == own).float().mean()),
+                                          "tokens_equal_to_plain": float((ids == plain_ids).float().mean())}), flush=True)
+            runs = {(name, k): [] for name, k, _ in legs}
+            for _ in range(a.rounds):
+                for name, k, dr in legs:
+                    runs[(name, k)].append(leg(name, k, dr)[0])
+            plain = [r["ms_per_emitted_token"] for r in runs[("plain", None)]]
+            for k in ks:
+                acc, rej, look = runs[("accepted", k)], runs[("rejected", k)], runs[("lookup", k)]
+                s = {"summary": f"{a.config} {mode} B={B} prompt={S} new={a.new} weights={a.weights} k={k}", "mode": mode, "rounds": a.rounds,
+                     "plain_ms_per_token": plain, "plain_median": _median(plain), "plain_spread": round(max(plain) - min(plain), 4)}
+                if acc[0]["path"] != "speculative":
+                    s["speculative"] = f"not run: {acc[0]['reason']}"
+                    print(json.dumps(s), flush=True)
+                    continue
+                for name, rs in (("accepted", acc), ("rejected", rej), ("lookup", look)):
+                    v = [r["ms_per_emitted_token"] for r in rs]
+                    s[name] = {"ms_per_emitted_token": v, "median": _median(v), "spread": round(max(v) - min(v), 4),
+                               "tokens_per_verify_step": rs[0]["tokens_per_verify_step"], "ms_per_verify_step": _median([r["ms_per_verify_step"] for r in rs])}
+                step_ms = _median([r["ms_per_verify_step"] for r in acc + rej])
+                s["verify_step_ms"] = step_ms
+                s["verify_step_over_plain_step"] = round(step_ms / s["plain_median"], 3)
+                s["break_even_tokens_per_verify_step"] = round(step_ms / s["plain_median"], 3)
+                s["break_even_accepted_drafts_per_step"] = round(step_ms / s["plain_median"] - 1, 3)
+                s["break_even_acceptance_of_k"] = round((step_ms / s["plain_median"] - 1) / k, 3)
+                s["accepted_speedup_median"] = round(s["plain_median"] / s["accepted"]["median"], 3)
+                s["accepted_faster_beyond_spread"] = bool(s["plain_median"] - s["accepted"]["median"] > s["plain_spread"] + s["accepted"]["spread"])
+                s["rejected_slowdown_median"] = round(s["rejected"]["median"] / s["plain_median"], 3)
+                s["lookup_note"] = "synthetic weights: the lookup leg's acceptance says nothing about a trained checkpoint"
                 print(json.dumps(s), flush=True)
-                continue
-            for name, rs in (("accepted", acc), ("rejected", rej), ("lookup", look)):
-                v = [r["ms_per_emitted_token"] for r in rs]
-                s[name] = {"ms_per_emitted_token": v, "median": _median(v), "spread": round(max(v) - min(v), 4),
-                           "tokens_per_verify_step": rs[0]["tokens_per_verify_step"], "ms_per_verify_step": _median([r["ms_per_verify_step"] for r in rs])}
-            step_ms = _median([r["ms_per_verify_step"] for r in acc + rej])
-            s["verify_step_ms"] = step_ms
-            s["verify_step_over_plain_step"] = round(step_ms / s["plain_median"], 3)
-            s["break_even_tokens_per_verify_step"] = round(step_ms / s["plain_median"], 3)
-            s["break_even_accepted_drafts_per_step"] = round(step_ms / s["plain_median"] - 1, 3)
-            s["break_even_acceptance_of_k"] = round((step_ms / s["plain_median"] - 1) / k, 3)
-            s["accepted_speedup_median"] = round(s["plain_median"] / s["accepted"]["median"], 3)
-            s["accepted_faster_beyond_spread"] = bool(s["plain_median"] - s["accepted"]["median"] > s["plain_spread"] + s["accepted"]["spread"])
-            s["rejected_slowdown_median"] = round(s["rejected"]["median"] / s["plain_median"], 3)
-            s["lookup_note"] = "synthetic weights: the lookup leg's acceptance says nothing about a trained checkpoint"
-            print(json.dumps(s), flush=True)
         model.set_speculative(None)
 
 
