@@ -1526,6 +1526,13 @@ __global__ __launch_bounds__(256) void attn_dq_sum_k(AttnArgs p, const float* __
 //      bf16 kernel rounds; the row sum keeps pv;
 //   6. V bytes become fp32 by the packed conversion instead of a shift (v_unpack).
 // and, arithmetic aside, in where decode_load_q is called (see there): a scheduling matter, measured.
+//
+// Verify step of draft-and-verify decoding (ROWS; desta_attention_verify{,_kv8}): seq_q = w = 2..8 query rows per sequence on the
+// same items.  The R = G w <= 16 query rows of a KV head take B columns 0..R-1 (column c: query row c / G, head hk G + c % G),
+// the mask is the forward kernel's causal rule per column (key <= j + seq_k - seq_q), and maximum, sum, empty chunk and the merge
+// are per column already.  At R > 8 the P . V walks two row groups of 8 with V kept in registers.  Row j equals the one-row kernel
+// at seq_k - (w - 1 - j) keys bit for bit (include/desta_hip.h says why), which is what lets the speculative loop and the plain
+// loop agree from the dispatch threshold on.
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 __device__ __forceinline__ bf16x8 e4m3x8_to_bf16(const uint2& q) {
     union { unsigned u[4]; bf16x8 v; } o;
@@ -1554,29 +1561,35 @@ __device__ __forceinline__ void v_unpack(const uint2& v, float (&f)[8]) {
     for (int j2 = 0; j2 < 4; ++j2) { f[2 * j2] = vv[j2][0]; f[2 * j2 + 1] = vv[j2][1]; }
 }
 
-// the B operand: this lane's 4 x 8 elements of its query row, zero for the columns past the group
+// the B operand: this lane's 4 x 8 elements of its query row, zero for the columns past the group.  ROWS (seq_q = w rows per
+// sequence): column c < R = G w is query row c / G of head hk G + c % G
+template <bool ROWS>
 __device__ __forceinline__ void decode_load_q(const AttnArgs& p, int b, int hk, int G, int c16, int q4, bf16x8 (&qf)[4]) {
-    const bf16_t* qptr = p.Q + (long)b * p.q_bs + (long)(hk * G + min(c16, G - 1)) * 128 + 8 * q4;
+    const int R = ROWS ? G * p.Sq : G, c = min(c16, R - 1);
+    const bf16_t* qptr = p.Q + (long)b * p.q_bs + (ROWS ? (long)(c / G) * p.q_rs + (long)(hk * G + c % G) * 128 : (long)(hk * G + c) * 128) + 8 * q4;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
         qf[ks] = *(const bf16x8*)(qptr + 32 * ks);
-        if (c16 >= G)
+        if (c16 >= R)
 #pragma unroll
             for (int j = 0; j < 8; ++j) qf[ks][j] = (__bf16)0.f;
     }
 }
-template <int GP, bool KV8>                                // G rounded up to 1, 2, 4, 8; KV8: k_scale, v_scale, sc_bs, sc_rs are read
+template <int GP, bool KV8, bool ROWS = false>            // GP: the query rows per KV head (G; ROWS: G seq_q) rounded up to 1, 2, 4, 8 (ROWS: 16 too); KV8: k_scale, v_scale, sc_bs, sc_rs are read
 __device__ __forceinline__ void attn_decode_body(const AttnArgs& p, const float* __restrict__ k_scale, const float* __restrict__ v_scale, long sc_bs,
                                                  long sc_rs, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
     typedef typename DecodeKV<KV8>::elem E;
     typedef typename DecodeKV<KV8>::kfrag KF;
     typedef typename DecodeKV<KV8>::vfrag VF;
     constexpr int CH = DESTA_ATTN_DECODE_CHUNK, KW = CH / 4, NT16 = KW / 16, NV = KW / 4;
-    __shared__ __attribute__((aligned(16))) float s_p[4][KW][8];
+    constexpr int PW = GP > 8 ? 16 : 8;                    // score columns kept: every query row of the item
+    constexpr int GA = GP > 8 ? 8 : GP;                    // query rows of one P . V pass (acc[GA][8] next to the V fragments)
+    static_assert(ROWS ? (GP >= 2 && GP <= 16) : GP <= 8, "one row per sequence: at most 8 rows per KV head");
+    __shared__ __attribute__((aligned(16))) float s_p[4][KW][PW];
     __shared__ __attribute__((aligned(16))) float s_red[4][GP][128];
-    __shared__ float s_m[4][8], s_l[4][8];
+    __shared__ float s_m[4][PW], s_l[4][PW];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), c16 = lane & 15, q4 = lane >> 4;
-    const int G = p.Hq / p.Hkv;
+    const int G = p.Hq / p.Hkv, R = ROWS ? G * p.Sq : G;
     int id = blockIdx.x;
     const int c = id % nch; id /= nch;
     const int hk = id % p.Hkv, b = id / p.Hkv;
@@ -1584,6 +1597,10 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& p, const float*
     const int k0 = c * CH + wave * KW;
     const bool live = k0 < p.Sk && k0 + KW > kv_lo;        // wave-uniform: some key of this wave is visible
     const int row_lo = min(kv_lo, p.Sk - 1), row_hi = p.Sk - 1;
+    // ROWS: the forward kernel's causal rule, key <= j + (seq_k - seq_q) for this lane's query row j = c16 / G.  A masked key
+    // gives p = exp2(-inf) = 0 and fma(0, v, acc) = acc (v is a loaded, finite cache value), so row j is the one-row kernel's
+    // result at seq_k - (seq_q - 1 - j), bit for bit
+    const int key_hi = ROWS ? p.Sk - (p.Sq - 1 - min(c16, R - 1) / G) : p.Sk;
 
     KF kf[NT16][4];
     VF vf[NV];
@@ -1593,7 +1610,7 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& p, const float*
     // want different things from hipcc (measured, B = 64 x 4 096 keys): behind the byte loads of KV8 it issues them one by one,
     // each after a full drain of the loads in flight (153.9 us against 136.2); in front of the bf16 loads it keeps fewer K / V
     // loads in flight (208 us against 199).
-    if constexpr (KV8) decode_load_q(p, b, hk, G, c16, q4, qf);
+    if constexpr (KV8) decode_load_q<ROWS>(p, b, hk, G, c16, q4, qf);
     if (live) {
         const E* kbase = (const E*)p.K + (long)b * p.k_bs + (long)hk * 128 + 8 * q4;
         const E* vbase = (const E*)p.V + (long)b * p.v_bs + (long)hk * 128 + 8 * c16;
@@ -1631,7 +1648,7 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& p, const float*
 #pragma unroll
         for (int i = 0; i < NV; ++i) vf[i] = VF{};
     }
-    if constexpr (!KV8) decode_load_q(p, b, hk, G, c16, q4, qf);
+    if constexpr (!KV8) decode_load_q<ROWS>(p, b, hk, G, c16, q4, qf);
 
     // scores of the wave's KW keys, masked and scaled; st[t][r]: key k0 + 16 t + 4 q4 + r, query row c16
     f32x4 st[NT16];
@@ -1645,15 +1662,15 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& p, const float*
         for (int r = 0; r < 4; ++r) {
             const int key = k0 + 16 * t + 4 * q4 + r;
             const float sk = KV8 ? st[t][r] * ksc[t][r] : st[t][r];         // 2^e commutes with every fp32 rounding
-            st[t][r] = (key >= kv_lo && key < p.Sk) ? sk * p.scale_log2 : -INFINITY;
+            st[t][r] = (key >= kv_lo && key < key_hi) ? sk * p.scale_log2 : -INFINITY;
             mx = fmaxf(mx, st[t][r]);
         }
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (lane < 8) s_m[wave][lane] = mx;
+    if (lane < PW) s_m[wave][lane] = mx;
     __syncthreads();
-    const int g8 = c16 & 7;
+    const int g8 = c16 & (PW - 1);
     const float mblk = fmaxf(fmaxf(s_m[0][g8], s_m[1][g8]), fmaxf(s_m[2][g8], s_m[3][g8]));
     const float muse = (mblk == -INFINITY) ? 0.f : mblk;
     float ls = 0.f;
@@ -1663,107 +1680,131 @@ __device__ __forceinline__ void attn_decode_body(const AttnArgs& p, const float*
         for (int r = 0; r < 4; ++r) {
             const float pv = __builtin_amdgcn_exp2f(st[t][r] - muse);
             ls += pv;
-            if (c16 < 8) s_p[wave][16 * t + 4 * q4 + r][c16] = KV8 ? pv * vsc[t][r] : pv;      // exact; the row sum keeps pv
+            if (c16 < PW) s_p[wave][16 * t + 4 * q4 + r][c16] = KV8 ? pv * vsc[t][r] : pv;      // exact; the row sum keeps pv
         }
     ls += __shfl_xor(ls, 16, 64);
     ls += __shfl_xor(ls, 32, 64);
-    if (lane < 8) s_l[wave][lane] = ls;
+    if (lane < PW) s_l[wave][lane] = ls;
     __syncthreads();
 
-    // P . V: acc[g][j] = sum over this lane's keys of P[g][key] * V[key][8 c16 + j]
-    float acc[GP][8];
+    // P . V: acc[g][j] = sum over this lane's keys of P[h0 + g][key] * V[key][8 c16 + j], GA query rows per pass (16 rows: two
+    // passes, V stays in registers and P is read again; a row's summation order does not depend on the pass it is in)
+#pragma unroll 1
+    for (int h0 = 0; h0 < GP; h0 += GA) {
+        float acc[GA][8];
 #pragma unroll
-    for (int g = 0; g < GP; ++g)
+        for (int g = 0; g < GA; ++g)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
+            for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const float* pr = &s_p[wave][4 * i + q4][0];
-        float pg[GP];
-        if constexpr (GP >= 4) {
+        for (int i = 0; i < NV; ++i) {
+            const float* pr = &s_p[wave][4 * i + q4][h0];
+            float pg[GA];
+            if constexpr (GA >= 4) {
 #pragma unroll
-            for (int g = 0; g < GP; g += 4) {
-                const f32x4 t4 = *(const f32x4*)(pr + g);
-                pg[g] = t4[0]; pg[g + 1] = t4[1]; pg[g + 2] = t4[2]; pg[g + 3] = t4[3];
-            }
-        } else {
-#pragma unroll
-            for (int g = 0; g < GP; ++g) pg[g] = pr[g];
-        }
-        float v8[8];
-        v_unpack(vf[i], v8);
-#pragma unroll
-        for (int j2 = 0; j2 < 4; ++j2) {
-            const float v0 = v8[2 * j2], v1 = v8[2 * j2 + 1];
-#pragma unroll
-            for (int g = 0; g < GP; ++g) {
-                acc[g][2 * j2] = fmaf(pg[g], v0, acc[g][2 * j2]);
-                acc[g][2 * j2 + 1] = fmaf(pg[g], v1, acc[g][2 * j2 + 1]);
-            }
-        }
-    }
-    // fold the four key classes (lanes l, l ^ 16, l ^ 32, l ^ 48): each exchange halves the query rows a lane keeps
-    const bool hi32 = (lane & 32) != 0, hi16 = (lane & 16) != 0;
-    constexpr int G1 = GP >= 2 ? GP / 2 : GP, G2 = GP >= 4 ? GP / 4 : G1;
-    float a1[G1][8], a2[G2][8];
-#pragma unroll
-    for (int g = 0; g < G1; ++g)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if constexpr (GP >= 2) {
-                const float keep = hi32 ? acc[g + G1][j] : acc[g][j], send = hi32 ? acc[g][j] : acc[g + G1][j];
-                a1[g][j] = keep + __shfl_xor(send, 32, 64);
+                for (int g = 0; g < GA; g += 4) {
+                    const f32x4 t4 = *(const f32x4*)(pr + g);
+                    pg[g] = t4[0]; pg[g + 1] = t4[1]; pg[g + 2] = t4[2]; pg[g + 3] = t4[3];
+                }
             } else {
-                a1[g][j] = acc[g][j] + __shfl_xor(acc[g][j], 32, 64);
+#pragma unroll
+                for (int g = 0; g < GA; ++g) pg[g] = pr[g];
+            }
+            float v8[8];
+            if constexpr (GP > GA) {                       // a second pass: keep the fp32 copy of V (128 registers) from being hoisted out of the pass
+                if constexpr (KV8) asm volatile("" : "+v"(vf[i].x), "+v"(vf[i].y));
+                else asm volatile("" : "+v"(vf[i].x), "+v"(vf[i].y), "+v"(vf[i].z), "+v"(vf[i].w));
+            }
+            v_unpack(vf[i], v8);
+#pragma unroll
+            for (int j2 = 0; j2 < 4; ++j2) {
+                const float v0 = v8[2 * j2], v1 = v8[2 * j2 + 1];
+#pragma unroll
+                for (int g = 0; g < GA; ++g) {
+                    acc[g][2 * j2] = fmaf(pg[g], v0, acc[g][2 * j2]);
+                    acc[g][2 * j2 + 1] = fmaf(pg[g], v1, acc[g][2 * j2 + 1]);
+                }
             }
         }
+        // fold the four key classes (lanes l, l ^ 16, l ^ 32, l ^ 48): each exchange halves the query rows a lane keeps
+        const bool hi32 = (lane & 32) != 0, hi16 = (lane & 16) != 0;
+        constexpr int G1 = GA >= 2 ? GA / 2 : GA, G2 = GA >= 4 ? GA / 4 : G1;
+        float a1[G1][8], a2[G2][8];
 #pragma unroll
-    for (int g = 0; g < G2; ++g)
+        for (int g = 0; g < G1; ++g)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if constexpr (GP >= 4) {
-                const float keep = hi16 ? a1[g + G2][j] : a1[g][j], send = hi16 ? a1[g][j] : a1[g + G2][j];
-                a2[g][j] = keep + __shfl_xor(send, 16, 64);
-            } else {
-                a2[g][j] = a1[g][j] + __shfl_xor(a1[g][j], 16, 64);
+            for (int j = 0; j < 8; ++j) {
+                if constexpr (GA >= 2) {
+                    const float keep = hi32 ? acc[g + G1][j] : acc[g][j], send = hi32 ? acc[g][j] : acc[g + G1][j];
+                    a1[g][j] = keep + __shfl_xor(send, 32, 64);
+                } else {
+                    a1[g][j] = acc[g][j] + __shfl_xor(acc[g][j], 32, 64);
+                }
             }
+#pragma unroll
+        for (int g = 0; g < G2; ++g)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                if constexpr (GA >= 4) {
+                    const float keep = hi16 ? a1[g + G2][j] : a1[g][j], send = hi16 ? a1[g][j] : a1[g + G2][j];
+                    a2[g][j] = keep + __shfl_xor(send, 16, 64);
+                } else {
+                    a2[g][j] = a1[g][j] + __shfl_xor(a1[g][j], 16, 64);
+                }
+            }
+        {
+            // query rows (of this pass) this lane now holds: GA >= 4: (hi32 ? G1 : 0) + (hi16 ? G2 : 0) + g;  GA == 2: hi32 (both lanes of an
+            // xor-16 pair hold the same sums: one writes);  GA == 1: row 0 on every lane (lanes 0..15 write)
+            const int gbase = h0 + (GA >= 2 && hi32 ? G1 : 0) + (GA >= 4 && hi16 ? G2 : 0);
+            const bool writer = GA >= 4 ? true : (GA == 2 ? !hi16 : lane < 16);
+            if (writer)
+#pragma unroll
+                for (int g = 0; g < G2; ++g) {
+                    float* dst = &s_red[wave][gbase + g][8 * c16];
+                    *(f32x4*)dst = f32x4{a2[g][0], a2[g][1], a2[g][2], a2[g][3]};
+                    *(f32x4*)(dst + 4) = f32x4{a2[g][4], a2[g][5], a2[g][6], a2[g][7]};
+                }
         }
-    {
-        // query rows this lane now holds: GP >= 4: (hi32 ? G1 : 0) + (hi16 ? G2 : 0) + g;  GP == 2: hi32 (both lanes of an
-        // xor-16 pair hold the same sums: one writes);  GP == 1: row 0 on every lane (lanes 0..15 write)
-        const int gbase = (GP >= 2 && hi32 ? G1 : 0) + (GP >= 4 && hi16 ? G2 : 0);
-        const bool writer = GP >= 4 ? true : (GP == 2 ? !hi16 : lane < 16);
-        if (writer)
-#pragma unroll
-            for (int g = 0; g < G2; ++g) {
-                float* dst = &s_red[wave][gbase + g][8 * c16];
-                *(f32x4*)dst = f32x4{a2[g][0], a2[g][1], a2[g][2], a2[g][3]};
-                *(f32x4*)(dst + 4) = f32x4{a2[g][4], a2[g][5], a2[g][6], a2[g][7]};
-            }
     }
     __syncthreads();
 
     // the block's result: thread t < 32 GP sums the four waves for query row t / 32, columns 4 (t % 32) .. + 3
-    const int tg = threadIdx.x >> 5, d4 = threadIdx.x & 31;
-    if (tg < G) {
+    // (16 rows: two rounds).  ROWS: row tg is query row tg / G of head hk G + tg % G; lse and the workspace are [b][h][seq_q]
+    const int d4 = threadIdx.x & 31;
+#pragma unroll
+    for (int t0 = 0; t0 < GP; t0 += 8) {
+        const int tg = t0 + (threadIdx.x >> 5);
+        if (tg >= R) continue;
         f32x4 o = *(const f32x4*)&s_red[0][tg][4 * d4];
 #pragma unroll
         for (int w = 1; w < 4; ++w) o += *(const f32x4*)&s_red[w][tg][4 * d4];
         const float m = fmaxf(fmaxf(s_m[0][tg], s_m[1][tg]), fmaxf(s_m[2][tg], s_m[3][tg]));
         const float l = ((s_l[0][tg] + s_l[1][tg]) + s_l[2][tg]) + s_l[3][tg];
-        const int h = hk * G + tg;
+        const int j = ROWS ? tg / G : 0, h = hk * G + (ROWS ? tg % G : tg);
+        const long row = ROWS ? ((long)b * p.Hq + h) * p.Sq + j : (long)b * p.Hq + h;
         if (nch == 1) {
             u16x4 ob;
 #pragma unroll
             for (int e = 0; e < 4; ++e) ob[e] = f2bf(l > 0.f ? o[e] / l : 0.f);
-            *(u16x4*)(p.O + (long)b * p.o_bs + (long)h * 128 + 4 * d4) = ob;
-            if (p.lse && d4 == 0) p.lse[(long)b * p.Hq + h] = l > 0.f ? m + log2f(l) : INFINITY;
+            *(u16x4*)(p.O + (long)b * p.o_bs + (ROWS ? (long)j * p.o_rs : 0) + (long)h * 128 + 4 * d4) = ob;
+            if (p.lse && d4 == 0) p.lse[row] = l > 0.f ? m + log2f(l) : INFINITY;
         } else {
-            const long r = ((long)b * p.Hq + h) * nch + c;
+            const long r = row * nch + c;
             *(f32x4*)(ws_o + r * 128 + 4 * d4) = o;
             if (d4 == 0) { ws_ml[2 * r] = m; ws_ml[2 * r + 1] = l; }
         }
     }
+}
+// seq_q = w rows per sequence (a verify step of draft-and-verify decoding): the same items, the K / V of an item loaded once
+// for all R = G w rows.  RP: R rounded up to 2, 4, 8, 16
+template <int RP>
+__global__ __launch_bounds__(256, 2) void attn_verify_k(AttnArgs p, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
+    attn_decode_body<RP, false, true>(p, nullptr, nullptr, 0, 0, ws_ml, ws_o, nch);
+}
+template <int RP>
+__global__ __launch_bounds__(256, 2) void attn_verify_kv8_k(AttnArgs p, const float* __restrict__ k_scale, const float* __restrict__ v_scale, long sc_bs,
+                                                         long sc_rs, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
+    attn_decode_body<RP, true, true>(p, k_scale, v_scale, sc_bs, sc_rs, ws_ml, ws_o, nch);
 }
 template <int GP>
 __global__ __launch_bounds__(256) void attn_decode_k(AttnArgs p, float* __restrict__ ws_ml, float* __restrict__ ws_o, int nch) {
@@ -1776,10 +1817,12 @@ __global__ __launch_bounds__(256) void attn_kv8_k(AttnArgs p, const float* __res
 }
 
 // Merge of a row's chunk partials, chunks in ascending order, fp32.  32 threads per (batch, query head), 8 heads per block.
-__global__ __launch_bounds__(256) void attn_decode_combine_k(AttnArgs p, const float* __restrict__ ws_ml, const float* __restrict__ ws_o, int nch) {
+// ROWS: per (batch, query head, query row); a chunk that is empty for this row alone is skipped like any empty chunk.
+template <bool ROWS>
+__device__ __forceinline__ void attn_combine_body(const AttnArgs& p, const float* __restrict__ ws_ml, const float* __restrict__ ws_o, int nch) {
     const long bh = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
     const int d4 = threadIdx.x & 31;
-    if (bh >= (long)p.B * p.Hq) return;
+    if (bh >= (long)p.B * p.Hq * (ROWS ? p.Sq : 1)) return;
     const float* ml = ws_ml + 2 * bh * nch;
     const float* po = ws_o + bh * nch * 128 + 4 * d4;
     float m = -INFINITY;
@@ -1795,12 +1838,19 @@ __global__ __launch_bounds__(256) void attn_decode_combine_k(AttnArgs p, const f
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = fmaf(w, oc[e], o[e]);
     }
-    const int b = (int)(bh / p.Hq), h = (int)(bh % p.Hq);
+    const long bhh = ROWS ? bh / p.Sq : bh;
+    const int b = (int)(bhh / p.Hq), h = (int)(bhh % p.Hq), j = ROWS ? (int)(bh % p.Sq) : 0;
     u16x4 ob;
 #pragma unroll
     for (int e = 0; e < 4; ++e) ob[e] = f2bf(l > 0.f ? o[e] / l : 0.f);
-    *(u16x4*)(p.O + (long)b * p.o_bs + (long)h * 128 + 4 * d4) = ob;
+    *(u16x4*)(p.O + (long)b * p.o_bs + (ROWS ? (long)j * p.o_rs : 0) + (long)h * 128 + 4 * d4) = ob;
     if (p.lse && d4 == 0) p.lse[bh] = l > 0.f ? m + log2f(l) : INFINITY;
+}
+__global__ __launch_bounds__(256) void attn_decode_combine_k(AttnArgs p, const float* __restrict__ ws_ml, const float* __restrict__ ws_o, int nch) {
+    attn_combine_body<false>(p, ws_ml, ws_o, nch);
+}
+__global__ __launch_bounds__(256) void attn_verify_combine_k(AttnArgs p, const float* __restrict__ ws_ml, const float* __restrict__ ws_o, int nch) {
+    attn_combine_body<true>(p, ws_ml, ws_o, nch);
 }
 
 int fill_args(const desta_attn_desc* d, AttnArgs& a) {
@@ -1903,13 +1953,25 @@ extern "C" size_t desta_attention_decode_workspace_bytes(int batch, int n_q_head
     return (decode_ml_floats(items) + items * (size_t)head_dim) * sizeof(float);
 }
 
-// Both decode entry points: `who` prefixes every message; k_scale != NULL selects the FP8-cache kernel.
-static int decode_launch(const char* who, const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t sbs, int64_t srs,
+extern "C" size_t desta_attention_verify_workspace_bytes(int batch, int n_q_heads, int seq_q, int seq_k, int head_dim) {
+    if (n_q_heads <= 0 || seq_q <= 0 || (long)n_q_heads * seq_q > 0x7fffffffL) return 0;
+    return desta_attention_decode_workspace_bytes(batch, n_q_heads * seq_q, seq_k, head_dim);     // one partial per (row, head, query row, chunk)
+}
+
+// The decode and verify entry points: `who` prefixes every message; k_scale != NULL selects the FP8-cache kernel; rows: the
+// verify kernels (seq_q = 2..8 query rows per sequence under the causal mask) instead of the one-row ones.
+static int decode_launch(const char* who, bool rows, const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t sbs, int64_t srs,
                          void* workspace, size_t workspace_bytes, void* stream) {
     DESTA_CHECK_ARG(d, "%s: null descriptor", who);
-    DESTA_CHECK_ARG(d->seq_q == 1, "%s: seq_q %d unsupported (one query row per sequence)", who, d->seq_q);
+    if (rows) {
+        DESTA_CHECK_ARG(d->seq_q >= 2 && d->seq_q <= DESTA_ATTN_VERIFY_MAX_SEQ_Q, "%s: seq_q %d unsupported (2..%d query rows per sequence)", who,
+                        d->seq_q, DESTA_ATTN_VERIFY_MAX_SEQ_Q);
+        DESTA_CHECK_ARG(d->causal, "%s: causal must be 1 (query row j sees keys [kv_start, j + seq_k - seq_q])", who);
+    } else {
+        DESTA_CHECK_ARG(d->seq_q == 1, "%s: seq_q %d unsupported (one query row per sequence)", who, d->seq_q);
+        DESTA_CHECK_ARG(!d->causal, "%s: causal must be 0 (the one query row sees every key of [kv_start, seq_k))", who);
+    }
     DESTA_CHECK_ARG(d->head_dim == 128, "%s: head_dim %d unsupported (128)", who, d->head_dim);
-    DESTA_CHECK_ARG(!d->causal, "%s: causal must be 0 (the one query row sees every key of [kv_start, seq_k))", who);
     DESTA_CHECK_ARG(d->dropout_p == 0.f, "%s: dropout_p must be 0", who);
     DESTA_CHECK_ARG(!d->rope_cos_sin, "%s: rope_cos_sin must be NULL", who);
     DESTA_CHECK_ARG(!d->O_f32, "%s: O_f32 must be NULL", who);
@@ -1918,18 +1980,21 @@ static int decode_launch(const char* who, const desta_attn_desc* d, const float*
     if (int rc = fill_args(d, a)) return rc;
     const int G = a.Hq / a.Hkv;
     DESTA_CHECK_ARG(G <= 8, "%s: group of %d query heads per kv head unsupported (at most 8)", who, G);
-    DESTA_CHECK_ARG(d->O && ((size_t)d->O & 15) == 0 && d->o_batch_stride % 8 == 0,
-                    "%s: O must be 16-byte aligned with a batch stride that is a multiple of 8 elements", who);
+    const int R = G * a.Sq;
+    DESTA_CHECK_ARG(R <= DESTA_ATTN_VERIFY_MAX_ROWS, "%s: group %d x seq_q %d = %d query rows per kv head unsupported (at most %d)", who, G, a.Sq, R,
+                    DESTA_ATTN_VERIFY_MAX_ROWS);
+    DESTA_CHECK_ARG(d->O && ((size_t)d->O & 15) == 0 && d->o_batch_stride % 8 == 0 && (!rows || d->o_row_stride % 8 == 0),
+                    "%s: O must be 16-byte aligned with batch and row strides that are multiples of 8 elements", who);
     DESTA_CHECK_ARG((((size_t)d->Q | (size_t)d->K | (size_t)d->V) & 15) == 0 && d->q_batch_stride % 8 == 0 &&
                     d->k_batch_stride % 8 == 0 && d->v_batch_stride % 8 == 0,
                     "%s: Q, K, V must be 16-byte aligned with batch strides that are multiples of 8 elements", who);
     const int nch = (a.Sk + DESTA_ATTN_DECODE_CHUNK - 1) / DESTA_ATTN_DECODE_CHUNK;
-    const size_t need = desta_attention_decode_workspace_bytes(a.B, a.Hq, a.Sk, 128);
+    const size_t need = desta_attention_verify_workspace_bytes(a.B, a.Hq, a.Sq, a.Sk, 128);
     DESTA_CHECK_ARG(need == 0 || (workspace && workspace_bytes >= need && ((size_t)workspace & 15) == 0),
                     "%s: workspace of %zu bytes is too small or misaligned (%zu needed, 16-byte aligned)", who, workspace_bytes, need);
     DESTA_CHECK_ARG((long)a.B * a.Hkv * nch <= 0x7fffffffL, "%s: grid too large", who);
     float* ws_ml = (float*)workspace;
-    float* ws_o = ws_ml ? ws_ml + decode_ml_floats((size_t)a.B * a.Hq * nch) : nullptr;
+    float* ws_o = ws_ml ? ws_ml + decode_ml_floats((size_t)a.B * a.Hq * a.Sq * nch) : nullptr;
     const dim3 grid((unsigned)(a.B * a.Hkv * nch));
     hipStream_t st = (hipStream_t)stream;
 #define DECODE_LAUNCH(GP)                                                                                                               \
@@ -1937,28 +2002,52 @@ static int decode_launch(const char* who, const desta_attn_desc* d, const float*
         if (k_scale) hipLaunchKernelGGL((attn_kv8_k<GP>), grid, dim3(256), 0, st, a, k_scale, v_scale, (long)sbs, (long)srs, ws_ml, ws_o, nch); \
         else hipLaunchKernelGGL((attn_decode_k<GP>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);                                      \
     } while (0)
-    if (G == 1) DECODE_LAUNCH(1);
+#define VERIFY_LAUNCH(RP)                                                                                                               \
+    do {                                                                                                                                \
+        if (k_scale) hipLaunchKernelGGL((attn_verify_kv8_k<RP>), grid, dim3(256), 0, st, a, k_scale, v_scale, (long)sbs, (long)srs, ws_ml, ws_o, nch); \
+        else hipLaunchKernelGGL((attn_verify_k<RP>), grid, dim3(256), 0, st, a, ws_ml, ws_o, nch);                                      \
+    } while (0)
+    if (rows) {
+        if (R <= 2) VERIFY_LAUNCH(2);
+        else if (R <= 4) VERIFY_LAUNCH(4);
+        else if (R <= 8) VERIFY_LAUNCH(8);
+        else VERIFY_LAUNCH(16);
+    } else if (G == 1) DECODE_LAUNCH(1);
     else if (G == 2) DECODE_LAUNCH(2);
     else if (G <= 4) DECODE_LAUNCH(4);
     else DECODE_LAUNCH(8);
+#undef VERIFY_LAUNCH
 #undef DECODE_LAUNCH
     DESTA_CHECK_LAUNCH(who);
     if (nch > 1) {
-        hipLaunchKernelGGL(attn_decode_combine_k, dim3((unsigned)((a.B * a.Hq + 7) / 8)), dim3(256), 0, st, a, ws_ml, ws_o, nch);
-        DESTA_CHECK_LAUNCH(k_scale ? "attention_decode_kv8 (combine)" : "attention_decode (combine)");
+        const dim3 cgrid((unsigned)(((long)a.B * a.Hq * a.Sq + 7) / 8));
+        if (rows) hipLaunchKernelGGL(attn_verify_combine_k, cgrid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
+        else hipLaunchKernelGGL(attn_decode_combine_k, cgrid, dim3(256), 0, st, a, ws_ml, ws_o, nch);
+        DESTA_CHECK_LAUNCH(who);
     }
     return DESTA_OK;
 }
 
 extern "C" int desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-    return decode_launch("attention_decode", d, nullptr, nullptr, 0, 0, workspace, workspace_bytes, stream);
+    return decode_launch("attention_decode", false, d, nullptr, nullptr, 0, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int desta_attention_decode_kv8(const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t scale_batch_stride,
                                           int64_t scale_row_stride, void* workspace, size_t workspace_bytes, void* stream) {
     DESTA_CHECK_ARG(d, "attention_decode_kv8: null descriptor");
     DESTA_CHECK_ARG(k_scale && v_scale && scale_batch_stride >= 0 && scale_row_stride > 0, "attention_decode_kv8: null scale or bad scale stride");
-    return decode_launch("attention_decode_kv8", d, k_scale, v_scale, scale_batch_stride, scale_row_stride, workspace, workspace_bytes, stream);
+    return decode_launch("attention_decode_kv8", false, d, k_scale, v_scale, scale_batch_stride, scale_row_stride, workspace, workspace_bytes, stream);
+}
+
+extern "C" int desta_attention_verify(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+    return decode_launch("attention_verify", true, d, nullptr, nullptr, 0, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int desta_attention_verify_kv8(const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t scale_batch_stride,
+                                          int64_t scale_row_stride, void* workspace, size_t workspace_bytes, void* stream) {
+    DESTA_CHECK_ARG(d, "attention_verify_kv8: null descriptor");
+    DESTA_CHECK_ARG(k_scale && v_scale && scale_batch_stride >= 0 && scale_row_stride > 0, "attention_verify_kv8: null scale or bad scale stride");
+    return decode_launch("attention_verify_kv8", true, d, k_scale, v_scale, scale_batch_stride, scale_row_stride, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------- FP8 KV cache -> bf16 staging slab (chunked prompt pass)

@@ -690,6 +690,35 @@ def attention_decode_kv8(d: AttnDesc, k_scale, v_scale, scale_bs, scale_rs, ws=N
     ATTN_KV8_CALLS += 1
 
 
+# The split-KV kernels at seq_q = w = 2..8 query rows per sequence under the causal mask (a verify step of draft-and-verify
+# decoding): K / V once for all G * w <= VERIFY_ATTN_MAX_ROWS rows of a KV head; row j is attention_decode{,_kv8}'s result at
+# seq_k - (w - 1 - j) keys, bit for bit (include/desta_hip.h).
+lib.desta_attention_verify_workspace_bytes.restype = c_size_t
+lib.desta_attention_verify_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+_attn_verify = _sig("desta_attention_verify", C.POINTER(AttnDesc), vp, c_size_t, vp)
+_attn_verify_kv8 = _sig("desta_attention_verify_kv8", C.POINTER(AttnDesc), vp, vp, i64, i64, vp, c_size_t, vp)
+VERIFY_ATTN_MAX_ROWS = 16          # query rows per KV head (DESTA_ATTN_VERIFY_MAX_ROWS): the B columns of the score MFMA
+
+
+def attention_verify_workspace_bytes(batch: int, hq: int, sq: int, sk: int, hd: int = 128) -> int:
+    """Bytes of fp32 workspace `attention_verify{,_kv8}` need for this shape (0 while sk fits one chunk)."""
+    return int(lib.desta_attention_verify_workspace_bytes(int(batch), int(hq), int(sq), int(sk), int(hd)))
+
+
+@_profiled(lambda d, *a, **k: "attn_verify:" + _attn_tag(d), lambda d, *a, **k: _attn_flops(d, 1.0))
+def attention_verify(d: AttnDesc, ws=None):
+    """The attention of one verify step (d.seq_q = 2..8, d.causal) on the split-KV kernel; `ws`: a device buffer of at least
+    `attention_verify_workspace_bytes` bytes (None while d.seq_k <= DECODE_ATTN_CHUNK).  Unsupported descriptors raise."""
+    check(_attn_verify(C.byref(d), p(ws), 0 if ws is None else ws.numel() * ws.element_size(), stream()), "desta_attention_verify")
+
+
+@_profiled(lambda d, *a, **k: "attn_verify_kv8:" + _attn_tag(d), lambda d, *a, **k: _attn_flops(d, 1.0))
+def attention_verify_kv8(d: AttnDesc, k_scale, v_scale, scale_bs, scale_rs, ws=None):
+    """attention_verify on an FP8 cache; the scale arguments of `attention_decode_kv8`, `ws` as for attention_verify."""
+    check(_attn_verify_kv8(C.byref(d), p(k_scale), p(v_scale), int(scale_bs), int(scale_rs), p(ws),
+                           0 if ws is None else ws.numel() * ws.element_size(), stream()), "desta_attention_verify_kv8")
+
+
 # One layer of the FP8 cache back as bf16 for the attention of a prompt chunk (`CausalLMHIP.prefill`; include/desta_hip.h).
 _kv8_dequant = _sig("desta_kv8_dequant", vp, i64, i64, vp, i64, i64, vp, i32, i32, i32, i32, vp, i64, i64, vp)
 KV8_DEQUANT_CALLS = 0              # FP8-cache dequantisations issued by this process

@@ -479,6 +479,15 @@ def check_speculative_arg(k) -> None:
 SPECULATIVE_SCOPES = ("greedy", "all")              # which generate() calls `set_speculative` covers
 
 
+SPECULATIVE_ATTENTIONS = ("forward", "split")       # which kernel a verify step of `set_speculative` attends through
+
+
+def check_speculative_attention(attention) -> None:
+    """`set_speculative(k, attention=...)`: "forward" (the causal forward kernel) or "split" (the split-KV verify kernels)."""
+    if attention not in SPECULATIVE_ATTENTIONS:
+        raise ValueError(f"speculative attention must be one of {SPECULATIVE_ATTENTIONS}, got {attention!r}")
+
+
 def check_speculative_scope(scope) -> None:
     """`set_speculative(k, scope=...)`: "greedy" (plain greedy calls only) or "all" (sampling, repetition penalty, logprobs too)."""
     if not isinstance(scope, str) or scope not in SPECULATIVE_SCOPES:
@@ -1606,10 +1615,11 @@ class CausalLMHIP:
         self.kv_stage = self._pf = None
         self.speculative = None                     # `set_speculative`: draft tokens per verify step of greedy generate(); None = one token per step
         self.spec_scope = "greedy"                  # `set_speculative(k, scope=...)`: "greedy" = plain greedy calls only, "all" = sampling, penalty and logprobs too
+        self.spec_attention = "forward"             # `set_speculative(k, attention=...)`: "forward" = the causal forward kernel, "split" = `H.attention_verify{,_kv8}`
         self._step1 = self._spec = None             # `_step_alloc` sets of the plain step (`_gen_alloc`) and of the verify step (`_spec_alloc`)
         self.spec_stats = None
 
-    def set_speculative(self, k: Optional[int], scope: str = "greedy") -> None:
+    def set_speculative(self, k: Optional[int], scope: str = "greedy", attention: str = "forward") -> None:
         """generate(): None or 0 (default) = one token per sequence per pass over the weights; an int k in 1..7 = draft and
         verify: k tokens proposed by looking the row's last tokens up in its own prompt and output (`H.spec_ngram_draft`), all k + 1
         rows per sequence checked by ONE pass (`verify_step`: the step body of `decode_step`, `_step_rows`, at width k + 1), and
@@ -1621,15 +1631,25 @@ class CausalLMHIP:
         the token is the sampler's own draw from the logits of the accepted prefix and a draft is accepted exactly when the draw
         hits it: the plain loop's sampled tokens, with no rejection-resampling rule.  `logprobs` costs one `H.topk_logprobs` launch
         over all rows per verify step.
-        Under both scopes `forced_tokens`, a `layer_hook` (ORCA), the FP8 KV cache and B * (k + 1) > H.DECODE_MAX_ROWS run the plain
-        loop; `spec_stats` says which ran and why."""
+        attention = "forward" (default): a verify step attends through the causal forward kernel at seq_q = k + 1, one block per
+        query head walking the whole cache.  attention = "split": through the split-KV verify kernels (`H.attention_verify`,
+        `H.attention_verify_kv8`: K / V once for all G (k + 1) query rows of a KV head, a row's 256-key chunks on different CUs).
+        On the bf16 cache iff head_dim is 128, G <= 8, G (k + 1) <= H.VERIFY_ATTN_MAX_ROWS and cur + 1 >= H.DECODE_ATTN_MIN_KEYS, the
+        plain loop's own rule at the step's first row (the forward kernel otherwise); row j of that kernel is the plain step's
+        split-KV result at slot cur + j bit for bit, so from that slot on both loops run one attention arithmetic.  On the FP8 KV
+        cache, where only "split" speculates, at every cur.
+        Under both scopes `forced_tokens`, a `layer_hook` (ORCA), B * (k + 1) > H.DECODE_MAX_ROWS and the FP8 KV cache (with
+        attention = "forward", or with more than H.VERIFY_ATTN_MAX_ROWS query rows per KV head) run the plain loop; `spec_stats`
+        says which ran and why."""
         check_speculative_arg(k)
         check_speculative_scope(scope)
+        check_speculative_attention(attention)
         k = k or None
-        if k != self.speculative:                                            # the verify buffers go with k, not with the scope
+        if k != self.speculative:                                            # the verify buffers go with k, not with the scope or the attention
             self._spec = None
         self.speculative = k
         self.spec_scope = scope
+        self.spec_attention = attention
 
     def set_prefill_chunk(self, n: Optional[int]) -> None:
         """Prompt pass of generate(): None (default) = the training `forward` with its per-layer save set; an int >= 16 = the
@@ -1673,7 +1693,9 @@ class CausalLMHIP:
         """What generate()'s KV cache holds: "bf16" (default, the reference's arithmetic) or "fp8" = OCP e4m3 bytes, quantised
         per head where a token is appended and dequantised in registers where the decode attention reads it (0.516 of the bf16
         bytes).  The prompt pass's own attention reads the bf16 q|k|v projection either way, so prompt logits do not depend on
-        the kind.  "fp8" needs the split-KV decode kernel's geometry: head_dim 128 and at most 8 query heads per KV head."""
+        the kind.  "fp8" needs the split-KV decode kernel's geometry: head_dim 128 and at most 8 query heads per KV head.  With
+        `set_speculative(k)` the FP8 cache speculates only under `attention="split"` and G (k + 1) <= H.VERIFY_ATTN_MAX_ROWS query rows
+        per KV head (the verify kernel that reads the bytes); otherwise the plain loop runs and `spec_stats` says why."""
         if kind not in self.KV_CACHE_KINDS:
             raise ValueError(f"kv_cache must be one of {self.KV_CACHE_KINDS}, got {kind!r}")
         if kind == "fp8" and (self.hd != 128 or self.hq // self.hkv > 8):
@@ -2080,8 +2102,10 @@ class CausalLMHIP:
         every M; else M > 16: `gemm_wide`, else `gemm_w8` on FP8 decode weights, else `gemm`; the LoRA-merged q|k|v stays on `gemm`) and the RMSNorm fusion (`H.rms_fusable`); the
         rotated K | V go to slots [cur, cur + w) of the cache.  w picks the attention alone: w = 1 reads slots [kv_start, cur] without
         a mask, through the kv8 kernel under the FP8 cache, the split-KV kernel from H.DECODE_ATTN_MIN_KEYS keys on where the
-        geometry allows, else the forward kernel; w > 1 (bf16 cache) reads slots [kv_start, cur + w) through the forward kernel under
-        the causal mask, the descriptor of `prefill`.  `layer_hook(l, x)` runs behind every layer on the step's rows [M, h]."""
+        geometry allows, else the forward kernel; w > 1 reads slots [kv_start, cur + w) under the causal mask, the descriptor of
+        `prefill`: through the forward kernel (bf16 cache), or with `set_speculative(attention="split")` through the split-KV verify
+        kernels, on the bf16 cache by the w = 1 rule at `cur` where G w <= H.VERIFY_ATTN_MAX_ROWS, on the FP8 cache always.
+        `layer_hook(l, x)` runs behind every layer on the step's rows [M, h]."""
         h, aw, eps = self.h, self.hq * self.hd, self.c.rms_norm_eps
         B, w = tokens.shape
         M = B * w
@@ -2116,10 +2140,15 @@ class CausalLMHIP:
                 H.rmsnorm_fwd(xin, nw, eps, hb, r)
                 mm(hb, w_, w8, out, N, h, **kw)
         # long caches: split-KV kernel (K / V once per GQA group, a row's chunks on different CUs); a rule of the shape alone
-        split_kv = w == 1 and self.hd == 128 and self.hq // self.hkv <= 8 and cur + 1 >= H.DECODE_ATTN_MIN_KEYS
-        kv8 = self._gen_kind == "fp8"                   # FP8 cache: the kv8 kernel at every cur (the forward kernel cannot read bytes)
-        one = dict(q_bs=self.qkvw, o_bs=aw) if w == 1 else {}
+        G = self.hq // self.hkv
+        split_kv = self.hd == 128 and G <= 8 and cur + 1 >= H.DECODE_ATTN_MIN_KEYS
+        if w > 1:                                       # the plain loop's rule at the step's first row, where the rows fit the MFMA's columns
+            split_kv = split_kv and self.spec_attention == "split" and G * w <= H.VERIFY_ATTN_MAX_ROWS
+        kv8 = self._gen_kind == "fp8"                   # FP8 cache: the kv8 kernels at every cur (the forward kernel cannot read bytes)
+        ws = self.g_attn_ws if w == 1 else bufs.get("attn_ws")
         Smax = self._gen_shape[1]
+        sc_bs, sc_rs = Smax * 2 * self.hkv, 2 * self.hkv
+        one = dict(q_bs=self.qkvw, o_bs=aw) if w == 1 else {}
         for li, (ly, cache) in enumerate(zip(self.layers, self.kv_cache)):
             q8 = ly["q4"] if mx else ly["q8"] if fp8 else {}
             if self.lora is None:
@@ -2129,9 +2158,9 @@ class CausalLMHIP:
             self._kv_append(li, ly, qkv, M, w, shift, cur)                   # rotate q,k + append K|V at slots [cur, cur + w)
             ad = self._cache_attn_desc(qkv, cache, att, lse, B, w, cur + w, w > 1, kv_start, **one)
             if kv8:
-                H.attention_decode_kv8(ad, self.kv_scale[li], self.kv_scale_v[li], Smax * 2 * self.hkv, 2 * self.hkv, self.g_attn_ws)
+                (H.attention_decode_kv8 if w == 1 else H.attention_verify_kv8)(ad, self.kv_scale[li], self.kv_scale_v[li], sc_bs, sc_rs, ws)
             elif split_kv:
-                H.attention_decode(ad, self.g_attn_ws)
+                (H.attention_decode if w == 1 else H.attention_verify)(ad, ws)
             else:
                 H.attention_fwd(ad)
             mm(att, ly["wo"], q8.get("wo"), xm, h, aw, residual=x)
@@ -2142,6 +2171,12 @@ class CausalLMHIP:
         proj(x, self.norm, self.head, self.head4 if mx else self.head8 if fp8 else None, logits, self.V, ldc=self.Vp)
         return logits
 
+    def _verify_attn_rows(self, k: int) -> bool:
+        """Whether the split-KV verify kernels take this geometry at k drafts: head_dim 128, G <= 8, G (k + 1) query rows per KV head
+        within the score MFMA's 16 columns."""
+        G = self.hq // self.hkv
+        return self.hd == 128 and G <= 8 and G * (k + 1) <= H.VERIFY_ATTN_MAX_ROWS
+
     def decode_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor, layer_hook=None) -> torch.Tensor:
         """One token per sequence: `tokens` [B] (ids) sit at cache slot `cur`; returns logits [B, Vp] for slot cur+1.  `_step_rows`
         at w = 1."""
@@ -2149,9 +2184,16 @@ class CausalLMHIP:
 
     # -- draft-and-verify greedy decoding (`set_speculative`): k + 1 rows per sequence through one pass over the weights ---------
     def _spec_alloc(self, B: int, k: int) -> dict:
-        """The `_step_alloc` set of `verify_step` for B * (k + 1) rows, and the loop's integer state."""
+        """The `_step_alloc` set of `verify_step` for B * (k + 1) rows, and the loop's integer state.  With
+        `set_speculative(attention="split")` the set also holds `attn_ws`, the fp32 chunk partials of the split-KV verify attention
+        for B * Hq * (k + 1) rows at the longest cache (None while that fits one chunk, or where the kernel does not take the
+        geometry); it is made when first needed, so changing the attention alone keeps the set."""
         sp = self._spec
         if sp is not None and sp["key"] == (B, k):
+            if self.spec_attention == "split" and sp.get("attn_ws_smax") != self._gen_shape[1]:
+                ws = H.attention_verify_workspace_bytes(B, self.hq, k + 1, self._gen_shape[1], self.hd) if self._verify_attn_rows(k) else 0
+                sp["attn_ws"] = None                                         # free the old one before the new one is made
+                sp["attn_ws"], sp["attn_ws_smax"] = (torch.empty(ws // 4, dtype=F32, device=self.dev) if ws else None), self._gen_shape[1]
             return sp
         self._spec = sp = None                                               # free the old set before the new one is made
         dev, w = self.dev, k + 1
@@ -2161,23 +2203,26 @@ class CausalLMHIP:
         self._spec = sp = dict(key=(B, k), **self._step_alloc(B, w), pred=i64(B, w), inp=i64(B, w), draft=i64(B, k),
                                taken=torch.zeros(1, dtype=torch.int32, device=dev), taken_host=torch.zeros(1, dtype=torch.int32).pin_memory(),
                                event=torch.cuda.Event())
-        return sp
+        return self._spec_alloc(B, k)
 
     def verify_step(self, tokens: torch.Tensor, cur: int, kv_start: torch.Tensor) -> torch.Tensor:
         """k + 1 tokens per sequence in one pass: `tokens` [B, k + 1] (ids >= 0; column 0 the last emitted token, columns 1..k the
         drafts), row j of a sequence sits at cache slot cur + j.  Returns logits [B * (k + 1), Vp] (batch-major): row j predicts
         slot cur + j + 1 GIVEN the chunk's tokens in front of it.  `_step_rows` at w = k + 1: `decode_step`'s body over
-        M = B * (k + 1) rows (at most H.DECODE_MAX_ROWS) of the bf16 cache, with the causal forward-kernel attention over slots
-        [kv_start, cur + k].  Only slots in front of the next step's `cur` are ever trusted: the slots at or behind it
-        hold drafts that were not accepted, and the next chunk rewrites them (its slot0 is the new `cur`, its width k + 1) before
+        M = B * (k + 1) rows (at most H.DECODE_MAX_ROWS), with the causal attention over slots [kv_start, cur + k] (the forward
+        kernel, or the split-KV verify kernels: `set_speculative(attention=...)`; the FP8 cache needs the latter).  Only slots in
+        front of the next step's `cur` are ever trusted: the slots at or behind it hold drafts that were not accepted, and the next
+        chunk rewrites them (its slot0 is the new `cur`, its width k + 1) before
         its attention, or any later one, reads them."""
         B, w = tokens.shape
-        assert self._gen_shape[0] == B and self._gen_kind == "bf16" and B * w <= H.DECODE_MAX_ROWS and cur + w <= self._gen_shape[1]
+        assert self._gen_shape[0] == B and B * w <= H.DECODE_MAX_ROWS and cur + w <= self._gen_shape[1]
+        assert self._gen_kind == "bf16" or (self.spec_attention == "split" and self._verify_attn_rows(w - 1))
         return self._step_rows(tokens, cur, kv_start)
 
     def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook) -> Optional[str]:
         """Why a call with speculation on runs the plain loop all the same; None when it does not.  The first three hold under
-        scope "greedy" only."""
+        scope "greedy" only; the FP8 KV cache is a reason unless `attention="split"` and the G (k + 1) query rows per KV head fit
+        the verify kernel."""
         if getattr(self, "spec_scope", "greedy") != "all":
             if do_sample:
                 return "do_sample"
@@ -2189,8 +2234,12 @@ class CausalLMHIP:
             return "forced_tokens"
         if layer_hook is not None:
             return "layer_hook"
-        if self.kv_cache_kind == "fp8":
-            return "fp8 kv cache"
+        if self.kv_cache_kind == "fp8":                                      # only the split-KV verify kernels read the byte cache
+            if getattr(self, "spec_attention", "forward") != "split":
+                return "fp8 kv cache"
+            G = self.hq // self.hkv
+            if G * (k + 1) > H.VERIFY_ATTN_MAX_ROWS:
+                return f"fp8 kv cache: {G} x {k + 1} = {G * (k + 1)} query rows per KV head > {H.VERIFY_ATTN_MAX_ROWS}"
         if B * (k + 1) > H.DECODE_MAX_ROWS:
             return f"B * (k + 1) = {B * (k + 1)} rows > {H.DECODE_MAX_ROWS}"
         return None
@@ -2709,16 +2758,19 @@ class DeSTA25AudioModel:
         check_prefill_chunk(n)
         self.llm.set_prefill_chunk(n)
 
-    def set_speculative(self, k: Optional[int], scope: str = "greedy") -> None:
+    def set_speculative(self, k: Optional[int], scope: str = "greedy", attention: str = "forward") -> None:
         """Decoding of `generate` / `_generate_step` / the trainer's evaluate: None or 0 (default) = one token per step; an
         int k in 1..7 = k draft tokens per step from a lookup in the row's own prompt (the spliced transcription included) and
         output, verified by one pass over the weights (`CausalLMHIP.set_speculative`, which lists what runs the plain loop
         instead).  scope = "greedy" (default): plain greedy calls only; scope = "all": sampled calls (the default of `generate`),
-        a repetition penalty and `logprobs` speculate too and return the plain loop's tokens.  A bad k or scope raises ValueError
+        a repetition penalty and `logprobs` speculate too and return the plain loop's tokens.  attention = "split": a verify step
+        attends through the split-KV verify kernels, from H.DECODE_ATTN_MIN_KEYS keys on with the bf16 cache and at every length
+        with the FP8 KV cache, which speculates only under this setting.  A bad k, scope or attention raises ValueError
         and leaves the setting as it was.  `model.llm.spec_stats` reports the path taken and the acceptance of the last call."""
         check_speculative_arg(k)
         check_speculative_scope(scope)
-        self.llm.set_speculative(k, scope)
+        check_speculative_attention(attention)
+        self.llm.set_speculative(k, scope, attention)
 
     def eval(self):
         return self.train(False)

@@ -219,6 +219,19 @@ def speculative_scope(cfg: Cfg) -> str:
     return scope
 
 
+SPECULATIVE_ATTENTIONS = ("forward", "split")
+
+
+def speculative_attention(cfg: Cfg) -> str:
+    """trainer.speculative_attention (this port's key; absent = "forward"): the attention kernel of a verify step of
+    `trainer.speculative`, "forward" (the causal forward kernel) or "split" (the split-KV verify kernels: long caches, and the
+    only setting under which `trainer.kv_cache: fp8` speculates; `DeSTA25AudioModel.set_speculative`)."""
+    attention = cfg.trainer.get("speculative_attention", "forward")
+    if not isinstance(attention, str) or attention not in SPECULATIVE_ATTENTIONS:
+        raise ValueError(f"trainer.speculative_attention={attention!r} is not supported (one of {', '.join(SPECULATIVE_ATTENTIONS)}, or absent)")
+    return attention
+
+
 def load_pretrained_weights(model, path: str) -> None:
     """Lightning-style {'state_dict': ...} with a 'model.' prefix (reference :73-83); tensors only."""
     import torch
@@ -285,6 +298,7 @@ def main(argv=None):
     chunk = prefill_chunk(cfg)
     spec = speculative(cfg)
     spec_scope = speculative_scope(cfg)
+    spec_attention = speculative_attention(cfg)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
@@ -294,7 +308,7 @@ def main(argv=None):
     model.set_decode_weights(decode_weights)
     model.set_kv_cache(kv_cache)
     model.set_prefill_chunk(chunk)
-    model.set_speculative(spec, spec_scope)
+    model.set_speculative(spec, spec_scope, **({} if spec_attention == "forward" else {"attention": spec_attention}))     # absent: the call as it always was
     if cfg.get("init_from_pretrained_weights"):
         load_pretrained_weights(model, cfg.init_from_pretrained_weights)
     train_ds, eval_ds, collate, tok = create_datasets(cfg, model, rank)

@@ -566,6 +566,31 @@ int    desta_attention_decode(const desta_attn_desc* d, void* workspace, size_t 
 int    desta_attention_decode_kv8(const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t scale_batch_stride,
                                   int64_t scale_row_stride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Split-KV attention of a verify step (additive to ABI 8: no struct changes): the attention of the k + 1 candidate rows that
+ * `llm_model.generate(prompt_lookup_num_tokens=k)` checks in one pass against past_key_values (modeling_desta25.py:1419;
+ * TF:generation/utils.py _assisted_decoding, TF:models/llama/modeling_llama.py:230-281), on either cache form.  The work
+ * items, chunks, workspace protocol and arithmetic of desta_attention_decode{,_kv8}, with seq_q = 2..8 query rows per sequence:
+ * the R = (n_q_heads / n_kv_heads) * seq_q <= DESTA_ATTN_VERIFY_MAX_ROWS query rows of a KV head share every K / V byte and
+ * scale of an item.  The descriptor is desta_attention_fwd's for that shape: causal = 1 (query row j sees keys
+ * kv_start[b] <= key <= j + seq_k - seq_q), Q rows at q_row_stride inside q_batch_stride, O likewise, lse optional,
+ * [batch][n_q_heads][seq_q] in the log2 domain.  A row that sees no key gets O = 0 and lse = +inf.
+ * Query row j equals, bit for bit in O and lse, desta_attention_decode{,_kv8} on the same cache with
+ * seq_k' = seq_k - (seq_q - 1 - j) and that row as the one query: a masked key enters as p = exp2(-inf) = 0 and
+ * fma(0, v, acc) = acc, block maximum, row sum, empty chunks and the merge are kept per query row, and the per-row summation
+ * order does not depend on R.  Rows >= seq_k of the cache (and their scales) are never read; rows in [seq_k', seq_k) are read
+ * and must hold finite values (a verify step has just appended them).
+ * Workspace: desta_attention_verify_workspace_bytes (0 while seq_k <= CHUNK; one partial per query row, head and chunk).
+ * Returns DESTA_EINVAL and launches nothing for: seq_q outside 2..8, more than 8 query heads per KV head, R > 16,
+ * head_dim != 128, causal == 0, dropout_p != 0, non-NULL rope_cos_sin / O_f32 / dO / dQ, O (or Q, K, V) not 16-byte aligned or
+ * with a batch or row stride that is no multiple of 8 elements, a workspace that is too small or not 16-byte aligned, and (kv8)
+ * NULL scales. */
+#define DESTA_ATTN_VERIFY_MAX_SEQ_Q 8
+#define DESTA_ATTN_VERIFY_MAX_ROWS 16
+size_t desta_attention_verify_workspace_bytes(int batch, int n_q_heads, int seq_q, int seq_k, int head_dim);
+int    desta_attention_verify(const desta_attn_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+int    desta_attention_verify_kv8(const desta_attn_desc* d, const float* k_scale, const float* v_scale, int64_t scale_batch_stride,
+                                  int64_t scale_row_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The FP8 KV cache of one layer back as bf16, for the attention of a prompt chunk (additive to ABI 8): the forward kernel
  * reads bf16, so a chunk that attends cached e4m3 keys gets them through a staging slab.  kv_cache / kv_scale: the bytes and
  * scales of desta_attention_decode_kv8's format, n_heads = K heads + V heads of one slot (2 * n_kv_heads), head_dim 128;

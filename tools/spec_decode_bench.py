@@ -2,7 +2,7 @@
 
   python tools/spec_decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 1,4,8,16] [--k 3,7] [--ctx 64] [--prompt-tail 16]
                                     [--new 64] [--weights {bf16,fp8}] [--prefill-chunk N] [--rounds 3] [--sample] [--penalty 1.05]
-                                    [--no-greedy]
+                                    [--no-greedy] [--attention {forward,split,ab}] [--kv {bf16,fp8}]
 The workload flags are those of tools/decode_bench.py (--batch and --k take comma-separated lists).  For every batch size the plain
 loop and, per k, three speculative legs alternate in ONE process for --rounds rounds after a warm-up of every leg; each run is
 timed with HIP events around `_generate_step`, and the time of a prompt-only run (one new token, same leg, same round) is taken
@@ -23,6 +23,11 @@ loop (`spec_stats["reason"]`): the summary says so and reports no speculative fi
 for sampled calls (temperature 0.7, top_p 0.9, the reference's defaults: `sample_top_p_rows` picks the verify rows) and for greedy
 calls with a repetition penalty (`sample_rows`); every line carries its `mode`.  `accepted` again takes the path's own output (the
 `rejected` leg's ids under the same mode) as drafts, and the plain leg of a mode is the plain loop with the same settings.
+--attention picks the attention of the verify step (`set_speculative(k, attention=...)`): forward (default), split (the split-KV
+verify kernels; on the bf16 cache from H.DECODE_ATTN_MIN_KEYS keys on, so give a --ctx that reaches them), or ab: the speculative
+legs of both, alternating in the same rounds, one summary line per (k, attention).  --kv fp8 runs everything on the FP8 KV cache:
+with attention forward the speculative legs report the plain loop (`"speculative": "not run: fp8 kv cache"`, today's fallback), with
+split they speculate.  Every line carries `attention` and `kv`.
 """
 import argparse
 import json
@@ -51,6 +56,8 @@ def main():
     ap.add_argument("--sample", action="store_true", help="add the sampled legs (temperature 0.7, top_p 0.9: the reference's defaults), scope \"all\"")
     ap.add_argument("--penalty", type=float, default=None, help="add greedy legs with this repetition penalty (e.g. 1.05), scope \"all\"")
     ap.add_argument("--no-greedy", action="store_true", help="leave the plain greedy legs out")
+    ap.add_argument("--attention", choices=("forward", "split", "ab"), default="forward", help="attention of the verify step; ab: both, alternating")
+    ap.add_argument("--kv", choices=("bf16", "fp8"), default="bf16", help="what the KV cache holds (`set_kv_cache`)")
     a = ap.parse_args()
     batches, ks = [int(x) for x in a.batch.split(",")], [int(x) for x in a.k.split(",")]
     assert a.new >= 2 and a.rounds >= 1
@@ -63,7 +70,9 @@ def main():
     model = DeSTA25AudioModel(cfg, weights=RandomWeights(cfg, dev, seed=0), device=dev).eval()
     model.set_decode_weights(a.weights)
     model.set_prefill_chunk(a.prefill_chunk)
+    model.set_kv_cache(a.kv)
     llm = model.llm
+    attentions = ["forward", "split"] if a.attention == "ab" else [a.attention]
     modes = [] if a.no_greedy else [("greedy", dict(do_sample=False), "greedy")]
     if a.sample:
         modes.append(("sample", dict(do_sample=True, temperature=0.7, top_p=0.9, seed=1), "all"))
@@ -80,9 +89,9 @@ def main():
         S = t["input_ids"].shape[1]
 
         for mode, gen_kw, scope in modes:
-            def timed(k, drafts, new):
+            def timed(k, att, drafts, new):
                 """-> (ms of one `_generate_step` by HIP events, ids, spec_stats)"""
-                model.set_speculative(k, scope=scope)
+                model.set_speculative(k, scope=scope, attention=att)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 torch.cuda.synchronize()
                 e0.record()
@@ -91,12 +100,12 @@ def main():
                 e1.synchronize()
                 return e0.elapsed_time(e1), ids, dict(llm.spec_stats)
 
-            def leg(name, k, drafts):
-                prompt_ms, _, _ = timed(k, None if drafts is None else drafts[:, :1], 1)
-                ms, ids, st = timed(k, drafts, a.new)
+            def leg(name, k, att, drafts):
+                prompt_ms, _, _ = timed(k, att, None if drafts is None else drafts[:, :1], 1)
+                ms, ids, st = timed(k, att, drafts, a.new)
                 assert ids.shape == (B, a.new)
                 steps = st["verify_steps"]
-                r = {"mode": mode, "B": B, "prompt": S, "new": a.new, "weights": a.weights, "leg": name, "k": k, "path": st["path"], "reason": st["reason"],
+                r = {"mode": mode, "B": B, "prompt": S, "new": a.new, "weights": a.weights, "kv": a.kv, "leg": name, "k": k, "attention": att if k else None, "path": st["path"], "reason": st["reason"],
                      "prompt_ms": round(prompt_ms, 3), "decode_ms": round(ms - prompt_ms, 3),
                      "ms_per_emitted_token": round((ms - prompt_ms) / (a.new - 1), 4), "verify_steps": steps,
                      "tokens_per_verify_step": round((a.new - 1) / steps, 3) if steps else None,
@@ -104,25 +113,27 @@ def main():
                 print(json.dumps(r), flush=True)
                 return r, ids
 
-            _, plain_ids = leg("plain", None, None)                             # warm-up
+            _, plain_ids = leg("plain", None, "forward", None)                  # warm-up
             none = torch.full_like(plain_ids, -1)
-            legs = [("plain", None, None)]
-            for k in ks:                                                         # warm-up of every leg: buffers, workspaces, code objects
-                _, own = leg("rejected", k, none)                                # the verify path's own greedy output at this row count
-                legs += [("accepted", k, own), ("rejected", k, none), ("lookup", k, None)]
-                for name, _, dr in legs[-3:]:
-                    r, ids = leg(name, k, dr)
+            legs = [("plain", None, "forward", None)]
+            for k, att in ((k, att) for k in ks for att in attentions):          # warm-up of every leg: buffers, workspaces, code objects
+                _, own = leg("rejected", k, att, none)                           # the verify path's own greedy output at this row count
+                legs += [("accepted", k, att, own), ("rejected", k, att, none), ("lookup", k, att, None)]
+                for name, _, _, dr in legs[-3:]:
+                    r, ids = leg(name, k, att, dr)
                     if r["path"] == "speculative":
-                        print(json.dumps({"mode": mode, "B": B, "k": k, "leg": name, "tokens_equal_to_rejected_leg": float((ids == own).float().mean()),
+                        print(json.dumps({"mode": mode, "B": B, "k": k, "attention": att, "leg": name,
+                                          "tokens_equal_to_rejected_leg": float((ids == own).float().mean()),
                                           "tokens_equal_to_plain": float((ids == plain_ids).float().mean())}), flush=True)
-            runs = {(name, k): [] for name, k, _ in legs}
+            runs = {(name, k, att): [] for name, k, att, _ in legs}
             for _ in range(a.rounds):
-                for name, k, dr in legs:
-                    runs[(name, k)].append(leg(name, k, dr)[0])
-            plain = [r["ms_per_emitted_token"] for r in runs[("plain", None)]]
-            for k in ks:
-                acc, rej, look = runs[("accepted", k)], runs[("rejected", k)], runs[("lookup", k)]
-                s = {"summary": f"{a.config} {mode} B={B} prompt={S} new={a.new} weights={a.weights} k={k}", "mode": mode, "rounds": a.rounds,
+                for name, k, att, dr in legs:
+                    runs[(name, k, att)].append(leg(name, k, att, dr)[0])
+            plain = [r["ms_per_emitted_token"] for r in runs[("plain", None, "forward")]]
+            for k, att in ((k, att) for k in ks for att in attentions):
+                acc, rej, look = runs[("accepted", k, att)], runs[("rejected", k, att)], runs[("lookup", k, att)]
+                s = {"summary": f"{a.config} {mode} B={B} prompt={S} new={a.new} weights={a.weights} kv={a.kv} k={k} attention={att}", "mode": mode,
+                     "attention": att, "kv": a.kv, "rounds": a.rounds,
                      "plain_ms_per_token": plain, "plain_median": _median(plain), "plain_spread": round(max(plain) - min(plain), 4)}
                 if acc[0]["path"] != "speculative":
                     s["speculative"] = f"not run: {acc[0]['reason']}"
