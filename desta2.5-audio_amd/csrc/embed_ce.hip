@@ -490,6 +490,88 @@ __global__ __launch_bounds__(LPT) void topk_logprob_k(const bf16_t* __restrict__
     }
 }
 
+// Classifier-free guidance of a decode step's rows (desta_cfg_scores_bf16): out[c] = g * (lc[c] - lu[c]) + lu[c] with lc / lu the
+// log-probabilities of the conditional and the unconditional row, by topk_logprob_k's code (lse_thread_pass<false>, the two merges,
+// lse_logprob), so they carry the bits that kernel reports.  One 1024-thread block per row.  Pass 1 reads both rows once for
+// their (m, s) pairs; pass 2 reads them again (from L2, unmeasured) and stores.  Pass 2 is cut at `out`'s 16-byte boundaries: the
+// elements in front of the first one and behind the last whole chunk go one by one, the chunks between by one 16-byte store
+// each; an input row takes 16-byte loads there if it is aligned like `out` and 2-byte loads if not.
+#pragma clang fp contract(off)
+// fl(fl(g * fl(lc - lu)) + lu) rounded to bf16; a -inf entry of either row has no mass under it and stays -inf (never inf - inf)
+__device__ __forceinline__ bf16_t cfg_combine(float xc, float xu, float mc, float sc, float mu, float su, float g) {
+    if (xc == -INFINITY || xu == -INFINITY) return 0xff80;
+    const float lc = lse_logprob(xc, mc, sc), lu = lse_logprob(xu, mu, su);
+    const float d = lc - lu;
+    const float t = g * d;
+    return f2bf(t + lu);
+}
+#pragma clang fp contract(fast)
+
+// Pass 2 over the whole 16-byte chunks of `out`'s row: two chunks per trip, so four loads are in flight per thread.  ALIGNED: both
+// input rows are aligned like `out` (every decode step's buffers are); otherwise a row that is not takes 2-byte loads.
+template <bool ALIGNED>
+__device__ __forceinline__ void cfg_store_chunks(const bf16_t* __restrict__ rc, const bf16_t* __restrict__ ru, bf16_t* __restrict__ ro,
+                                                 int head, int n8, int tid, bool vec_c, bool vec_u, float mc, float sc, float mu, float su,
+                                                 float g) {
+    auto load8 = [](const bf16_t* src, bool vec) {
+        if (ALIGNED || vec) return *(const u16x8*)src;
+        u16x8 v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = src[e];
+        return v;
+    };
+    auto put = [&](long c0, const u16x8& vc, const u16x8& vu) {
+        u16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = cfg_combine(bf2f(vc[e]), bf2f(vu[e]), mc, sc, mu, su, g);
+        *(u16x8*)(ro + c0) = o;
+    };
+    int i = tid;
+    for (; i + LPT < n8; i += 2 * LPT) {
+        const long c0 = head + (long)i * 8, c1 = head + (long)(i + LPT) * 8;
+        const u16x8 vc0 = load8(rc + c0, vec_c), vu0 = load8(ru + c0, vec_u);
+        const u16x8 vc1 = load8(rc + c1, vec_c), vu1 = load8(ru + c1, vec_u);
+        put(c0, vc0, vu0);
+        put(c1, vc1, vu1);
+    }
+    for (; i < n8; i += LPT) {
+        const long c0 = head + (long)i * 8;
+        put(c0, load8(rc + c0, vec_c), load8(ru + c0, vec_u));
+    }
+}
+
+__global__ __launch_bounds__(LPT) void cfg_scores_k(const bf16_t* __restrict__ cond, const bf16_t* __restrict__ uncond, long ld, int V,
+                                                    float g, bf16_t* __restrict__ out, long ld_out) {
+    __shared__ float red_m[2][LPT / 64], red_s[2][LPT / 64];
+    __shared__ int red_e[LPT / 64];
+    __shared__ float fin[4];                                     // m, s of the conditional row, then of the unconditional one
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const bf16_t* rc = cond + (long)r * ld;
+    const bf16_t* ru = uncond + (long)r * ld;
+    bf16_t* ro = out + (long)r * ld_out;
+    float mc = -INFINITY, sc = 0.f, mu = -INFINITY, su = 0.f;
+    int early = 0;
+    lse_thread_pass<false>(rc, V, 0, 0.f, tid, mc, sc, early);
+    lse_thread_pass<false>(ru, V, 0, 0.f, tid, mu, su, early);
+    lse_wave_merge(mc, sc, early, tid, red_m[0], red_s[0], red_e);
+    lse_wave_merge(mu, su, early, tid, red_m[1], red_s[1], red_e);
+    __syncthreads();
+    if (tid == 0) {
+        lse_block_merge(mc, sc, early, red_m[0], red_s[0], red_e);
+        lse_block_merge(mu, su, early, red_m[1], red_s[1], red_e);
+        fin[0] = mc; fin[1] = sc; fin[2] = mu; fin[3] = su;
+    }
+    __syncthreads();
+    mc = fin[0]; sc = fin[1]; mu = fin[2]; su = fin[3];
+    const int head = min(V, (int)(((16 - ((uintptr_t)ro & 15)) & 15) >> 1));
+    const int n8 = (V - head) >> 3;
+    const bool vec_c = (((uintptr_t)(rc + head)) & 15) == 0, vec_u = (((uintptr_t)(ru + head)) & 15) == 0;
+    if (tid < head) ro[tid] = cfg_combine(bf2f(rc[tid]), bf2f(ru[tid]), mc, sc, mu, su, g);
+    if (vec_c && vec_u) cfg_store_chunks<true>(rc, ru, ro, head, n8, tid, true, true, mc, sc, mu, su, g);
+    else cfg_store_chunks<false>(rc, ru, ro, head, n8, tid, vec_c, vec_u, mc, sc, mu, su, g);
+    for (int c = head + n8 * 8 + tid; c < V; c += LPT) ro[c] = cfg_combine(bf2f(rc[c]), bf2f(ru[c]), mc, sc, mu, su, g);
+}
+
 __global__ __launch_bounds__(256) void ce_finish_k(const float* __restrict__ row_loss, int M, const float* __restrict__ scal,
                                                    float* __restrict__ loss) {
     __shared__ float red[4];
@@ -678,6 +760,18 @@ extern "C" int desta_topk_logprobs(const void* logits_bf16, int64_t ld, const in
     hipLaunchKernelGGL(topk_logprob_k, dim3(rows), dim3(LPT), 0, (hipStream_t)stream, (const bf16_t*)logits_bf16, (long)ld,
                        (const long*)tokens, vocab, top_n, token_logprob, top_ids, top_logprobs);
     DESTA_CHECK_LAUNCH("topk_logprobs");
+    return DESTA_OK;
+}
+
+extern "C" int desta_cfg_scores_bf16(const void* cond_bf16, const void* uncond_bf16, int64_t ld, int rows, int vocab,
+                                     float guidance_scale, void* out_bf16, int64_t ld_out, void* stream) {
+    DESTA_CHECK_ARG(cond_bf16 && uncond_bf16 && out_bf16, "cfg_scores: null argument");
+    DESTA_CHECK_ARG(out_bf16 != cond_bf16 && out_bf16 != uncond_bf16, "cfg_scores: out may not be an input");
+    DESTA_CHECK_ARG(rows > 0 && vocab > 0 && vocab <= 262144 && ld >= vocab && ld_out >= vocab, "cfg_scores: bad shape");
+    DESTA_CHECK_ARG(guidance_scale > 0.f && guidance_scale < INFINITY, "cfg_scores: guidance_scale must be finite and > 0");
+    hipLaunchKernelGGL(cfg_scores_k, dim3(rows), dim3(LPT), 0, (hipStream_t)stream, (const bf16_t*)cond_bf16,
+                       (const bf16_t*)uncond_bf16, (long)ld, vocab, guidance_scale, (bf16_t*)out_bf16, (long)ld_out);
+    DESTA_CHECK_LAUNCH("cfg_scores");
     return DESTA_OK;
 }
 

@@ -530,7 +530,9 @@ _token_logprobs = _sig("desta_token_logprobs", vp, i64, vp, i32, i32, vp, vp, vp
 _topk_logprobs = _sig("desta_topk_logprobs", vp, i64, vp, i32, i32, i32, vp, vp, vp, vp)
 TOPK_LOGPROBS_MAX = 32             # largest top_n of desta_topk_logprobs
 TOPK_LOGPROBS_CALLS = 0            # launches issued by this process (tests assert one per decode step, none without logprobs=)
-_mix_fwd = _sig("desta_tap_mix_fwd", vp, vp, i32, i32, i32, i32, vp, vp)
+_cfg_scores = _sig("desta_cfg_scores_bf16", vp, vp, i64, i32, i32, f32, vp, i64, vp)
+CFG_SCORES_CALLS = 0               # launches issued by this process (tests assert one per guided decode step, none without guidance)
+_mix_fwd = _sig("desta_tap_mix_fwd",vp, vp, i32, i32, i32, i32, vp, vp)
 _mix_bwd = _sig("desta_tap_mix_bwd", vp, vp, vp, i32, i32, i32, i32, vp, vp, vp)
 
 
@@ -567,6 +569,16 @@ def topk_logprobs(logits, ld, tokens, rows, vocab, top_n, token_logprob=None, to
     check(_topk_logprobs(p(logits), ld, p(tokens), rows, vocab, top_n, p(token_logprob), p(top_ids), p(top_logprobs), stream()),
           "desta_topk_logprobs")
     TOPK_LOGPROBS_CALLS += 1
+
+
+@_profiled("cfg_scores", lambda cond, uncond, ld, rows, vocab, scale, out, ld_out: 10 * rows * vocab)
+def cfg_scores(cond, uncond, ld, rows, vocab, scale, out, ld_out):
+    """out[r, :vocab] (bf16, stride ld_out) = scale * (lc - lu) + lu with lc / lu the fp32 log-softmax of the bf16 rows cond[r] /
+    uncond[r] (stride ld, untouched): classifier-free guidance, HF's first logits processor.  -inf in either row gives -inf;
+    columns >= vocab of out are not written (include/desta_hip.h desta_cfg_scores_bf16)."""
+    global CFG_SCORES_CALLS
+    check(_cfg_scores(p(cond), p(uncond), ld, rows, vocab, scale, p(out), ld_out, stream()), "desta_cfg_scores_bf16")
+    CFG_SCORES_CALLS += 1
 
 
 def tap_mix_fwd(x, lw, taps, batch, prompt, d, out):

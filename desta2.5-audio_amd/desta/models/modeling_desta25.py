@@ -447,10 +447,39 @@ def check_logprobs_arg(n) -> None:
         raise ValueError(f"`logprobs` has to be None or an integer in [0, {H.TOPK_LOGPROBS_MAX}], but is {n!r}")
 
 
-def check_decode_rows(B: int) -> None:
-    """A KV-cached decode step streams the weights once for all its rows; its projections take at most H.DECODE_MAX_ROWS of them."""
+def check_decode_rows(B: int, guided: bool = False) -> None:
+    """A KV-cached decode step streams the weights once for all its rows; its projections take at most H.DECODE_MAX_ROWS of them.
+    guided: B counts the unconditional rows of a `guidance_scale` call as well."""
     if B > H.DECODE_MAX_ROWS:
+        if guided:
+            raise ValueError(f"generate: guidance_scale doubles the rows (one unconditional row per sequence): {B // 2} sequences are {B} rows, "
+                             f"the KV-cached decode step takes at most {H.DECODE_MAX_ROWS}: split the batch")
         raise ValueError(f"generate: a batch of {B} sequences, the KV-cached decode step takes at most {H.DECODE_MAX_ROWS}: split the batch")
+
+
+def check_guidance_arg(g) -> None:
+    """`guidance_scale=` of generate(): None (off) or a finite real > 0 (1 is off as well: HF builds no processor at scale 1)."""
+    if g is None:
+        return
+    if isinstance(g, bool) or not isinstance(g, (int, float)) or not (g > 0 and math.isfinite(g)):
+        raise ValueError(f"`guidance_scale` has to be None or a finite number > 0, but is {g!r}")
+
+
+def guidance_negative_messages(messages, audio_locator: str):
+    """The negative prompt `generate(guidance_scale=)` derives when none is given: the same chat without its audio.  Every
+    conversation of `messages` (one conversation, or a list of them) is copied with each `audio_locator` taken out of every
+    `content` (str.replace, nothing else touched) and the `audios` entries dropped; the input is not modified."""
+    def strip(conv):
+        neg = []
+        for m in conv:
+            m2 = {k: v for k, v in m.items() if k != "audios"}
+            if isinstance(m2.get("content"), str):
+                m2["content"] = m2["content"].replace(audio_locator, "")
+            neg.append(m2)
+        return neg
+    if messages and isinstance(messages[0], dict):
+        return strip(messages)
+    return [strip(conv) for conv in messages]
 
 
 PREFILL_CHUNK_MIN = 16                              # positions: a 16-row MFMA tile; below it a chunk is launch overhead only
@@ -2219,10 +2248,12 @@ class CausalLMHIP:
         assert self._gen_kind == "bf16" or (self.spec_attention == "split" and self._verify_attn_rows(w - 1))
         return self._step_rows(tokens, cur, kv_start)
 
-    def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook) -> Optional[str]:
-        """Why a call with speculation on runs the plain loop all the same; None when it does not.  The first three hold under
-        scope "greedy" only; the FP8 KV cache is a reason unless `attention="split"` and the G (k + 1) query rows per KV head fit
-        the verify kernel."""
+    def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook, guided: bool = False) -> Optional[str]:
+        """Why a call with speculation on runs the plain loop all the same; None when it does not.  A guided call (`guidance_scale`)
+        always does.  The next three hold under scope "greedy" only; the FP8 KV cache is a reason unless `attention="split"` and the
+        G (k + 1) query rows per KV head fit the verify kernel."""
+        if guided:
+            return "guidance_scale"
         if getattr(self, "spec_scope", "greedy") != "all":
             if do_sample:
                 return "do_sample"
@@ -2368,7 +2399,7 @@ class CausalLMHIP:
                         after_prompt=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                         repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None, chunk_hook=None,
                         logprobs: Optional[int] = None, speculate: Optional[int] = None, draft_tokens: Optional[torch.Tensor] = None,
-                        lookup_ids: Optional[torch.Tensor] = None):
+                        lookup_ids: Optional[torch.Tensor] = None, guidance_scale: Optional[float] = None):
         """Prompt pass + KV-cached decode (greedy, or temperature / top-p sampling with the library's counter RNG).  Returns new token ids [B, n_new] (int64; finished sequences are
         filled with pad_token_id, generation stops early once every sequence has produced an EOS), and, with
         collect_logits, the per-step logits [n_new, B, V] (bf16).  `forced_tokens` [B, T] teacher-forces the
@@ -2388,14 +2419,28 @@ class CausalLMHIP:
         scope "all" takes do_sample, repetition_penalty and logprobs off that list: the verify rows then go through the sampler
         this loop would launch, row j at step n + j, and the result is this loop's).  The
         drafts come from a lookup in `lookup_ids` [B, S] (the prompt's token ids, -1 at left pads and audio positions) followed by
-        the emitted tokens, or from `draft_tokens` [B, max_new_tokens] (int64; the proposal for emitted position t, -1 = none)."""
+        the emitted tokens, or from `draft_tokens` [B, max_new_tokens] (int64; the proposal for emitted position t, -1 = none).
+        guidance_scale = g (None or 1: off, everything above as it stands): classifier-free guidance.  B = 2 Bc rows: rows [0, Bc) are
+        the conditional prompts, row Bc + b the unconditional (negative) prompt of sequence b.  Prompt pass, cache and decode step
+        run on all 2 Bc rows; per step one `H.cfg_scores` launch writes g * (lc - lu) + lu of the two halves' log-softmaxes into a
+        [Bc, Vp] scratch and the pick above runs on that with rows = Bc (HF: the guidance processor is the first of the chain, so
+        penalty, temperature and filters act on the guided scores); both rows of a sequence are fed its pick.  The result,
+        `forced_tokens`, `prompt_ids` (the conditional prompts') and `logprobs` have Bc rows; EOS is judged per sequence.
+        `logprobs` still reports the model's own distribution: the raw CONDITIONAL rows.  collect_logits returns the raw logits of
+        all rows, [n_new, 2 Bc, V], conditional rows first: the values the guidance kernel read.  Speculation does not cover a
+        guided call (`spec_stats["reason"] == "guidance_scale"`)."""
         assert max_new_tokens >= 1
-        check_decode_rows(B)
+        check_guidance_arg(guidance_scale)
+        guided = guidance_scale is not None and float(guidance_scale) != 1.0
+        if guided and B % 2:
+            raise ValueError(f"generate: guidance_scale needs an even number of rows (conditional rows, then one unconditional row each), got {B}")
+        check_decode_rows(B, guided)
+        Bc = B // 2 if guided else B                                         # sequences: rows of the result and of every per-call state
         use_pen = repetition_penalty is not None and float(repetition_penalty) != 1.0
         chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0)))
         check_speculative_arg(speculate)
         spec_k = (self.speculative if speculate is None else speculate) or 0
-        spec_reason = self._spec_reason(spec_k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook) if spec_k else "off"
+        spec_reason = self._spec_reason(spec_k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook, guided=guided) if spec_k else "off"
         # a verify chunk writes up to k slots past the last accepted one: cache, cos / sin table and workspaces get k more slots
         Smax = S + max_new_tokens + (spec_k if spec_reason is None else 0)
         self._gen_alloc(B, Smax)
@@ -2410,13 +2455,13 @@ class CausalLMHIP:
                          kv_cache=self.kv_cache, layer_hook=layer_hook)
         if after_prompt is not None:
             after_prompt()
-        out = torch.full((B, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
-        finished = torch.zeros(B, dtype=torch.bool, device=dev)
+        out = torch.full((Bc, max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
+        finished = torch.zeros(Bc, dtype=torch.bool, device=dev)
         eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
         P = 0
         if chain:                                                            # token history = [prompt ids,] emitted tokens: out is its tail
             P = 0 if prompt_ids is None else int(prompt_ids.shape[1])
-            hist = torch.full((B, P + max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
+            hist = torch.full((Bc, P + max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
             if P:
                 hist[:, :P] = prompt_ids.to(dev, torch.int64)
             out = hist[:, P:]
@@ -2429,29 +2474,37 @@ class CausalLMHIP:
                                           pick=pick, pen_hist=hist if chain else None, logprobs=logprobs)
         steps_logits = []
         if logprobs is not None:
-            lp_tok = torch.zeros(B, max_new_tokens, dtype=F32, device=dev)
-            lp_ids = torch.full((B, max_new_tokens, logprobs), -1, dtype=torch.int32, device=dev)
-            lp_top = torch.zeros(B, max_new_tokens, logprobs, dtype=F32, device=dev)
-            st_tok = torch.empty(B, dtype=F32, device=dev)                   # one step's rows, contiguous for the kernel
-            st_ids = torch.empty(B, logprobs, dtype=torch.int32, device=dev)
-            st_top = torch.empty(B, logprobs, dtype=F32, device=dev)
+            lp_tok = torch.zeros(Bc, max_new_tokens, dtype=F32, device=dev)
+            lp_ids = torch.full((Bc, max_new_tokens, logprobs), -1, dtype=torch.int32, device=dev)
+            lp_top = torch.zeros(Bc, max_new_tokens, logprobs, dtype=F32, device=dev)
+            st_tok = torch.empty(Bc, dtype=F32, device=dev)                  # one step's rows, contiguous for the kernel
+            st_ids = torch.empty(Bc, logprobs, dtype=torch.int32, device=dev)
+            st_top = torch.empty(Bc, logprobs, dtype=F32, device=dev)
         n_new = 0
+        g_next = self.g_next[:Bc]
+        scores = logits                                                      # what the pick reads: the logits, or the guided scores
+        if guided:                                                           # made once per shape; the kernel leaves the zero pad columns alone
+            if getattr(self, "_cfg_scratch", None) is None or self._cfg_scratch.shape != (Bc, self.Vp):
+                self._cfg_scratch = torch.zeros(Bc, self.Vp, dtype=BF16, device=dev)
+            scores = self._cfg_scratch
         for t in range(max_new_tokens):
             if collect_logits:
                 steps_logits.append(logits[:, :self.V].clone())
+            if guided:
+                H.cfg_scores(logits[:Bc], logits[Bc:], self.Vp, Bc, self.V, float(guidance_scale), scores, self.Vp)
             if chain:
-                H.sample(logits, self.Vp, B, self.V, self.g_next, do_sample=do_sample, temperature=float(temperature),
+                H.sample(scores, self.Vp, Bc, self.V, g_next, do_sample=do_sample, temperature=float(temperature),
                          top_k=int(top_k or 0), top_p=float(top_p), min_p=float(min_p or 0.0),
                          repetition_penalty=float(repetition_penalty) if use_pen else 1.0, hist=hist, hist_len=P + t, seed=seed, step=t)
             elif do_sample:
-                H.sample_top_p(logits, self.Vp, B, self.V, float(temperature), float(top_p), seed, t, self.g_next)
+                H.sample_top_p(scores, self.Vp, Bc, self.V, float(temperature), float(top_p), seed, t, g_next)
             else:
-                H.argmax_bf16(logits, self.Vp, B, self.V, self.g_next)
-            nxt = self.g_next if forced_tokens is None else forced_tokens[:, t].to(dev, torch.int64)
+                H.argmax_bf16(scores, self.Vp, Bc, self.V, g_next)
+            nxt = g_next if forced_tokens is None else forced_tokens[:, t].to(dev, torch.int64)
             nxt = torch.where(finished, torch.full_like(nxt, int(pad_token_id)), nxt)
             out[:, t] = nxt
             if logprobs is not None:                                         # rows finished before this step carry -1: not read, 0 / -1 / 0
-                H.topk_logprobs(logits, self.Vp, torch.where(finished, torch.full_like(nxt, -1), nxt), B, self.V, logprobs, st_tok, st_ids, st_top)
+                H.topk_logprobs(logits, self.Vp, torch.where(finished, torch.full_like(nxt, -1), nxt), Bc, self.V, logprobs, st_tok, st_ids, st_top)
                 lp_tok[:, t] = st_tok
                 lp_ids[:, t] = st_ids
                 lp_top[:, t] = st_top
@@ -2462,7 +2515,7 @@ class CausalLMHIP:
                     break
             if t + 1 == max_new_tokens:
                 break
-            logits = self.decode_step(nxt, S + t, kv_start, layer_hook=layer_hook)
+            logits = self.decode_step(torch.cat([nxt, nxt]) if guided else nxt, S + t, kv_start, layer_hook=layer_hook)
         n_new = self._trim_after_eos(out, eos, n_new)
         self.spec_stats = dict(path="plain", reason=spec_reason, verify_steps=0, emitted=n_new, drafts_accepted=0)
         out = out[:, :n_new]
@@ -2965,7 +3018,7 @@ class DeSTA25AudioModel:
     @torch.no_grad()
     def _generate_step(self, inputs, pad_token_id, temperature=0.7, top_p=0.9, max_new_tokens=512, do_sample=True,
                        eos_token_id=None, forced_tokens=None, collect_logits=False, seed=0, top_k=None, min_p=None,
-                       repetition_penalty=None, prompt_in_history=False, logprobs=None, draft_tokens=None):
+                       repetition_penalty=None, prompt_in_history=False, logprobs=None, draft_tokens=None, guidance_scale=None):
         """Reference `_generate_step` (modeling_desta25.py:1358-1431): audio features spliced into the prompt
         embeddings, then `llm_model.generate(inputs_embeds=…)` — here the KV-cached decoder on the HIP path.
         Returns ONLY the new tokens, as HF does for inputs_embeds prompts.  do_sample=False: greedy (temperature / top_p
@@ -2982,14 +3035,24 @@ class DeSTA25AudioModel:
         penalised and `logprobs` calls do too, with the plain loop's tokens and `TokenLogprobs`.
         The drafts are looked up in the row's prompt ids (the
         spliced transcription included, audio slots and pads never match) and its output, or taken from `draft_tokens`
-        [B, max_new_tokens] (the proposal for emitted position t, -1 = none: tests and benchmarks)."""
+        [B, max_new_tokens] (the proposal for emitted position t, -1 = none: tests and benchmarks).
+        guidance_scale = g (None or 1: off): classifier-free guidance, HF's `guidance_scale` with a negative prompt.  `inputs` hold
+        2 Bc rows, the Bc conditional prompts and then the unconditional prompt of each (audio spans may lie in any of them); the
+        result and `forced_tokens` have Bc rows (`CausalLMHIP.generate_greedy`).  Not with ORCA deep injection."""
         check_sampling_args(top_k, min_p, repetition_penalty)
         check_logprobs_arg(logprobs)
+        check_guidance_arg(guidance_scale)
+        guided = guidance_scale is not None and float(guidance_scale) != 1.0
+        if guided and self.orca is not None:
+            raise NotImplementedError("guidance_scale with ORCA deep injection (orca_hybrid): the injection hook takes one audio per row, "
+                                      "the unconditional rows of a guided batch have none")
         cfg, dev = self.config, self.device
         input_ids = inputs["context_input_ids"].to(dev)                      # only the context (prompt) part of the batch
         attention_mask = inputs["context_attention_mask"].to(dev)
         B, S = input_ids.shape
-        check_decode_rows(B)                                                 # before the encoder and the prompt pass run
+        if guided and B % 2:
+            raise ValueError(f"guidance_scale: inputs hold the conditional rows and then one unconditional row each, got {B} rows")
+        check_decode_rows(B, guided)                                         # before the encoder and the prompt pass run
         starts = inputs["context_batch_start_positions"]
         N_audio = len(starts)
         was_training = self.training
@@ -3041,7 +3104,8 @@ class DeSTA25AudioModel:
                                                 temperature=1.0 if temperature is None else float(temperature),
                                                 top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after,
                                                 top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty,
-                                                prompt_ids=input_ids if prompt_in_history else None, chunk_hook=chunk, logprobs=logprobs)
+                                                prompt_ids=(input_ids[:B // 2] if guided else input_ids) if prompt_in_history else None,
+                                                chunk_hook=chunk, logprobs=logprobs, guidance_scale=guidance_scale)
         finally:
             self.training = was_training
 
@@ -3110,7 +3174,7 @@ class DeSTA25AudioModel:
         return dict(token_logprobs=token_logprobs, top_logprobs=top, sum_logprob=[float(sum(r)) for r in token_logprobs])
 
     def generate(self, messages, temperature=0.7, top_p=0.9, do_sample=True, max_new_tokens=512, seed=0, top_k=None, min_p=None,
-                 repetition_penalty=None, logprobs=None):
+                 repetition_penalty=None, logprobs=None, guidance_scale=None, negative_messages=None):
         """The reference's chat-level `generate` (modeling_desta25.py:1491-1721): messages -> audio decode -> log-mel -> placeholder
         expansion of every `<|AUDIO|>` -> left-padded tokenisation, pad-shifted start positions, transcription ids ->
         `_generate_step` -> `GenerationOutput(text, audios, generated_ids)`.  Same messages schema, same errors; the front-end
@@ -3120,14 +3184,40 @@ class DeSTA25AudioModel:
         `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))`.
         logprobs = n (0..32): the output also carries `token_logprobs`, `top_logprobs` (n alternatives per token) and `sum_logprob`,
         each row cut behind its first EOS — the model's own distribution, log_softmax of the raw logits in front of the penalty,
-        the temperature and the filters (HF's output_logits, not output_scores)."""
+        the temperature and the filters (HF's output_logits, not output_scores).
+        guidance_scale = g (None or 1: off): classifier-free guidance, HF's `guidance_scale` with a negative prompt
+        (UnbatchedClassifierFreeGuidanceLogitsProcessor): every step's scores are g * (lc - lu) + lu, lc / lu the log-softmax under
+        the prompt and under the negative prompt, in front of the penalty, temperature and filters.  `negative_messages`: one
+        conversation per conversation of `messages`; None: the same chat without its audio (`guidance_negative_messages`), which
+        pushes the answer towards what the audio says (audio-contrastive decoding).  Both run as one left-padded batch of twice
+        the rows; the output has one row per conversation of `messages` and lists their audios only."""
         check_sampling_args(top_k, min_p, repetition_penalty)
         check_logprobs_arg(logprobs)
+        check_guidance_arg(guidance_scale)
         extra = dict(top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty)
         if logprobs is not None:
             extra["logprobs"] = logprobs
-        tok, inputs, audios, texts = self._chat_inputs(messages)
-        if not audios:
+        if guidance_scale is not None and float(guidance_scale) != 1.0:
+            if not isinstance(messages, list) or not messages:
+                raise ValueError("messages should be a list of dictionaries or a list of lists.")
+            conversations = [messages] if isinstance(messages[0], dict) else list(messages)
+            n_audio = sum(len(m.get("audios", [])) for conv in conversations for m in conv)
+            if negative_messages is None:
+                if n_audio == 0:
+                    raise ValueError("guidance_scale: the chat has no audio, so the derived negative prompt would be the prompt itself: pass negative_messages")
+                negatives = guidance_negative_messages(conversations, self.audio_locator)
+            else:
+                negatives = [negative_messages] if negative_messages and isinstance(negative_messages[0], dict) else list(negative_messages)
+            if len(negatives) != len(conversations):
+                raise ValueError(f"guidance_scale: negative_messages holds {len(negatives)} conversations for {len(conversations)} of messages")
+            extra["guidance_scale"] = guidance_scale
+            tok, inputs, audios, texts = self._chat_inputs(conversations + negatives)
+            text_only = not audios
+            audios, texts = audios[:n_audio], texts[:n_audio]                # the conditional conversations' (they come first)
+        else:
+            tok, inputs, audios, texts = self._chat_inputs(messages)
+            text_only = not audios
+        if text_only:
             # no audio: plain LLM generation on the chat template; stops on eos or <|eot_id|>
             eos = [tok.eos_token_id, tok.convert_tokens_to_ids("<|eot_id|>")]
             ids = self._generate_step(inputs, pad_token_id=tok.pad_token_id, temperature=temperature, top_p=top_p, max_new_tokens=max_new_tokens,

@@ -410,6 +410,26 @@ int desta_topk_logprobs(const void* logits_bf16, int64_t ld, const int64_t* toke
                         int top_n, float* token_logprob /* [rows], NULL iff tokens NULL */,
                         int32_t* top_ids /* [rows, top_n] */, float* top_logprobs /* [rows, top_n] */, void* stream);
 
+/* Classifier-free guidance of a decode step's rows (`generate(guidance_scale=g)` with a negative prompt; audio-contrastive
+ * decoding): `UnbatchedClassifierFreeGuidanceLogitsProcessor.__call__` TF:generation/logits_process.py,
+ *   scores = log_softmax(scores); uncond = log_softmax(uncond_logits); out = g * (scores - uncond) + uncond,
+ * which `_get_logits_processor` TF:generation/utils.py puts FIRST in the chain: the repetition penalty, temperature and the
+ * filters act on `out`.  HF runs a second forward for `uncond`; here both rows come out of one decode step.  Additive to ABI 8.
+ * cond, uncond bf16 [rows, ld], READ ONLY; out bf16 [rows, ld_out]; ld, ld_out >= vocab; each of the three may have any
+ * (2-byte) alignment.  Per row r and column c < vocab:
+ *   lc = logprob of cond[r, c], lu = logprob of uncond[r, c]: the bits desta_topk_logprobs reports for that row (shared code);
+ *   out[r, c] = bf16_rne( fl( fl(g * fl(lc - lu)) + lu ) ), every fp32 rounding as written, nothing fused;
+ *   cond[r, c] or uncond[r, c] == -inf: out[r, c] = -inf.  A deliberate difference: HF gives NaN (-inf - -inf) wherever the
+ *   unconditional entry alone is -inf; a token either distribution rules out stays ruled out here.
+ * Columns >= vocab of out are not written.  out may not overlap an input (an equal pointer is refused).  NaN inputs and rows
+ * without a finite entry are out of contract, as for desta_topk_logprobs.
+ * DESTA_EINVAL, nothing launched, unless: pointers non-NULL, out != cond, out != uncond, rows > 0, 0 < vocab <= 262144,
+ * ld >= vocab, ld_out >= vocab, guidance_scale finite and > 0.
+ * One 1024-thread block per row: one pass over both rows for their (maximum, sum) pairs, a second that stores (16-byte stores
+ * between out's 16-byte boundaries).  Fixed reduction order: bitwise reproducible, independent of rows. */
+int desta_cfg_scores_bf16(const void* cond_bf16, const void* uncond_bf16, int64_t ld, int rows, int vocab,
+                          float guidance_scale, void* out_bf16, int64_t ld_out, void* stream);
+
 /* Connector tap mix (modeling_desta25.py:600-604): x fp32 [taps][batch*prompt][d], layer_weights
  * fp32 [prompt][taps]; out[b,k,:] = sum_j softmax(layer_weights[k,:])_j x[j,b,k,:]; and its backward. */
 int desta_tap_mix_fwd(const float* x, const float* layer_weights, int taps, int batch, int prompt, int d,
