@@ -923,6 +923,32 @@ def sample_rows(logits, ld, batch, width, cols, out, *, do_sample=True, temperat
     SAMPLE_ROWS_CALLS += 1
 
 
+_logit_constraints = _sig("desta_logit_constraints_bf16", vp, i64, vp, i64, i32, i32, i32, vp, i64, i32, vp, i64, C.c_uint32, i32,
+                          vp, vp, i32, i32, vp, i32, vp, i32, i32, i32, vp)
+CONSTRAINT_CALLS = 0               # launches issued by this process (tests assert one per constrained decode step, none without)
+CONSTRAINT_MAX_WORDS, CONSTRAINT_MAX_WORD_IDS = 65536, 1048576     # caps of one bad-word table (desta_logit_constraints_bf16)
+
+
+def logit_constraints(src, ld_src, dst, ld_dst, batch, width, cols, *, hist=None, hist_len=0, tail=None, step0=0, no_repeat_ngram=0,
+                      word_ids=None, word_off=None, n_words=0, n_word_ids=0, begin_ids=None, n_begin=0, eos_ids=None, n_eos=0,
+                      min_new_tokens=0, id_max=-1):
+    """HF's banning processors on the batch * width bf16 rows of one decode step: dst[r, c] = -inf where no_repeat_ngram, the
+    bad-word table (suppress_tokens as one-token words), begin_ids (emitted position 0) or eos_ids (positions < min_new_tokens)
+    ban token c for the row's history, else src[r, c]; dst may be src.  Row (b, j) picks emitted position step0 + j with history
+    hist[b, :hist_len] followed by tail[b, 1:1 + j] (both int64); the tables are int32 on the device, id_max their largest id
+    (include/desta_hip.h desta_logit_constraints_bf16).  With every rule off nothing is launched."""
+    global CONSTRAINT_CALLS
+    assert hist is None or (hist.dtype == torch.int64 and hist.stride(1) == 1)
+    assert tail is None or (tail.dtype == torch.int64 and tail.stride(1) == 1 and tail.shape[0] >= batch and tail.shape[1] >= width)
+    assert all(t is None or (t.dtype == torch.int32 and t.is_contiguous()) for t in (word_ids, word_off, begin_ids, eos_ids))
+    check(_logit_constraints(p(src), ld_src, p(dst), ld_dst, batch, width, cols, p(hist), 0 if hist is None else hist.stride(0), hist_len,
+                             p(tail), 0 if tail is None else tail.stride(0), step0 & 0xFFFFFFFF, no_repeat_ngram, p(word_ids), p(word_off),
+                             n_words, n_word_ids, p(begin_ids), n_begin, p(eos_ids), n_eos, min_new_tokens, id_max, stream()),
+          "desta_logit_constraints_bf16")
+    if no_repeat_ngram or n_words or n_begin or (min_new_tokens and n_eos):
+        CONSTRAINT_CALLS += 1
+
+
 _spec_draft = _sig("desta_spec_ngram_draft", vp, i64, i32, i32, vp, i32, i32, i32, vp, vp)
 _spec_accept = _sig("desta_spec_accept", vp, vp, i32, i32, vp, vp, i32, i64, i32, vp, i64, i32, vp, vp, vp, i64, i32, vp)
 SPEC_DRAFT_CALLS = 0               # prompt-lookup launches issued by this process

@@ -407,15 +407,24 @@ _HF_GEN_UNSUPPORTED = {"num_beams": 1, "typical_p": 1.0, "epsilon_cutoff": 0.0, 
                        "no_repeat_ngram_size": 0, "bad_words_ids": None, "suppress_tokens": None}
 
 
-def resolve_generation_kwargs(llm_generation_config: dict, **explicit) -> dict:
+# HF's banning processors, honoured by `desta_logit_constraints_bf16` where a caller opts in (`constraints=True` below)
+_HF_GEN_CONSTRAINTS = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_new_tokens")
+
+
+def resolve_generation_kwargs(llm_generation_config: dict, *, constraints: bool = False, **explicit) -> dict:
     """The sampling settings HF's `generate` would use (TF:generation/utils.py:1806-1808): an explicit argument, else the
     checkpoint's `generation_config.json`, else HF's global default (so top_k = 50 unless someone says otherwise).  `None`
     counts as unset.  Keys other than the sampling settings (max_new_tokens, seed, ...) pass through.  Raises
     NotImplementedError for any setting this path cannot honour that is set away from HF's default (beam search, typical_p,
-    epsilon / eta cutoffs, top_h, no_repeat_ngram_size, bad_words_ids, suppress_tokens)."""
+    epsilon / eta cutoffs, top_h, no_repeat_ngram_size, bad_words_ids, suppress_tokens).
+    constraints=True: no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens and min_new_tokens are
+    resolved as well (explicit, else the file's, else None = off; 0 and [] count as off) and returned for `generate` instead of
+    raising; the other settings of that list still raise."""
     file_cfg = dict(llm_generation_config or {})
     bad = []
     for k, off in _HF_GEN_UNSUPPORTED.items():
+        if constraints and k in _HF_GEN_CONSTRAINTS:
+            continue
         v = explicit.get(k) if explicit.get(k) is not None else file_cfg.get(k)
         if v is not None and v != off and v != []:
             bad.append(f"{k}={v!r}")
@@ -425,6 +434,10 @@ def resolve_generation_kwargs(llm_generation_config: dict, **explicit) -> dict:
     for k, default in _HF_GEN_DEFAULTS.items():
         v = explicit.get(k)
         out[k] = v if v is not None else (file_cfg[k] if file_cfg.get(k) is not None else default)
+    if constraints:
+        for k in _HF_GEN_CONSTRAINTS:
+            v = explicit.get(k) if explicit.get(k) is not None else file_cfg.get(k)
+            out[k] = None if (v is None or v == [] or (v == 0 and not isinstance(v, bool))) else v
     return out
 
 
@@ -437,6 +450,81 @@ def check_sampling_args(top_k=None, min_p=None, repetition_penalty=None) -> None
         raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k}")
     if min_p is not None and not (isinstance(min_p, (int, float)) and 0 <= min_p <= 1.0):
         raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+
+
+def _is_id(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool) and v >= 0
+
+
+def check_constraint_args(no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None,
+                          min_new_tokens=None, vocab: Optional[int] = None) -> None:
+    """HF's argument checks for the banning processors (TF:generation/logits_process.py NoRepeatNGramLogitsProcessor,
+    NoBadWordsLogitsProcessor, MinNewTokensLengthLogitsProcessor; SuppressTokens[AtBegin]LogitsProcessor take a list of ids);
+    None means off.  vocab (where it is known): every id has to lie below it, since only ids in [0, vocab) can be banned."""
+    n = no_repeat_ngram_size
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or n <= 0):
+        raise ValueError(f"`no_repeat_ngram_size` (HF's `ngram_size`) has to be a strictly positive integer, but is {n}")
+    if bad_words_ids is not None:
+        if not isinstance(bad_words_ids, list) or len(bad_words_ids) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+        if any(not isinstance(w, list) or len(w) == 0 for w in bad_words_ids):
+            raise ValueError(f"`bad_words_ids` has to be a list of non-empty lists, but is {bad_words_ids}.")
+        if any(not _is_id(t) for w in bad_words_ids for t in w):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad_words_ids}.")
+    for name, ids in (("suppress_tokens", suppress_tokens), ("begin_suppress_tokens", begin_suppress_tokens)):
+        if ids is not None and (not isinstance(ids, (list, tuple)) or any(not _is_id(t) for t in ids)):
+            raise ValueError(f"`{name}` has to be a list of non-negative integers, but is {ids}")
+    m = min_new_tokens
+    if m is not None and (isinstance(m, bool) or not isinstance(m, int) or m < 0):
+        raise ValueError(f"`min_new_tokens` has to be a non-negative integer, but is {m}")
+    if vocab is not None:
+        for name, ids in (("bad_words_ids", [t for w in bad_words_ids or [] for t in w]), ("suppress_tokens", suppress_tokens or []),
+                          ("begin_suppress_tokens", begin_suppress_tokens or [])):
+            over = [t for t in ids if t >= vocab]
+            if over:
+                raise ValueError(f"`{name}` holds token id {over[0]}, the vocabulary has {vocab} tokens")
+    n_sup = len(suppress_tokens or [])                                       # they join the word table as one-token words
+    if len(bad_words_ids or []) + n_sup > H.CONSTRAINT_MAX_WORDS or sum(len(w) for w in bad_words_ids or []) + n_sup > H.CONSTRAINT_MAX_WORD_IDS:
+        raise ValueError(f"`bad_words_ids` and `suppress_tokens` together hold more than {H.CONSTRAINT_MAX_WORDS} words or "
+                         f"{H.CONSTRAINT_MAX_WORD_IDS} ids")
+
+
+def constraint_tables(eos_token_ids=None, no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None,
+                      begin_suppress_tokens=None, min_new_tokens=None) -> dict:
+    """The host form of a call's constraint tables, as `desta_logit_constraints_bf16` takes them: `[e]` words of an EOS id e
+    dropped (NoBadWordsLogitsProcessor.__init__ does that), suppress_tokens appended as one-token words (EOS not filtered there),
+    the words flattened to ids + offsets; min_new_tokens off when the call has no EOS."""
+    eos = [int(e) for e in (eos_token_ids or [])]
+    words = [[int(t) for t in w] for w in (bad_words_ids or []) if not (len(w) == 1 and int(w[0]) in eos)]
+    words += [[int(t)] for t in (suppress_tokens or [])]
+    off = [0]
+    for w in words:
+        off.append(off[-1] + len(w))
+    begin = [int(t) for t in (begin_suppress_tokens or [])]
+    min_new = int(min_new_tokens or 0) if eos else 0
+    return dict(no_repeat_ngram=int(no_repeat_ngram_size or 0), word_ids=[t for w in words for t in w], word_off=off, n_words=len(words),
+                begin_ids=begin, eos_ids=eos if min_new else [], min_new_tokens=min_new)
+
+
+class ConstraintPlan:
+    """The constraints of one generate() call on the device, built once: the int32 tables of `constraint_tables` and the scalar
+    settings.  `active` is False when every rule is off (the loop then runs as without a plan); `apply` is one
+    `H.logit_constraints` launch."""
+
+    def __init__(self, device, eos_token_ids=None, no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None,
+                 begin_suppress_tokens=None, min_new_tokens=None):
+        t = constraint_tables(eos_token_ids, no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens)
+
+        def dev(ids):
+            return torch.tensor(ids, dtype=torch.int32, device=device) if ids else None
+        ids = t["word_ids"] + t["begin_ids"] + t["eos_ids"]
+        self.kw = dict(no_repeat_ngram=t["no_repeat_ngram"], word_ids=dev(t["word_ids"]), word_off=dev(t["word_off"]) if t["n_words"] else None,
+                       n_words=t["n_words"], n_word_ids=len(t["word_ids"]), begin_ids=dev(t["begin_ids"]), n_begin=len(t["begin_ids"]),
+                       eos_ids=dev(t["eos_ids"]), n_eos=len(t["eos_ids"]), min_new_tokens=t["min_new_tokens"], id_max=max(ids, default=-1))
+        self.active = bool(t["no_repeat_ngram"] or t["n_words"] or t["begin_ids"] or t["min_new_tokens"])
+
+    def apply(self, src, ld_src, dst, ld_dst, batch, width, cols, hist, hist_len, tail=None, step0=0) -> None:
+        H.logit_constraints(src, ld_src, dst, ld_dst, batch, width, cols, hist=hist, hist_len=hist_len, tail=tail, step0=step0, **self.kw)
 
 
 def check_logprobs_arg(n) -> None:
@@ -2248,10 +2336,11 @@ class CausalLMHIP:
         assert self._gen_kind == "bf16" or (self.spec_attention == "split" and self._verify_attn_rows(w - 1))
         return self._step_rows(tokens, cur, kv_start)
 
-    def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook, guided: bool = False) -> Optional[str]:
+    def _spec_reason(self, k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook, guided: bool = False,
+                     constrained: bool = False) -> Optional[str]:
         """Why a call with speculation on runs the plain loop all the same; None when it does not.  A guided call (`guidance_scale`)
-        always does.  The next three hold under scope "greedy" only; the FP8 KV cache is a reason unless `attention="split"` and the
-        G (k + 1) query rows per KV head fit the verify kernel."""
+        always does.  The next four hold under scope "greedy" only (constrained: the call has an active `ConstraintPlan`); the FP8 KV
+        cache is a reason unless `attention="split"` and the G (k + 1) query rows per KV head fit the verify kernel."""
         if guided:
             return "guidance_scale"
         if getattr(self, "spec_scope", "greedy") != "all":
@@ -2261,6 +2350,8 @@ class CausalLMHIP:
                 return "repetition_penalty"
             if logprobs is not None:
                 return "logprobs"
+            if constrained:
+                return "logit_constraints"
         if forced_tokens is not None:
             return "forced_tokens"
         if layer_hook is not None:
@@ -2285,7 +2376,8 @@ class CausalLMHIP:
         return min(n_new, int(torch.where(hit.any(dim=1), done_at + 1, torch.full_like(done_at, n_new)).max()))
 
     def _speculative_loop(self, logits, out, finished, eos, S: int, k: int, kv_start, pad_token_id: int, collect_logits: bool, draft_tokens, lookup_ids,
-                          pick: Optional[dict] = None, pen_hist: Optional[torch.Tensor] = None, logprobs: Optional[int] = None):
+                          pick: Optional[dict] = None, pen_hist: Optional[torch.Tensor] = None, logprobs: Optional[int] = None,
+                          constraints: Optional["ConstraintPlan"] = None):
         """The decode loop of `generate_greedy` with k drafts per step, on its `out` [B, T] / `finished` / `eos`.  Token 0 is the
         prompt pass's; then, with n tokens emitted and the last of them (not yet in the cache) due at slot cur = S + n - 1: draft ->
         `verify_step` on [last, drafts] -> the pick of all M rows -> `H.spec_accept`, which emits a >= 1 tokens for every row (the
@@ -2298,15 +2390,27 @@ class CausalLMHIP:
         accept kernel's store into `out` is the store into it, and row j adds the chunk's j drafts in front of it.  The lookup
         history carries -1 at pads and audio slots and holds the spliced transcription; the accept kernel writes it as well.
         logprobs = n: one `H.topk_logprobs` launch over the M rows per verify step, in front of the host wait; row (b, j) scores the
-        token it emits, -1 (0 / -1 / 0) on a row finished before the step or behind the first EOS of its run."""
+        token it emits, -1 (0 / -1 / 0) on a row finished before the step or behind the first EOS of its run.
+        constraints (an active `ConstraintPlan`; `pen_hist` is then set as well): one `H.logit_constraints` launch in front of
+        every pick writes the banned scores into a [B (k + 1), Vp] scratch the pick reads, row (b, j) with the history `pen_hist[b,
+        :Pp + n]` + the chunk's j drafts at emitted position n + j, as the plain loop bans there; `logprobs` and collect_logits
+        keep reading the raw rows."""
         dev, w, (B, T) = self.dev, k + 1, out.shape
         sp = self._spec_alloc(B, k)
         pred, inp, draft, taken, taken_host, event = (sp[n] for n in ("pred", "inp", "draft", "taken", "taken_host", "event"))
         hist = row_start = None
         P = 0
         Pp = 0 if pen_hist is None else int(pen_hist.shape[1]) - T
+        con_scores = None
+        if constraints is not None:                                          # made once per shape; the kernel leaves the zero pad columns alone
+            if getattr(self, "_con_scratch", None) is None or self._con_scratch.shape != (B * w, self.Vp):
+                self._con_scratch = torch.zeros(B * w, self.Vp, dtype=BF16, device=dev)
+            con_scores = self._con_scratch
 
-        def first_pick():                                                    # the plain loop's launch at step 0
+        def first_pick(logits):                                              # the plain loop's launch at step 0
+            if constraints is not None:
+                constraints.apply(logits, self.Vp, con_scores, self.Vp, B, 1, self.V, pen_hist, Pp, step0=0)
+                logits = con_scores
             if pick is None:
                 H.argmax_bf16(logits, self.Vp, B, self.V, self.g_next)
             elif pick["chain"]:
@@ -2317,6 +2421,9 @@ class CausalLMHIP:
                 H.sample_top_p(logits, self.Vp, B, self.V, pick["temperature"], pick["top_p"], pick["seed"], 0, self.g_next)
 
         def verify_pick(vl, n):                                              # row j: the plain loop's launch at step n + j
+            if constraints is not None:
+                constraints.apply(vl, self.Vp, con_scores, self.Vp, B, w, self.V, pen_hist, Pp + n, tail=inp, step0=n)
+                vl = con_scores
             if pick is None:
                 H.argmax_bf16(vl, self.Vp, B * w, self.V, pred)
             elif pick["chain"]:
@@ -2342,7 +2449,7 @@ class CausalLMHIP:
                 hist[:, :P] = lookup_ids.to(dev, torch.int64)
             row_start = kv_start if P else torch.zeros(B, dtype=torch.int32, device=dev)
         steps_logits = [logits[:, :self.V].clone()] if collect_logits else None
-        first_pick()
+        first_pick(logits)
         out[:, 0] = self.g_next
         if hist is not None:
             hist[:, P] = self.g_next
@@ -2399,7 +2506,8 @@ class CausalLMHIP:
                         after_prompt=None, top_k: Optional[int] = None, min_p: Optional[float] = None,
                         repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None, chunk_hook=None,
                         logprobs: Optional[int] = None, speculate: Optional[int] = None, draft_tokens: Optional[torch.Tensor] = None,
-                        lookup_ids: Optional[torch.Tensor] = None, guidance_scale: Optional[float] = None):
+                        lookup_ids: Optional[torch.Tensor] = None, guidance_scale: Optional[float] = None,
+                        constraints: Optional["ConstraintPlan"] = None):
         """Prompt pass + KV-cached decode (greedy, or temperature / top-p sampling with the library's counter RNG).  Returns new token ids [B, n_new] (int64; finished sequences are
         filled with pad_token_id, generation stops early once every sequence has produced an EOS), and, with
         collect_logits, the per-step logits [n_new, B, V] (bf16).  `forced_tokens` [B, T] teacher-forces the
@@ -2428,7 +2536,15 @@ class CausalLMHIP:
         `forced_tokens`, `prompt_ids` (the conditional prompts') and `logprobs` have Bc rows; EOS is judged per sequence.
         `logprobs` still reports the model's own distribution: the raw CONDITIONAL rows.  collect_logits returns the raw logits of
         all rows, [n_new, 2 Bc, V], conditional rows first: the values the guidance kernel read.  Speculation does not cover a
-        guided call (`spec_stats["reason"] == "guidance_scale"`)."""
+        guided call (`spec_stats["reason"] == "guidance_scale"`).
+        constraints (a `ConstraintPlan`; None or an inactive one: off, no launch, no allocation): HF's banning processors,
+        no_repeat_ngram_size / bad_words_ids / suppress_tokens / begin_suppress_tokens / min_new_tokens.  One
+        `H.logit_constraints` launch per step sets the banned scores to -inf in front of the pick (and behind `H.cfg_scores`: in
+        place on the guided scores); every other score keeps its bits, and the pickers never keep a -inf score.  The history the
+        rules see is the penalty's above, kept with a plan even without a chain.  Without guidance the pass runs in place on the
+        step's logits, or into a [Bc, Vp] scratch when `logprobs` or collect_logits read them: those keep reporting the raw model
+        output.  A row with every token banned yields token 0.  Under `set_speculative(k, scope="all")` the verify rows go through
+        the same pass (`_speculative_loop`); under scope "greedy" the plain loop runs (`spec_stats["reason"] == "logit_constraints"`)."""
         assert max_new_tokens >= 1
         check_guidance_arg(guidance_scale)
         guided = guidance_scale is not None and float(guidance_scale) != 1.0
@@ -2440,7 +2556,9 @@ class CausalLMHIP:
         chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0)))
         check_speculative_arg(speculate)
         spec_k = (self.speculative if speculate is None else speculate) or 0
-        spec_reason = self._spec_reason(spec_k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook, guided=guided) if spec_k else "off"
+        con = constraints if constraints is not None and constraints.active else None
+        spec_reason = self._spec_reason(spec_k, B, do_sample, use_pen, logprobs, forced_tokens, layer_hook, guided=guided,
+                                        constrained=con is not None) if spec_k else "off"
         # a verify chunk writes up to k slots past the last accepted one: cache, cos / sin table and workspaces get k more slots
         Smax = S + max_new_tokens + (spec_k if spec_reason is None else 0)
         self._gen_alloc(B, Smax)
@@ -2459,7 +2577,7 @@ class CausalLMHIP:
         finished = torch.zeros(Bc, dtype=torch.bool, device=dev)
         eos = None if not eos_token_ids else torch.tensor(list(eos_token_ids), dtype=torch.int64, device=dev)
         P = 0
-        if chain:                                                            # token history = [prompt ids,] emitted tokens: out is its tail
+        if chain or con is not None:                                         # token history = [prompt ids,] emitted tokens: out is its tail
             P = 0 if prompt_ids is None else int(prompt_ids.shape[1])
             hist = torch.full((Bc, P + max_new_tokens), int(pad_token_id), dtype=torch.int64, device=dev)
             if P:
@@ -2471,7 +2589,7 @@ class CausalLMHIP:
                 pick = dict(chain=chain, do_sample=do_sample, temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p),
                             min_p=float(min_p or 0.0), repetition_penalty=float(repetition_penalty) if use_pen else 1.0, seed=seed)
             return self._speculative_loop(logits, out, finished, eos, S, spec_k, kv_start, int(pad_token_id), collect_logits, draft_tokens, lookup_ids,
-                                          pick=pick, pen_hist=hist if chain else None, logprobs=logprobs)
+                                          pick=pick, pen_hist=hist if chain or con is not None else None, logprobs=logprobs, constraints=con)
         steps_logits = []
         if logprobs is not None:
             lp_tok = torch.zeros(Bc, max_new_tokens, dtype=F32, device=dev)
@@ -2487,11 +2605,17 @@ class CausalLMHIP:
             if getattr(self, "_cfg_scratch", None) is None or self._cfg_scratch.shape != (Bc, self.Vp):
                 self._cfg_scratch = torch.zeros(Bc, self.Vp, dtype=BF16, device=dev)
             scores = self._cfg_scratch
+        elif con is not None and (logprobs is not None or collect_logits):   # the raw logits are read again: the banned copy goes elsewhere
+            if getattr(self, "_con_scratch", None) is None or self._con_scratch.shape != (Bc, self.Vp):
+                self._con_scratch = torch.zeros(Bc, self.Vp, dtype=BF16, device=dev)
+            scores = self._con_scratch
         for t in range(max_new_tokens):
             if collect_logits:
                 steps_logits.append(logits[:, :self.V].clone())
             if guided:
                 H.cfg_scores(logits[:Bc], logits[Bc:], self.Vp, Bc, self.V, float(guidance_scale), scores, self.Vp)
+            if con is not None:                                              # guided: in place on the guided scores
+                con.apply(scores if guided else logits, self.Vp, scores, self.Vp, Bc, 1, self.V, hist, P + t, step0=t)
             if chain:
                 H.sample(scores, self.Vp, Bc, self.V, g_next, do_sample=do_sample, temperature=float(temperature),
                          top_k=int(top_k or 0), top_p=float(top_p), min_p=float(min_p or 0.0),
@@ -3018,7 +3142,8 @@ class DeSTA25AudioModel:
     @torch.no_grad()
     def _generate_step(self, inputs, pad_token_id, temperature=0.7, top_p=0.9, max_new_tokens=512, do_sample=True,
                        eos_token_id=None, forced_tokens=None, collect_logits=False, seed=0, top_k=None, min_p=None,
-                       repetition_penalty=None, prompt_in_history=False, logprobs=None, draft_tokens=None, guidance_scale=None):
+                       repetition_penalty=None, prompt_in_history=False, logprobs=None, draft_tokens=None, guidance_scale=None,
+                       no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=None):
         """Reference `_generate_step` (modeling_desta25.py:1358-1431): audio features spliced into the prompt
         embeddings, then `llm_model.generate(inputs_embeds=…)` — here the KV-cached decoder on the HIP path.
         Returns ONLY the new tokens, as HF does for inputs_embeds prompts.  do_sample=False: greedy (temperature / top_p
@@ -3038,10 +3163,20 @@ class DeSTA25AudioModel:
         [B, max_new_tokens] (the proposal for emitted position t, -1 = none: tests and benchmarks).
         guidance_scale = g (None or 1: off): classifier-free guidance, HF's `guidance_scale` with a negative prompt.  `inputs` hold
         2 Bc rows, the Bc conditional prompts and then the unconditional prompt of each (audio spans may lie in any of them); the
-        result and `forced_tokens` have Bc rows (`CausalLMHIP.generate_greedy`).  Not with ORCA deep injection."""
+        result and `forced_tokens` have Bc rows (`CausalLMHIP.generate_greedy`).  Not with ORCA deep injection.
+        no_repeat_ngram_size / bad_words_ids / suppress_tokens / begin_suppress_tokens / min_new_tokens: HF's banning processors of
+        the same names (NoRepeatNGram, NoBadWords, SuppressTokens, SuppressTokensAtBegin, MinNewTokensLength); None = off.  They see
+        the penalty's history (empty for an inputs_embeds prompt, the prompt ids with `prompt_in_history`), `[eos]` bad words are
+        dropped, min_new_tokens bans every EOS id for the first m emitted tokens, and begin_suppress_tokens act on the first one.
+        One launch per step sets the banned scores to -inf in front of the pick and behind the guidance
+        (`desta_logit_constraints_bf16`); `logprobs` and collect_logits keep the raw model output.  If every token of a step is
+        banned the step yields token 0."""
         check_sampling_args(top_k, min_p, repetition_penalty)
         check_logprobs_arg(logprobs)
         check_guidance_arg(guidance_scale)
+        check_constraint_args(no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens,
+                              vocab=getattr(getattr(self, "llm", None), "V", None))
+        constrained = any(v is not None for v in (no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens))
         guided = guidance_scale is not None and float(guidance_scale) != 1.0
         if guided and self.orca is not None:
             raise NotImplementedError("guidance_scale with ORCA deep injection (orca_hybrid): the injection hook takes one audio per row, "
@@ -3098,6 +3233,10 @@ class DeSTA25AudioModel:
                 if self.llm.speculative:                                     # the lookup history: the ids the prompt embeds, -1 at pads and audio slots
                     lookup = src.view(B, S).to(torch.int64)
                     lookup = torch.where((attention_mask == 0) | (lookup < 0), torch.full_like(lookup, -1), lookup)
+                extra = {}
+                if constrained:                                              # the device tables, once per call
+                    extra["constraints"] = ConstraintPlan(dev, eos, no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens,
+                                                          min_new_tokens)
                 return self.llm.generate_greedy(fill, B, S, kv_start, int(max_new_tokens), int(pad_token_id), eos, draft_tokens=draft_tokens,
                                                 lookup_ids=lookup,
                                                 forced_tokens=forced_tokens, collect_logits=collect_logits, do_sample=bool(do_sample),
@@ -3105,15 +3244,17 @@ class DeSTA25AudioModel:
                                                 top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after,
                                                 top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty,
                                                 prompt_ids=(input_ids[:B // 2] if guided else input_ids) if prompt_in_history else None,
-                                                chunk_hook=chunk, logprobs=logprobs, guidance_scale=guidance_scale)
+                                                chunk_hook=chunk, logprobs=logprobs, guidance_scale=guidance_scale, **extra)
         finally:
             self.training = was_training
 
-    def hf_generation_kwargs(self, **explicit) -> dict:
+    def hf_generation_kwargs(self, *, constraints: bool = False, **explicit) -> dict:
         """`resolve_generation_kwargs(self.llm_generation_config, **explicit)`: the settings HF's `generate` would use for this
         checkpoint.  `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))` samples
-        as the reference does (modeling_desta25.py:1419-1427), top_k from the checkpoint or HF's default 50 included."""
-        return resolve_generation_kwargs(self.llm_generation_config, **explicit)
+        as the reference does (modeling_desta25.py:1419-1427), top_k from the checkpoint or HF's default 50 included.
+        constraints=True: the checkpoint's no_repeat_ngram_size / bad_words_ids / suppress_tokens / begin_suppress_tokens /
+        min_new_tokens come along for `generate` instead of raising."""
+        return resolve_generation_kwargs(self.llm_generation_config, constraints=constraints, **explicit)
 
     def _asr_whisper(self, waves) -> List[str]:
         """`perception.whisper.generate(input_features, attention_mask=None, max_new_tokens=128)` + `processor.batch_decode(...,
@@ -3174,7 +3315,8 @@ class DeSTA25AudioModel:
         return dict(token_logprobs=token_logprobs, top_logprobs=top, sum_logprob=[float(sum(r)) for r in token_logprobs])
 
     def generate(self, messages, temperature=0.7, top_p=0.9, do_sample=True, max_new_tokens=512, seed=0, top_k=None, min_p=None,
-                 repetition_penalty=None, logprobs=None, guidance_scale=None, negative_messages=None):
+                 repetition_penalty=None, logprobs=None, guidance_scale=None, negative_messages=None, no_repeat_ngram_size=None,
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=None):
         """The reference's chat-level `generate` (modeling_desta25.py:1491-1721): messages -> audio decode -> log-mel -> placeholder
         expansion of every `<|AUDIO|>` -> left-padded tokenisation, pad-shifted start positions, transcription ids ->
         `_generate_step` -> `GenerationOutput(text, audios, generated_ids)`.  Same messages schema, same errors; the front-end
@@ -3190,11 +3332,20 @@ class DeSTA25AudioModel:
         the prompt and under the negative prompt, in front of the penalty, temperature and filters.  `negative_messages`: one
         conversation per conversation of `messages`; None: the same chat without its audio (`guidance_negative_messages`), which
         pushes the answer towards what the audio says (audio-contrastive decoding).  Both run as one left-padded batch of twice
-        the rows; the output has one row per conversation of `messages` and lists their audios only."""
+        the rows; the output has one row per conversation of `messages` and lists their audios only.
+        no_repeat_ngram_size / bad_words_ids / suppress_tokens / begin_suppress_tokens / min_new_tokens: HF's hard constraints of
+        the same names, None = off (see `_generate_step`): no n-gram of that size twice, the listed token sequences / tokens never
+        (the listed begin tokens not as the first token), no EOS before m new tokens.  An audio chat matches them against the
+        answer alone, a text-only chat against prompt + answer, as HF does for `inputs_embeds` / `input_ids` prompts.  A
+        checkpoint's own settings: `model.generate(msgs, **model.hf_generation_kwargs(constraints=True))`."""
         check_sampling_args(top_k, min_p, repetition_penalty)
         check_logprobs_arg(logprobs)
         check_guidance_arg(guidance_scale)
+        cons = dict(no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
+                    begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens)
+        check_constraint_args(**cons, vocab=getattr(getattr(self, "llm", None), "V", None))
         extra = dict(top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty)
+        extra.update({k: v for k, v in cons.items() if v is not None})
         if logprobs is not None:
             extra["logprobs"] = logprobs
         if guidance_scale is not None and float(guidance_scale) != 1.0:

@@ -608,9 +608,11 @@ class DeSTA25Trainer:
     def _predict_step(self, batch: Dict[str, Any], generation_kwargs: Optional[Dict[str, Any]] = None) -> torch.Tensor:
         """desta_trainer.py:160-189: generate from the context part of the batch; decode when a tokenizer is attached.
         generation_kwargs `logprobs` = n: every prediction row also carries `token_logprobs` (its tokens up to and including the
-        first EOS, under the model's own distribution) and `avg_logprob`, their mean."""
+        first EOS, under the model's own distribution) and `avg_logprob`, their mean.  no_repeat_ngram_size, bad_words_ids,
+        suppress_tokens, begin_suppress_tokens and min_new_tokens reach `_generate_step` when set (None: not passed)."""
+        cons = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_new_tokens")
         gk = dict(temperature=0.7, top_p=0.9, max_new_tokens=128, do_sample=False, top_k=None, min_p=None, repetition_penalty=None,
-                  logprobs=None)
+                  logprobs=None, **{k: None for k in cons})
         cfg_gk = getattr(getattr(self.cfg, "model", None), "generation_kwargs", None) if self.cfg is not None else None
         for src in (cfg_gk, generation_kwargs):
             if src:
@@ -618,11 +620,15 @@ class DeSTA25Trainer:
         tok = self.processing_class
         eos_id = getattr(tok, "eos_token_id", None)
         pad_id = eos_id if eos_id is not None else 0
+
+        def plain(v):                                                        # a YAML list arrives as a config node: the checks want lists
+            return [plain(x) for x in v] if hasattr(v, "__iter__") and not isinstance(v, (str, bytes, dict)) else v
         ids = self.model._generate_step(batch, pad_token_id=pad_id, temperature=gk["temperature"], top_p=gk["top_p"],
                                         max_new_tokens=gk["max_new_tokens"], do_sample=gk["do_sample"],
                                         seed=self.global_step, top_k=gk["top_k"], min_p=gk["min_p"],
                                         repetition_penalty=gk["repetition_penalty"],
-                                        **({} if gk["logprobs"] is None else {"logprobs": gk["logprobs"]}))
+                                        **({} if gk["logprobs"] is None else {"logprobs": gk["logprobs"]}),
+                                        **{k: plain(gk[k]) for k in cons if gk[k] is not None})
         extras = None
         if gk["logprobs"] is not None:
             ids, lp = ids

@@ -722,6 +722,44 @@ int desta_sample_top_p_rows_bf16(const void* logits, int64_t ld, int batch, int 
                                  float temperature, float top_p, uint64_t seed, uint32_t step0,
                                  int64_t* out, uint8_t* keep_mask, void* stream);
 
+/* The hard constraints of HF's logits chain on the scores of one decode step (additive to ABI 8; `generate(no_repeat_ngram_size=,
+ * bad_words_ids=, suppress_tokens=, begin_suppress_tokens=, min_new_tokens=)`, the loop of `llm_model.generate`
+ * modeling_desta25.py:1419 / :1703): NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, SuppressTokensLogitsProcessor,
+ * SuppressTokensAtBeginLogitsProcessor and MinNewTokensLengthLogitsProcessor of TF:generation/logits_process.py, in the order
+ * of `_get_logits_processor` TF:generation/utils.py:1174-1290.  All five only set scores to -inf, so their order among
+ * themselves and against the repetition penalty (-inf stays -inf) does not show; the pass runs behind desta_cfg_scores_bf16
+ * and in front of the pickers, which never keep a -inf score.
+ * src bf16 [batch * width, ld_src], dst bf16 [batch * width, ld_dst], any (2-byte) alignment.  The grid is (batch, width),
+ * 1 <= width <= 8, the convention of desta_sample_rows_bf16: row (b, j) is row r = b * width + j, it picks emitted position
+ * t = step0 + j (a uint32 sum), and its history h, of length L = hist_len + j, is hist[b*hist_ld + 0 .. hist_len) followed by
+ * tail[b*tail_ld + 1 .. 1 + j) (the verify step's input; width == 1 never reads tail).  h is HF's `input_ids` of the row.  Every
+ * value of h is an ordinary token for matching, a -1 or an id >= cols included; only ids in [0, cols) can be banned.
+ *   no_repeat_ngram = n > 0: nothing while L + 1 < n; else h[i + n - 1] is banned for every 0 <= i <= L - n with
+ *                     h[i .. i + n - 1) == h[L - n + 1 .. L)  (n == 1: every token of h).
+ *   words ........... word w is word_ids[word_off[w] .. word_off[w + 1]), m ids (int32, DEVICE memory, word_off holds n_words + 1
+ *                     ascending offsets, the last one n_word_ids).  m == 1: the id is banned, always (suppress_tokens are passed
+ *                     as such words).  m > 1: the last id is banned iff m <= L and the last m - 1 tokens of h are the word's
+ *                     first m - 1: m <= L, not m - 1 <= L, as HF skips a word longer than the context (logits_process.py:1303).
+ *                     The caller drops [eos] words first, as HF does.
+ *   begin_ids ....... banned iff t == 0.
+ *   eos_ids ......... banned iff t < min_new_tokens; off when n_eos == 0.
+ * dst[r, c] = -inf (0xFF80) for a banned c, else src[r, c] bit for bit, c < cols; columns >= cols of dst are not written.  dst
+ * == src is allowed (equal pointers and strides; any other overlap is not): then only the banned entries are stored and src
+ * is not read.  A row with every token banned makes the pickers return token 0.  id_max is the largest id of the three
+ * tables as their builder knows it (-1 for none): the tables live on the device, so this is what the call can check.
+ * DESTA_EINVAL, nothing launched, unless: src, dst non-NULL; batch > 0; 0 < cols <= 262144; ld_src, ld_dst >= cols; width in
+ * 1..8; tail non-NULL and tail_ld >= width when width > 1; hist non-NULL and hist_ld >= hist_len when hist_len > 0; no size
+ * negative; n_words <= 65536 and n_words <= n_word_ids <= 1048576, with both tables non-NULL when n_words > 0; begin_ids /
+ * eos_ids non-NULL when counted; id_max < cols.  no_repeat_ngram == 0, n_words == 0, n_begin == 0 and min_new_tokens == 0
+ * (or n_eos == 0) each switch their rule off; with all off DESTA_OK is returned and nothing is launched or written.
+ * One 1024-thread block per row; the banned set is a 32 KiB LDS bitmap; no global atomics, no scratch. */
+int desta_logit_constraints_bf16(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int batch, int width, int cols,
+                                 const int64_t* hist, int64_t hist_ld, int hist_len, const int64_t* tail, int64_t tail_ld,
+                                 uint32_t step0, int no_repeat_ngram,
+                                 const int32_t* word_ids, const int32_t* word_off, int n_words, int n_word_ids,
+                                 const int32_t* begin_ids, int n_begin, const int32_t* eos_ids, int n_eos, int min_new_tokens,
+                                 int id_max, void* stream);
+
 /* desta_rope (forward) on a fused q|k|v projection [rows, ld] that ALSO appends the rotated K heads and the V heads of
  * row (b, s) to a KV cache slab: kv_cache + b*kv_batch_stride + (slot0 + s)*kv_row_stride, K heads then V heads.
  * This is what `DynamicCache.update` does inside `llm_model.generate` (modeling_desta25.py:1419) for the prompt
