@@ -1778,6 +1778,140 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_skinny_wide_fixup_kernel(Gem
     else epilogue4(p, 0, m, n, total(n));
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Tall skinny GEMM, 65 <= M <= 256 (decode at 65..256 rows; desta_gemm_tall_nt).  The wide kernel's item (64 weight rows, T = 4 MFMA
+// tiles, one K-slice) over all M rows in ONE launch: the 8 waves of a block form RG row groups of 64 rows (at most MF = 4 activation
+// fragments a wave, the wide kernel's largest accumulator set) times KW = 8 / RG waves that interleave the 64-k chunks of the item.
+// RG is 2 for M <= 128 and 4 above (M in 129..192 leaves the fourth group's waves without rows: they load nothing and only meet the
+// barriers), so the order of a sum depends on that class alone: chunk kw, kw + KW, .. of the slice in a wave, the KW waves of a row
+// group in kw order through LDS, the slices in slice order in gemm_bf16_nt_skinny_wide_fixup_kernel.  Wave = kw * RG + rg: the RG
+// waves that want the same weight chunk sit next to each other and ask for it within one group, so it comes from HBM once and from
+// the CU's L1 / the L2 for the others.  A wave skips the fragments behind M (wave-uniform), rows >= M of a live fragment and weight
+// rows >= N are computed on clamped addresses and never stored.  The walk, the slab, SwiGLU pairing, W8 and the row scale are the
+// wide kernel's.
+template <bool SWIGLU, int KW>
+struct TallWalk : WideWalk<SWIGLU> {
+    __device__ TallWalk(int N_, int ntiles_, int ks_, int cps_, int nchunks_) : WideWalk<SWIGLU>(N_, ntiles_, ks_, cps_, nchunks_) {
+        const int my_items = this->G / this->gpt;
+        this->gpt = (cps_ + KW - 1) / KW;                                // groups per item: one chunk per K-wave
+        this->G = my_items * this->gpt;
+    }
+    __device__ int chunk(const WideCursor& c, int kw) const { return c.slice * this->cps + kw + c.grp * KW; }
+};
+
+template <int RG, bool SWIGLU, bool W8>
+__global__ __launch_bounds__(512) void gemm_bf16_nt_skinny_tall_kernel(GemmArgs p, int ntiles, int ks, int cps, float* part) {
+    constexpr int T = 4, MF = 4, KW = 8 / RG;
+    __shared__ __attribute__((aligned(16))) char smem[8 * T * MF * 1024];
+    f32x4 (*red)[T * MF][64] = (f32x4 (*)[T * MF][64])smem;              // red[wave][t * MF + f][lane]
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int r = lane & 15, g = lane >> 4;
+    const int rg = wave % RG, kw = wave / RG, m0 = rg * 64;
+    const int mfw = min(MF, max(0, (p.M - m0 + 15) >> 4));               // live fragments of this wave's row group
+    const bf16_t* Bz = p.B + g * 16;
+    const char* Bq = (const char*)p.B + g * 16;                          // W8: one byte per element
+    const bf16_t* ap[MF];
+#pragma unroll
+    for (int f = 0; f < MF; ++f) ap[f] = p.A + (long)min(m0 + f * 16 + r, p.M - 1) * p.lda + g * 16;
+    const TallWalk<SWIGLU, KW> wk(p.N, ntiles, ks, cps, p.K >> 6);
+    const int G = wk.G;
+    const RowScale<W8> scaled{p.b_scale};
+    f32x4 acc[T][MF];
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+#pragma unroll
+        for (int f = 0; f < MF; ++f) acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    WideStage<MF, W8> sa, sb;
+    WideCursor lc = wk.first(), mc = lc;
+
+    // the KW partial tiles of row group grp, summed in kw order
+    auto reduced = [&](int grp, int t, int f) -> f32x4 {
+        f32x4 sum = red[grp][t * MF + f][lane];
+#pragma unroll
+        for (int w = 1; w < KW; ++w) sum += red[w * RG + grp][t * MF + f][lane];
+        return sum;
+    };
+    // park the accumulators, then the 8 waves share the (row group, tile, fragment) units of the item: the raw slab of the K-slice
+    // (ks > 1; the fix-up launch finishes it), the SwiGLU pair, or epilogue4
+    auto finish_item = [&](int tile, int slice) {
+#pragma unroll
+        for (int f = 0; f < MF; ++f)
+            if (f < mfw) {
+#pragma unroll
+                for (int t = 0; t < T; ++t) { red[wave][t * MF + f][lane] = acc[t][f]; acc[t][f] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+            }
+        __syncthreads();
+        const int tiles = (wk.ks == 1 && SWIGLU) ? 2 : T;
+        for (int u = wave; u < RG * tiles * MF; u += 8) {
+            const int grp = u / (tiles * MF), t = (u / MF) % tiles, f = u % MF, m = grp * 64 + f * 16 + r;
+            if (grp * 64 + f * 16 >= p.M) continue;
+            bool ok;
+            const int n = wk.wrow(tile, t, g * 4, ok);                   // N % 4 == 0: the four rows exist together
+            if (!ok || m >= p.M) continue;
+            if (wk.ks > 1) *(f32x4*)(part + ((long)slice * p.M + m) * wk.ntot + n) = reduced(grp, t, f);
+            else if (SWIGLU)
+                *(u16x4*)((bf16_t*)p.C + (long)m * p.ldc + n) = swiglu4_bf16(scaled(reduced(grp, t, f), n), scaled(reduced(grp, t + 2, f), p.N + n), p.alpha);
+            else epilogue4(p, 0, m, n, scaled(reduced(grp, t, f), n));
+        }
+        __syncthreads();                                                 // red is free again before the next item's partial tiles land
+    };
+
+#define TL_LOAD(S)                                                                          \
+    {                                                                                       \
+        const int cc = wk.chunk(lc, kw);                                                    \
+        if (cc < wk.chunk_end(lc) && mfw > 0) {                                             \
+            _Pragma("unroll") for (int t = 0; t < T; ++t) {                                 \
+                bool ok;                                                                    \
+                const long row = wk.wrow(lc.tile, t, r, ok);                                \
+                if constexpr (W8) {                                                         \
+                    S.wq[t] = *(const u32x4*)(Bq + row * p.ldb + (long)cc * 64);            \
+                } else {                                                                    \
+                    S.w0[t] = *(const bf16x8*)(Bz + row * p.ldb + (long)cc * 64);           \
+                    S.w1[t] = *(const bf16x8*)(Bz + row * p.ldb + (long)cc * 64 + 8);       \
+                }                                                                           \
+            }                                                                               \
+            _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                \
+                if (f < mfw) {                                                              \
+                    S.x0[f] = *(const bf16x8*)(ap[f] + (long)cc * 64);                      \
+                    S.x1[f] = *(const bf16x8*)(ap[f] + (long)cc * 64 + 8);                  \
+                }                                                                           \
+            }                                                                               \
+        }                                                                                   \
+        wk.advance(lc);                                                                     \
+    }
+#define TL_MMA(S)                                                                           \
+    {                                                                                       \
+        const int cc = wk.chunk(mc, kw);                                                    \
+        if (cc < wk.chunk_end(mc) && mfw > 0) {                                             \
+            bf16x8 w0[T], w1[T];                                                            \
+            _Pragma("unroll") for (int t = 0; t < T; ++t) {                                 \
+                if constexpr (W8) e4m3x16_to_bf16(S.wq[t], w0[t], w1[t]);                   \
+                else { w0[t] = S.w0[t]; w1[t] = S.w1[t]; }                                  \
+            }                                                                               \
+            _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                \
+                if (f < mfw) {                                                              \
+                    _Pragma("unroll") for (int t = 0; t < T; ++t) {                         \
+                        acc[t][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0[t], S.x0[f], acc[t][f], 0, 0, 0); \
+                        acc[t][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[t], S.x1[f], acc[t][f], 0, 0, 0); \
+                    }                                                                       \
+                }                                                                           \
+            }                                                                               \
+        }                                                                                   \
+        if (mc.grp == wk.gpt - 1) finish_item(mc.tile, mc.slice);                           \
+        wk.advance(mc);                                                                     \
+    }
+
+    if (G > 0) TL_LOAD(sa)
+    for (int gi = 0; gi < G; gi += 2) {
+        if (gi + 1 < G) TL_LOAD(sb)
+        TL_MMA(sa)
+        if (gi + 2 < G) TL_LOAD(sa)
+        if (gi + 1 < G) TL_MMA(sb)
+    }
+#undef TL_LOAD
+#undef TL_MMA
+}
+
 }  // namespace
 
 static int g_last_kernel = 0;      // kernel family of the most recent launch: 1 = 128x128, 2 = 256x256 (+ split-K fix-up), 3 = skinny
@@ -2153,6 +2287,33 @@ extern "C" int desta_gemm_wide_nt(const desta_gemm_desc* d, const float* b_scale
     if (pl.ks > 1) {
         wide_fixup_launch(a, pl, b_scale, st);
         DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny_wide_fixup");
+    }
+    g_last_kernel = 3;
+    return DESTA_OK;
+}
+
+// Decode projections at 65..256 rows: the tall skinny kernel, one weight pass for all rows.  Operands, checks, K-slice plan and
+// fix-up launch as desta_gemm_wide_nt; the row-group count (2 up to 128 rows, 4 above) is the only thing M decides.
+extern "C" int desta_gemm_tall_nt(const desta_gemm_desc* d, const float* b_scale, void* stream) {
+    if (const int e = decode_check_args("gemm_tall", d, b_scale, DecodeLimits{65, 256, b_scale ? 16 : 8, 0, false, 16, false, false, 0})) return e;
+    const GemmArgs a = decode_gemm_args(d, b_scale);
+    const bool swiglu = d->act == 4;
+    const int ntiles = swiglu ? (d->N + 31) / 32 : (d->N + 63) / 64;
+    WidePlan pl;                                                         // 64-k chunks, at least 16 a slice: the wide kernel's slices
+    if (const int e = wide_plan("gemm_tall", d, ntiles, d->K / BK, 16, swiglu ? 2L * d->N : d->N, &pl)) return e;
+    hipStream_t st = (hipStream_t)stream;
+#define TL_LAUNCH(RG_) \
+    do { if (swiglu && b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_tall_kernel<RG_, true, true>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); \
+         else if (swiglu) hipLaunchKernelGGL((gemm_bf16_nt_skinny_tall_kernel<RG_, true, false>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); \
+         else if (b_scale) hipLaunchKernelGGL((gemm_bf16_nt_skinny_tall_kernel<RG_, false, true>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); \
+         else hipLaunchKernelGGL((gemm_bf16_nt_skinny_tall_kernel<RG_, false, false>), pl.grid, dim3(512), 0, st, a, ntiles, pl.ks, pl.cps, pl.part); } while (0)
+    if (d->M <= 128) TL_LAUNCH(2);
+    else TL_LAUNCH(4);
+#undef TL_LAUNCH
+    DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny_tall");
+    if (pl.ks > 1) {
+        wide_fixup_launch(a, pl, b_scale, st);
+        DESTA_CHECK_LAUNCH("gemm_bf16_nt_skinny_tall_fixup");
     }
     g_last_kernel = 3;
     return DESTA_OK;

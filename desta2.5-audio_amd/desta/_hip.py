@@ -218,6 +218,22 @@ def gemm_wide(A, B, out, M, N, K, *, scale=None, lda=None, ldb=None, ldc=None, r
     return out
 
 
+_gemm_tall = _sig("desta_gemm_tall_nt", C.POINTER(GemmDesc), vp, vp)
+GEMM_TALL_CALLS = 0                # tall (65 <= M <= 256) weight-streaming projections issued by this process
+DECODE_TALL_MAX_ROWS = 256         # rows per KV-cached step a model may opt into (`set_decode_rows`): what `gemm_tall` takes
+
+
+def gemm_tall(A, B, out, M, N, K, *, scale=None, lda=None, ldb=None, ldc=None, residual=None, ldr=None, act=0, alpha=1.0):
+    """out[M,N] = act(alpha * A[M,K] @ B[N,K]^T) + residual for 65 <= M <= 256: `gemm_wide`'s operands and features at more rows,
+    every weight byte still read once.  The order of a sum depends on N, K and the row-group count (2 for M <= 128, 4 above), so
+    inside one class a row's bits do not depend on M or on where the row sits; they are not `gemm_wide`'s bits."""
+    global GEMM_TALL_CALLS
+    d = _decode_desc(A, B, out, M, N, K, lda, ldb, ldc, residual, ldr, act, alpha, workspace=True)
+    check(_gemm_tall(C.byref(d), p(scale), stream()), "desta_gemm_tall_nt")
+    GEMM_TALL_CALLS += 1
+    return out
+
+
 _quantize_rows_mxfp4 = _sig("desta_quantize_rows_mxfp4", vp, i32, i32, i64, vp, i64, vp, i64, vp)
 _gemm_w4 = _sig("desta_gemm_w4a16_nt", C.POINTER(GemmDesc), vp, i64, vp)
 GEMM_W4_CALLS = 0                  # weight-only MXFP4 projections issued by this process

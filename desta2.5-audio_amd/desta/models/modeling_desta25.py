@@ -535,14 +535,48 @@ def check_logprobs_arg(n) -> None:
         raise ValueError(f"`logprobs` has to be None or an integer in [0, {H.TOPK_LOGPROBS_MAX}], but is {n!r}")
 
 
-def check_decode_rows(B: int, guided: bool = False) -> None:
-    """A KV-cached decode step streams the weights once for all its rows; its projections take at most H.DECODE_MAX_ROWS of them.
-    guided: B counts the unconditional rows of a `guidance_scale` call as well."""
-    if B > H.DECODE_MAX_ROWS:
+def check_decode_rows(B: int, guided: bool = False, limit: Optional[int] = None) -> None:
+    """A KV-cached decode step streams the weights once for all its rows; its projections take at most H.DECODE_MAX_ROWS of them,
+    or the model's `set_decode_rows` ceiling (`limit`).  guided: B counts the unconditional rows of a `guidance_scale` call as well."""
+    limit = H.DECODE_MAX_ROWS if limit is None else limit
+    if B > limit:
         if guided:
             raise ValueError(f"generate: guidance_scale doubles the rows (one unconditional row per sequence): {B // 2} sequences are {B} rows, "
-                             f"the KV-cached decode step takes at most {H.DECODE_MAX_ROWS}: split the batch")
-        raise ValueError(f"generate: a batch of {B} sequences, the KV-cached decode step takes at most {H.DECODE_MAX_ROWS}: split the batch")
+                             f"the KV-cached decode step takes at most {limit}: split the batch")
+        raise ValueError(f"generate: a batch of {B} sequences, the KV-cached decode step takes at most {limit}: split the batch")
+
+
+def check_decode_rows_arg(n) -> None:
+    """`set_decode_rows`: None or H.DECODE_MAX_ROWS (the default ceiling) or an int up to H.DECODE_TALL_MAX_ROWS."""
+    if n is None:
+        return
+    if isinstance(n, bool) or not isinstance(n, int) or not H.DECODE_MAX_ROWS <= n <= H.DECODE_TALL_MAX_ROWS:
+        raise ValueError(f"decode_rows must be None or an int in {H.DECODE_MAX_ROWS}..{H.DECODE_TALL_MAX_ROWS}, got {n!r}")
+
+
+PERCEPTION_SLICE = 64                               # audios per encoder + connector call of generate() above that many (H.DECODE_MAX_ROWS)
+TALL_PREFILL_ROWS = 16384                         # rows of one prompt chunk above H.DECODE_MAX_ROWS sequences: a memory bound
+TALL_GEMM_ROWS = 8192                               # `tall_rows_to_gemm`: bf16 weight rows from which the tile GEMM takes a tall step's projection
+TALL_GEMM_ROWS_ABOVE_128 = 6144                     # ... and from which it does at more than 128 rows
+
+
+def tall_rows_to_gemm(M: int, weight_rows: int) -> bool:
+    """bf16 projections of a step of more than H.DECODE_MAX_ROWS rows that go to `H.gemm` instead of `H.gemm_tall`: a rule of the
+    shape alone, from the five Llama-3.1-8B shapes at M = 65, 128, 192, 256 (DESIGN §3 "Decode at batch 65–256").  The tile GEMM
+    won gate|up (28672 weight rows) and the lm_head (128256) at every M and q|k|v (6144) at M = 192 and 256; `gemm_tall` won o and
+    down (4096) at every M and q|k|v at M = 65 and 128.  The thresholds (TALL_GEMM_ROWS, TALL_GEMM_ROWS_ABOVE_128) sit between
+    those shapes."""
+    return weight_rows >= TALL_GEMM_ROWS or (weight_rows >= TALL_GEMM_ROWS_ABOVE_128 and M > 128)
+
+
+def tall_prefill_chunk(B: int) -> Optional[int]:
+    """Chunk of the prompt pass of more than H.DECODE_MAX_ROWS sequences where `set_prefill_chunk` names none: the largest multiple
+    of 16 positions with B * chunk <= TALL_PREFILL_ROWS rows (B = 65: 240, 128: 128, 256: 64).  A memory rule: the training
+    `forward` keeps a save set per layer and prompt row, the lean pass one set of TALL_PREFILL_ROWS rows (about 2.3 GB at
+    Llama-3.1-8B's widths); nothing was tuned.  None at or under H.DECODE_MAX_ROWS sequences: nothing changes there."""
+    if B <= H.DECODE_MAX_ROWS:
+        return None
+    return max(PREFILL_CHUNK_MIN, TALL_PREFILL_ROWS // B // 16 * 16)
 
 
 def check_guidance_arg(g) -> None:
@@ -1735,6 +1769,37 @@ class CausalLMHIP:
         self.spec_attention = "forward"             # `set_speculative(k, attention=...)`: "forward" = the causal forward kernel, "split" = `H.attention_verify{,_kv8}`
         self._step1 = self._spec = None             # `_step_alloc` sets of the plain step (`_gen_alloc`) and of the verify step (`_spec_alloc`)
         self.spec_stats = None
+        self.decode_rows = None                     # `set_decode_rows`: row ceiling of a KV-cached step; None = H.DECODE_MAX_ROWS
+
+    def set_decode_rows(self, n: Optional[int]) -> None:
+        """Row ceiling of a KV-cached step (sequences of a plain step, 2 Bc under `guidance_scale`, B (k + 1) of a verify step):
+        None or 64 (default) = H.DECODE_MAX_ROWS, what `H.gemm_wide` takes; an int in 65..H.DECODE_TALL_MAX_ROWS lets steps of more
+        than 64 rows run, their projections through `H.gemm_tall` on bf16 or FP8 decode weights (one weight pass per step whatever
+        the rows; MXFP4 decode weights stay at 64 rows and say so).  Steps of at most 64 rows run what they ran before.  Above 64
+        sequences the prompt pass is the lean `prefill`, in chunks of `tall_prefill_chunk(B)` positions unless `set_prefill_chunk`
+        names a size."""
+        check_decode_rows_arg(n)
+        self.decode_rows = None if n in (None, H.DECODE_MAX_ROWS) else n
+
+    decode_rows: Optional[int] = None               # (class defaults: the settings of a model nobody has set)
+    decode_weights: str = "bf16"
+
+    @property
+    def row_limit(self) -> int:
+        """Rows a KV-cached step of this model takes: `set_decode_rows`, or H.DECODE_MAX_ROWS by default and with MXFP4 decode
+        weights, which have no kernel above it."""
+        return H.DECODE_MAX_ROWS if self.decode_weights == "mxfp4" else (self.decode_rows or H.DECODE_MAX_ROWS)
+
+    def check_rows(self, B: int, guided: bool = False) -> None:
+        """`check_decode_rows` at this model's ceiling; under MXFP4 decode weights the rows `set_decode_rows` would admit say so."""
+        if self.decode_weights == "mxfp4" and H.DECODE_MAX_ROWS < B <= (self.decode_rows or H.DECODE_MAX_ROWS):
+            raise ValueError(f"generate: {B} rows in a KV-cached step with MXFP4 decode weights: `gemm_w4` takes at most {H.DECODE_MAX_ROWS} "
+                             f"(`set_decode_rows` covers bf16 and FP8 decode weights): split the batch or set another weight kind")
+        check_decode_rows(B, guided, self.row_limit)
+
+    def _prompt_chunk(self, B: int) -> Optional[int]:
+        """Positions per chunk of generate()'s prompt pass for B rows: `set_prefill_chunk`, else `tall_prefill_chunk` (None = `forward`)."""
+        return self.prefill_chunk if self.prefill_chunk is not None else tall_prefill_chunk(B)
 
     def set_speculative(self, k: Optional[int], scope: str = "greedy", attention: str = "forward") -> None:
         """generate(): None or 0 (default) = one token per sequence per pass over the weights; an int k in 1..7 = draft and
@@ -1755,7 +1820,7 @@ class CausalLMHIP:
         plain loop's own rule at the step's first row (the forward kernel otherwise); row j of that kernel is the plain step's
         split-KV result at slot cur + j bit for bit, so from that slot on both loops run one attention arithmetic.  On the FP8 KV
         cache, where only "split" speculates, at every cur.
-        Under both scopes `forced_tokens`, a `layer_hook` (ORCA), B * (k + 1) > H.DECODE_MAX_ROWS and the FP8 KV cache (with
+        Under both scopes `forced_tokens`, a `layer_hook` (ORCA), B * (k + 1) > `row_limit` (H.DECODE_MAX_ROWS, or `set_decode_rows`) and the FP8 KV cache (with
         attention = "forward", or with more than H.VERIFY_ATTN_MAX_ROWS query rows per KV head) run the plain loop; `spec_stats`
         says which ran and why."""
         check_speculative_arg(k)
@@ -2098,7 +2163,7 @@ class CausalLMHIP:
             # chunked prompt pass: ONE layer's slots as bf16 for the forward kernel (`prefill`), 1 / L of a bf16 cache.  Zeroed: the
             # dequantisation leaves the slots in front of kv_start alone, and the forward kernel multiplies the V rows of a masked
             # key of the first visible tile by p = 0, so they have to be finite (in the bf16 cache the append writes them)
-            self.kv_stage = torch.zeros(B, Smax, self.kvw, dtype=BF16, device=dev) if self.prefill_chunk is not None else None
+            self.kv_stage = torch.zeros(B, Smax, self.kvw, dtype=BF16, device=dev) if self._prompt_chunk(B) is not None else None
         else:
             self.kv_cache = [b16(B, Smax, self.kvw) for _ in range(self.L)]
         fr = torch.outer(torch.arange(Smax, device=dev, dtype=F32), self.inv_freq)
@@ -2167,7 +2232,7 @@ class CausalLMHIP:
         sequence is projected into `last_logits` [B, Vp].  `chunk_hook(i, Cc)` runs in front of chunk i (ORCA sizes its row
         buffers), `layer_hook(l, x)` behind every layer on the chunk's rows [B*Cc, h] (batch-major)."""
         c, h, hq, hkv, hd = self.c, self.h, self.hq, self.hkv, self.hd
-        chunks = prefill_chunks(S, self.prefill_chunk)
+        chunks = prefill_chunks(S, self._prompt_chunk(B))
         pf = self._prefill_alloc(B, S, chunks[0][1])
         Smax, kvw, aw, eps = self._gen_shape[1], self.kvw, hq * hd, c.rms_norm_eps
         kv8 = self._gen_kind == "fp8"
@@ -2216,7 +2281,7 @@ class CausalLMHIP:
         """The KV-cached step, the one body of `decode_step` (w = 1) and `verify_step` (w = k + 1): `tokens` [B, w] (ids), row j of
         a sequence sits at cache slot cur + j (position = slot - left pad); returns logits [B * w, Vp] (batch-major), row j for
         slot cur + j + 1.  The row count M = B * w picks the buffer set, the projection kernel (MXFP4 decode weights: `gemm_w4` at
-        every M; else M > 16: `gemm_wide`, else `gemm_w8` on FP8 decode weights, else `gemm`; the LoRA-merged q|k|v stays on `gemm`) and the RMSNorm fusion (`H.rms_fusable`); the
+        every M; else M > 64 (`set_decode_rows`): `gemm_tall`, else M > 16: `gemm_wide`, else `gemm_w8` on FP8 decode weights, else `gemm`; the LoRA-merged q|k|v stays on `gemm`) and the RMSNorm fusion (`H.rms_fusable`); the
         rotated K | V go to slots [cur, cur + w) of the cache.  w picks the attention alone: w = 1 reads slots [kv_start, cur] without
         a mask, through the kv8 kernel under the FP8 cache, the split-KV kernel from H.DECODE_ATTN_MIN_KEYS keys on where the
         geometry allows, else the forward kernel; w > 1 reads slots [kv_start, cur + w) under the causal mask, the descriptor of
@@ -2243,6 +2308,16 @@ class CausalLMHIP:
         def mm(xin, w_, w8, out, N, K, wide=M > 16, **kw):   # one projection on the bf16 weight, or on its e4m3 / MXFP4 copy (q, scale)
             if mx and w8 is not None:                   # every M up to H.DECODE_MAX_ROWS
                 H.gemm_w4(xin, w8[0], w8[1], out, M, N, K, **kw)
+            elif wide and M > H.DECODE_MAX_ROWS and w8 is None and tall_rows_to_gemm(M, 2 * N if kw.get("act") == 4 else N):
+                if kw.get("act") == 4:                  # bf16 shapes the tile GEMM wins: the unfused gate|up + SwiGLU of `forward`
+                    if bufs.get("gu") is None:          # [M, 2I], made by the first step of this set that takes the route
+                        bufs["gu"] = self._b16(M, 2 * N)
+                    H.gemm(xin, w_, bufs["gu"], M, 2 * N, K)
+                    H.swiglu_fwd(bufs["gu"], out, M, N)
+                else:
+                    H.gemm(xin, w_, out, M, N, K, **kw)
+            elif wide and M > H.DECODE_MAX_ROWS:        # M = 65..256 (`set_decode_rows`): still one weight pass
+                H.gemm_tall(xin, w_ if w8 is None else w8[0], out, M, N, K, scale=None if w8 is None else w8[1], **kw)
             elif wide:                                  # M = 17..64: every weight byte once for all rows
                 H.gemm_wide(xin, w_ if w8 is None else w8[0], out, M, N, K, scale=None if w8 is None else w8[1], **kw)
             elif w8 is not None:
@@ -2326,13 +2401,13 @@ class CausalLMHIP:
         """k + 1 tokens per sequence in one pass: `tokens` [B, k + 1] (ids >= 0; column 0 the last emitted token, columns 1..k the
         drafts), row j of a sequence sits at cache slot cur + j.  Returns logits [B * (k + 1), Vp] (batch-major): row j predicts
         slot cur + j + 1 GIVEN the chunk's tokens in front of it.  `_step_rows` at w = k + 1: `decode_step`'s body over
-        M = B * (k + 1) rows (at most H.DECODE_MAX_ROWS), with the causal attention over slots [kv_start, cur + k] (the forward
+        M = B * (k + 1) rows (at most `row_limit`), with the causal attention over slots [kv_start, cur + k] (the forward
         kernel, or the split-KV verify kernels: `set_speculative(attention=...)`; the FP8 cache needs the latter).  Only slots in
         front of the next step's `cur` are ever trusted: the slots at or behind it hold drafts that were not accepted, and the next
         chunk rewrites them (its slot0 is the new `cur`, its width k + 1) before
         its attention, or any later one, reads them."""
         B, w = tokens.shape
-        assert self._gen_shape[0] == B and B * w <= H.DECODE_MAX_ROWS and cur + w <= self._gen_shape[1]
+        assert self._gen_shape[0] == B and B * w <= self.row_limit and cur + w <= self._gen_shape[1]
         assert self._gen_kind == "bf16" or (self.spec_attention == "split" and self._verify_attn_rows(w - 1))
         return self._step_rows(tokens, cur, kv_start)
 
@@ -2362,8 +2437,8 @@ class CausalLMHIP:
             G = self.hq // self.hkv
             if G * (k + 1) > H.VERIFY_ATTN_MAX_ROWS:
                 return f"fp8 kv cache: {G} x {k + 1} = {G * (k + 1)} query rows per KV head > {H.VERIFY_ATTN_MAX_ROWS}"
-        if B * (k + 1) > H.DECODE_MAX_ROWS:
-            return f"B * (k + 1) = {B * (k + 1)} rows > {H.DECODE_MAX_ROWS}"
+        if B * (k + 1) > self.row_limit:                                     # `set_decode_rows`; MXFP4 decode weights stay at the default
+            return f"B * (k + 1) = {B * (k + 1)} rows > {self.row_limit}"
         return None
 
     @staticmethod
@@ -2550,8 +2625,8 @@ class CausalLMHIP:
         guided = guidance_scale is not None and float(guidance_scale) != 1.0
         if guided and B % 2:
             raise ValueError(f"generate: guidance_scale needs an even number of rows (conditional rows, then one unconditional row each), got {B}")
-        check_decode_rows(B, guided)
-        Bc = B // 2 if guided else B                                         # sequences: rows of the result and of every per-call state
+        self.check_rows(B, guided)
+        Bc = B // 2 if guided else B                                        # sequences: rows of the result and of every per-call state
         use_pen = repetition_penalty is not None and float(repetition_penalty) != 1.0
         chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0)))
         check_speculative_arg(speculate)
@@ -2566,7 +2641,7 @@ class CausalLMHIP:
         kv_start = kv_start.to(torch.int32).contiguous()
         neg_pad = (-kv_start).contiguous()                                   # prompt: position = index - left_pad
         logits = self._step1["logits"]                                       # the prompt's last row goes where the first pick reads
-        if self.prefill_chunk is not None:                                   # lean prompt pass: chunks on rolling buffers, no save set
+        if self._prompt_chunk(B) is not None:                                # lean prompt pass: chunks on rolling buffers, no save set
             self.prefill(x0_filler, B, S, kv_start, logits, layer_hook=layer_hook, chunk_hook=chunk_hook)
         else:
             self.forward(x0_filler, B, S, kv_start, None, False, pos_shift=neg_pad, cos_sin=self.gen_cos_sin, last_logits=logits,
@@ -2935,6 +3010,34 @@ class DeSTA25AudioModel:
         check_prefill_chunk(n)
         self.llm.set_prefill_chunk(n)
 
+    def set_decode_rows(self, n: Optional[int]) -> None:
+        """Row ceiling of a KV-cached step of `generate` / `_generate_step` / the trainer's evaluate: None or 64 (default), or an
+        int in 65..256 (`CausalLMHIP.set_decode_rows`): that many sequences per call, half of it under `guidance_scale`,
+        B (k + 1) <= n under `set_speculative(k)`.  bf16 and FP8 decode weights; MXFP4 stays at 64 rows.  Above 64 audios the
+        encoder and the connector run in slices, above 64 sequences the prompt pass is the lean chunked one.  Anything else raises
+        ValueError and leaves the setting as it was."""
+        check_decode_rows_arg(n)
+        self.llm.set_decode_rows(n)
+
+    def _perceive_sliced(self, feats: torch.Tensor, N: int) -> torch.Tensor:
+        """Encoder + connector of N > PERCEPTION_SLICE audios in equal slices of at most PERCEPTION_SLICE, so that their scratch
+        buffers are sized by a slice: self.enc_all [taps, N*T, d] and the returned audio features [N*K, h] hold, audio by audio,
+        the rows one call over all N would have written."""
+        self.drop_prefetched()                                               # the encoder's scratch is shared with pending prefetches
+        e, con = self.config.encoder_config, self.connector
+        T, nt = e.max_source_positions, len(self.config.target_layer_ids)
+        self.enc_all = self._enc_buf(self._enc_cur, N)
+        af = torch.empty(N * con.K, con.h, dtype=BF16, device=self.device)
+        step = -(-N // -(-N // PERCEPTION_SLICE))
+        part = torch.empty(nt, step * T, e.d_model, dtype=BF16, device=self.device)
+        for a0 in range(0, N, step):
+            n = min(step, N - a0)
+            enc = part if n == step else torch.empty(nt, n * T, e.d_model, dtype=BF16, device=self.device)
+            self.encoder.forward(feats[a0:a0 + n].to(self.device, F32).contiguous(), enc)
+            self.enc_all[:, a0 * T:(a0 + n) * T].copy_(enc)
+            af[a0 * con.K:(a0 + n) * con.K].copy_(con.forward(enc, n))
+        return af
+
     def set_speculative(self, k: Optional[int], scope: str = "greedy", attention: str = "forward") -> None:
         """Decoding of `generate` / `_generate_step` / the trainer's evaluate: None or 0 (default) = one token per step; an
         int k in 1..7 = k draft tokens per step from a lookup in the row's own prompt (the spliced transcription included) and
@@ -3187,7 +3290,7 @@ class DeSTA25AudioModel:
         B, S = input_ids.shape
         if guided and B % 2:
             raise ValueError(f"guidance_scale: inputs hold the conditional rows and then one unconditional row each, got {B} rows")
-        check_decode_rows(B, guided)                                         # before the encoder and the prompt pass run
+        self.llm.check_rows(B, guided)                                       # before the encoder and the prompt pass run
         starts = inputs["context_batch_start_positions"]
         N_audio = len(starts)
         was_training = self.training
@@ -3202,9 +3305,12 @@ class DeSTA25AudioModel:
                     feats = inputs["batch_features"]
                     trs = [t.to(dev) for t in inputs["batch_transcription_ids"]]
                     assert len(starts) == len(trs) == feats.shape[0]
-                    self._encode(feats, N_audio)
                     self.connector.p_drop = 0.0
-                    af = self.connector.forward(self.enc_all, N_audio)
+                    if N_audio > PERCEPTION_SLICE:                           # more audios than a default step has rows: buffers sized by a slice
+                        af = self._perceive_sliced(feats, N_audio)
+                    else:
+                        self._encode(feats, N_audio)
+                        af = self.connector.forward(self.enc_all, N_audio)
                     src = self._src_rows(input_ids, trs, starts, None)
                 else:
                     src = input_ids.to(torch.int32).reshape(-1).contiguous()
@@ -3220,7 +3326,7 @@ class DeSTA25AudioModel:
                     assert N_audio == B and [int(r) for r, _ in starts] == list(range(B)), "orca_hybrid: one audio per text row, in row order"
                     orca = self.orca
                     local16 = orca.local_forward(self.enc_all, N_audio) if cfg.orca_local_enabled else None
-                    pc = self.llm.prefill_chunk                               # chunked prompt pass: row buffers for one chunk (`begin_chunk`)
+                    pc = self.llm._prompt_chunk(B)                            # chunked prompt pass: row buffers for one chunk (`begin_chunk`)
                     orca.begin(af, local16, B, S if pc is None else min(S, pc), None, False, keep_kv=True)
                     if orca.audio is not None:
                         hook, after = orca.inject, orca.begin_decode

@@ -145,6 +145,17 @@ class DeSTA25Trainer:
         self._log_buffer: List[Dict[str, Any]] = []
         self.log_history: List[Dict[str, float]] = []
         self.prediction_step_outputs: List[Dict[str, Any]] = []
+        self._apply_decode_rows(model, cfg)
+
+    @staticmethod
+    def _apply_decode_rows(model, cfg: Any) -> Optional[int]:
+        """`trainer.decode_rows: n` of the config: the row ceiling of evaluate()'s KV-cached steps (`model.set_decode_rows`; absent or
+        null: the model keeps its setting).  Returns what it set."""
+        tr = (cfg.get("trainer") if hasattr(cfg, "get") else getattr(cfg, "trainer", None)) if cfg is not None else None
+        rows = (tr.get("decode_rows") if hasattr(tr, "get") else getattr(tr, "decode_rows", None)) if tr is not None else None
+        if rows is not None:
+            model.set_decode_rows(rows)
+        return rows
 
     def steps_per_epoch(self) -> Optional[int]:
         ds = self.train_dataset

@@ -216,6 +216,20 @@ int desta_gemm_w4a16_nt(const desta_gemm_desc* d, const uint8_t* b_scale_e8m0, i
 int desta_gemm_wide_nt(const desta_gemm_desc* d, const float* b_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Decode at 65..256 rows: the same projections as one weight-streaming launch for up to 256 rows (additive to ABI 8: no struct
+ * changes).
+ *
+ * desta_gemm_tall_nt: C[M,N] = epilogue( A[M,K] . B[N,K]^T ) for 65 <= M <= 256, batch 1; M outside that range returns
+ *   DESTA_EINVAL (17 <= M <= 64 is desta_gemm_wide_nt).  Operands, b_scale, the supported and the rejected features, the K-slice
+ *   workspace (slices * M * N * 4 bytes, 2N for act 4, plus 4096: at most 24 MB on the Llama-3.1-8B shapes) and the fix-up launch
+ *   are those of desta_gemm_wide_nt.  Every weight byte is requested from HBM once for all M rows.  The e4m3 form is bit-identical
+ *   to the bf16 form on the dequantised weight, act 4 to act 0 on the 2N-row weight followed by SwiGLU.  The summation order of an
+ *   output element depends on N, K and on the row-group count alone: 2 groups for 65 <= M <= 128, 4 for 129 <= M <= 256.  Inside
+ *   one class a row's result does not depend on M, on the row's position or on the grid (desta_gemm_set_option 3); across the
+ *   classes, and against desta_gemm_wide_nt, results differ in the last bits. */
+int desta_gemm_tall_nt(const desta_gemm_desc* d, const float* b_scale, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Global-norm clip + Adafactor over a flat fp32 arena.
  * Replaces `clip_grad_norm_(params, max_grad_norm)` (TF:trainer.py:1780-1782) followed by
  * `Adafactor.step` (TF:optimization.py:1203-1294; scale_parameter=False, relative_step=False,

@@ -5,7 +5,7 @@ rate of the decode GEMMs (bytes of frozen LLM weights read per token / token tim
   python tools/decode_bench.py [--config desta25_llama31-8B_Qformer6L] [--batch 8] [--ctx 64] [--prompt-tail 16] [--new 64]
                                [--do-sample --temperature T --top-p P --top-k K --min-p M --repetition-penalty R]
                                [--weights {bf16,fp8,mxfp4}] [--ab [--rounds R]] [--attn-ab [--rounds R]] [--kv {bf16,fp8}] [--kv-ab [--rounds R]]
-                               [--prefill-chunk N[,N...]] [--prefill-ab [--rounds R]]
+                               [--prefill-chunk N[,N...]] [--prefill-ab [--rounds R]] [--rows-ab B1,B2,... [--rounds R]]
 Without --do-sample the decode is greedy (with --repetition-penalty, through the full-chain sampler kernel).
 --weights: what the decode steps stream (`set_decode_weights`; fp8 = weight-only OCP e4m3, half the bytes; mxfp4 = OCP MXFP4,
 0.266 of the bytes).  --ab alternates bf16, fp8 and mxfp4 in ONE process on one model (R rounds of bf16, fp8, mxfp4) and prints one
@@ -18,6 +18,10 @@ the two cache kinds for the chosen --weights in ONE process, R rounds, same repo
 --attn-ab alternates, for the chosen --weights, the decode step's attention dispatch (split-KV kernel from
 H.DECODE_ATTN_MIN_KEYS keys on) with the forward kernel at every length (H.DECODE_ATTN_MIN_KEYS = 1 << 30, the path before the
 split-KV kernel) in ONE process, R rounds, same report.
+--batch above 64 runs with `set_decode_rows(256)` (the tall projections, the lean prompt pass, the sliced encoder).  --rows-ab
+B1,B2,...: alternates the batch sizes (the first rows of the --batch inputs, so --batch is the largest) on bf16 and fp8 decode
+weights in ONE process, R rounds: ms per step, tokens/s and weight GB/s per (rows, weights) with the spread over the rounds, and
+whether each size's tokens/s exceed the first size's beyond the spread.
 --prefill-chunk N: the prompt pass is the lean chunked one (`set_prefill_chunk(N)`) in every leg above.  --prefill-ab alternates
 today's prompt pass (the training forward) and the chunked pass, one leg per N of a comma-separated --prefill-chunk, in ONE
 process for the chosen --kv: prompt ms (one generated token) and `torch.cuda.max_memory_allocated` of each leg, one leg at a time
@@ -55,7 +59,8 @@ def main():
     ap.add_argument("--kv-ab", action="store_true", help="alternate bf16 / fp8 KV cache in this process")
     ap.add_argument("--prefill-chunk", default=None, help="positions per chunk of the lean prompt pass (--prefill-ab: a comma-separated list)")
     ap.add_argument("--prefill-ab", action="store_true", help="alternate today's prompt pass / the chunked pass in this process")
-    ap.add_argument("--rounds", type=int, default=3, help="--ab / --attn-ab / --kv-ab / --prefill-ab: alternations")
+    ap.add_argument("--rows-ab", default=None, help="comma-separated batch sizes (<= --batch) alternated on bf16 / fp8 decode weights in this process")
+    ap.add_argument("--rounds", type=int, default=3, help="--ab / --attn-ab / --kv-ab / --prefill-ab / --rows-ab: alternations")
     a = ap.parse_args()
     chunks = [int(x) for x in a.prefill_chunk.split(",")] if a.prefill_chunk else []
     if a.prefill_ab and not chunks:
@@ -85,6 +90,8 @@ def main():
         ("greedy" + (f" repetition_penalty={a.repetition_penalty}" if a.repetition_penalty is not None else ""))
 
     model.set_kv_cache(a.kv)
+    if B > H.DECODE_MAX_ROWS:                                                # opt in: a KV-cached step of up to 256 rows
+        model.set_decode_rows(H.DECODE_TALL_MAX_ROWS)
     if chunks and not a.prefill_ab:
         model.set_prefill_chunk(chunks[0])
 
@@ -170,7 +177,18 @@ def main():
         print(json.dumps(summary), flush=True)
         return
 
-    def leg(kind):
+    full_inputs = inputs
+
+    def first_rows(b):                                                       # the first b rows of the batch with their audios
+        keep = [i for i, (r, _) in enumerate(full_inputs["context_batch_start_positions"]) if r < b]
+        return {"context_input_ids": full_inputs["context_input_ids"][:b], "context_attention_mask": full_inputs["context_attention_mask"][:b],
+                "context_batch_start_positions": [full_inputs["context_batch_start_positions"][i] for i in keep],
+                "batch_features": full_inputs["batch_features"][keep], "batch_transcription_ids": [full_inputs["batch_transcription_ids"][i] for i in keep]}
+
+    def leg(kind, rows=None):
+        nonlocal B, inputs
+        if rows is not None:
+            B, inputs = rows, first_rows(rows)
         model.set_decode_weights(kind)
         res = []
         for new in (1, a.new):
@@ -194,6 +212,34 @@ def main():
         print(json.dumps(r), flush=True)
         return r
 
+    if a.rows_ab:
+        sizes = [int(x) for x in a.rows_ab.split(",")]
+        assert max(sizes) <= a.batch, "--batch is the largest size of --rows-ab"
+        legs = [(b, kind) for b in sizes for kind in ("bf16", "fp8")]
+        for b, kind in legs:                                                 # warm-up: quantise once, every buffer set once
+            leg(kind, b)
+        runs = {lg: [] for lg in legs}
+        for _ in range(a.rounds):
+            for lg in legs:
+                r = leg(lg[1], lg[0])
+                runs[lg].append((r["ms_per_token_step"], r["tokens_per_s"], r["weight_stream_GBps"], r["prompt_ms"]))
+        model.set_decode_weights("bf16")
+        out = {"rows_ab": f"{a.config} prompt={S} new={a.new} {mode} kv={a.kv}", "rounds": a.rounds, "legs": {}}
+        for (b, kind), v in runs.items():
+            ms, tps = sorted(x[0] for x in v), sorted(x[1] for x in v)
+            out["legs"][f"B{b}_{kind}"] = {"ms_per_step": [x[0] for x in v], "median_ms_per_step": ms[len(ms) // 2], "spread_ms": round(ms[-1] - ms[0], 3),
+                                           "tokens_per_s": [x[1] for x in v], "median_tokens_per_s": tps[len(tps) // 2],
+                                           "spread_tokens_per_s": round(tps[-1] - tps[0], 1), "median_weight_GBps": sorted(x[2] for x in v)[len(v) // 2],
+                                           "median_prompt_ms": sorted(x[3] for x in v)[len(v) // 2]}
+        for kind in ("bf16", "fp8"):
+            base = out["legs"][f"B{sizes[0]}_{kind}"]
+            for b in sizes[1:]:
+                lg = out["legs"][f"B{b}_{kind}"]
+                lg[f"tokens_per_s_vs_B{sizes[0]}"] = round(lg["median_tokens_per_s"] / base["median_tokens_per_s"], 3)
+                lg[f"more_tokens_per_s_than_B{sizes[0]}_beyond_spread"] = bool(
+                    min(lg["tokens_per_s"]) - max(base["tokens_per_s"]) > lg["spread_tokens_per_s"] + base["spread_tokens_per_s"])
+        print(json.dumps(out), flush=True)
+        return
     if a.attn_ab:
         min_keys = H.DECODE_ATTN_MIN_KEYS
         legs = {"split_kv": min_keys, "forward": 1 << 30}
