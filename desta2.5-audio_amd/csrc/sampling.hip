@@ -10,6 +10,12 @@
 // 32-bit keys, and both cut-offs are found by a radix select over those keys with LDS histograms (12 + 10 + 10 bits, three
 // passes each): top-k on counts, top-p on masses e_j = exp(t_j - t_max) held as 2^-40 fixed point, so every sum is an
 // integer sum and its order cannot change the result.  The draw inverts the prefix sum of the kept masses in index order.
+//
+// sample_truncated_k (desta_sample_truncated_rows_bf16) puts TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper
+// between min-p and the draw.  Each renormalises over the survivors so far: one reduction pass per active step gives their
+// Z = sum e, sum e * (-a) (a = t - t_max, both 2^-40 fixed point) and largest key; typical-p adds a three-pass radix select over
+// the keys of d = |a - c| with the same mass bins.  Both kernels are one body, sampling_chain.h, included once per kernel;
+// sample_chain_k compiles to the assembly it had before steps 7-9 existed.
 #include "common.h"
 #include "desta_hip.h"
 
@@ -166,157 +172,23 @@ __global__ __launch_bounds__(SNT) void sample_greedy_k(const bf16_t* __restrict_
         for (int c = tid; c < cols; c += SNT) keep_mask[(long)r * cols + c] = c == pick ? 1 : 0;
 }
 
-__global__ __launch_bounds__(SNT) void sample_chain_k(const bf16_t* __restrict__ x, long ld, int cols, const long* __restrict__ hist,
-                                                      long hist_ld, int hist_len, const long* __restrict__ tail, long tail_ld, int width,
-                                                      float penalty, float temp, int top_k, float top_p, float min_p, unsigned seed_lo,
-                                                      unsigned seed_hi, unsigned step, long* __restrict__ out,
-                                                      unsigned char* __restrict__ keep_mask) {
-    __shared__ u64 bins[SBINS];
-    __shared__ unsigned pen_bits[PEN_MAX_COLS / 32];
-    __shared__ u64 wred[SNT / 64];
-    __shared__ u64 sel[2];
-    const GroupRow g = group_row(width);
-    const int tid = threadIdx.x, r = g.r;
-    const bf16_t* row = x + (long)r * ld;
-    const bool vec = ((uintptr_t)row & 15) == 0;
-    const bool pen = penalty != 1.0f && hist_len + g.j > 0;
-    if (pen) build_penalty_bits(pen_bits, cols, g, hist, hist_ld, hist_len, tail, tail_ld);
-    auto score = [&](int c, bf16_t b) -> float { return penalised(pen_bits, pen, penalty, c, b); };
+// steps 7-9 of desta_sample_truncated_rows_bf16; 1 / 0 / 0 switch a step off
+struct Truncation {
+    float typical_p, epsilon_cutoff, eta_cutoff;
+};
 
-    auto tval = [&](int c, bf16_t b) -> float { return score(c, b) / temp; };   // TemperatureLogitsWarper: an fp32 division
-    const bool do_k = top_k > 0 && top_k < cols;
-    const bool do_p = top_p < 1.0f;
+// the chain kernel and its twin with steps 7-9: one body, sampling_chain.h
+#define CHAIN_KERNEL sample_chain_k
+#define CHAIN_TR 0
+#include "sampling_chain.h"
+#define CHAIN_KERNEL sample_truncated_k
+#define CHAIN_TR 1
+#include "sampling_chain.h"
 
-    // pass 0: row maximum (+ the first top-k digit histogram)
-    if (do_k) {
-        for (int i = tid; i < SBINS; i += SNT) bins[i] = 0ull;
-        __syncthreads();
-    }
-    unsigned kmax = 0u;
-    row_strided(row, cols, vec, [&](int c, bf16_t b) {
-        const unsigned k = f32_key(tval(c, b));
-        kmax = k > kmax ? k : kmax;
-        if (do_k) atomicAdd(&bins[k >> 20], 1ull);
-    });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned ok = __shfl_xor(kmax, o, 64);
-        kmax = ok > kmax ? ok : kmax;
-    }
-    if ((tid & 63) == 0) wred[tid >> 6] = kmax;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < SNT / 64; ++w) kmax = (unsigned)wred[w] > kmax ? (unsigned)wred[w] : kmax;
-    const float tmax = key_f32(kmax);
-    auto mass = [&](float t) -> u64 {                            // exp(t - t_max) in 2^-40 units (0 for -inf)
-        return t > -INFINITY ? (u64)(__expf(t - tmax) * MASS_ONE) : 0ull;
-    };
-
-    // TopKLogitsWarper: keep t >= the k-th largest t (ties with it included) = the key of ascending rank cols - k
-    unsigned kthr = 0u;
-    if (do_k) {
-        u64 m = (u64)(cols - top_k);
-        unsigned prefix = 0u;
-        for (int pass = 0; pass < 3; ++pass) {
-            const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
-            if (pass > 0) {
-                bins[tid] = 0ull;
-                __syncthreads();
-                row_strided(row, cols, vec, [&](int c, bf16_t b) {
-                    const unsigned k = f32_key(tval(c, b));
-                    if ((k >> (shift + 10)) == (prefix >> (shift + 10))) atomicAdd(&bins[(k >> shift) & 1023u], 1ull);
-                });
-                __syncthreads();
-                select_bin<1>(bins, wred, sel, [&](u64) { return m; });
-            } else {
-                __syncthreads();
-                select_bin<SBINS / SNT>(bins, wred, sel, [&](u64) { return m; });
-            }
-            prefix |= (unsigned)sel[0] << shift;
-            m -= sel[1];
-            __syncthreads();
-        }
-        kthr = prefix;
-    }
-
-    // TopPLogitsWarper over the top-k survivors: keep key >= the smallest key K whose ascending cumulative mass exceeds
-    // (1 - top_p) * Z; tokens tied with K are all kept
-    unsigned pthr = 0u;
-    if (do_p) {
-        u64 m = 0;
-        unsigned prefix = 0u;
-        for (int pass = 0; pass < 3; ++pass) {
-            const int shift = pass == 0 ? 20 : (pass == 1 ? 10 : 0);
-            const int nb = pass == 0 ? SBINS : 1024;
-            for (int i = tid; i < nb; i += SNT) bins[i] = 0ull;
-            __syncthreads();
-            row_strided(row, cols, vec, [&](int c, bf16_t b) {
-                const float t = tval(c, b);
-                const unsigned k = f32_key(t);
-                if (k >= kthr && (pass == 0 || (k >> (shift + 10)) == (prefix >> (shift + 10))))
-                    atomicAdd(&bins[pass == 0 ? (k >> 20) : ((k >> shift) & 1023u)], mass(t));
-            });
-            __syncthreads();
-            if (pass == 0) {
-                select_bin<SBINS / SNT>(bins, wred, sel, [&](u64 total) {
-                    u64 cut = (u64)((1.0 - (double)top_p) * (double)total);
-                    cut = cut < total ? cut : total - 1;                 // the maximum (mass 2^40) is always kept
-                    m = cut;
-                    return cut;
-                });
-            } else {
-                select_bin<1>(bins, wred, sel, [&](u64) { return m; });
-            }
-            prefix |= (unsigned)sel[0] << shift;
-            m -= sel[1];
-            __syncthreads();
-        }
-        pthr = prefix;
-    }
-    const unsigned thr = kthr > pthr ? kthr : pthr;
-
-    // MinPLogitsWarper on the survivors: p_i >= min_p * p_max  <=>  exp(t_i - t_max) >= min_p; then the kept masses per
-    // thread over a contiguous index chunk, so the draw's prefix sum runs in index order
-    // (a -inf score, as desta_mask_tokens_bf16 leaves it, has mass 0 and is never kept)
-    auto kept = [&](float t) -> bool { return t > -INFINITY && f32_key(t) >= thr && (min_p <= 0.f || expf(t - tmax) >= min_p); };
-    const int chunk = (((cols + SNT - 1) / SNT) + 7) & ~7;
-    const int c0 = min(cols, tid * chunk), c1 = min(cols, c0 + chunk);
-    u64 mine = 0;
-    row_chunk(row, c0, c1, vec, [&](int c, bf16_t b) {
-        const float t = tval(c, b);
-        const bool keep = kept(t);
-        if (keep) mine += mass(t);
-        if (keep_mask) keep_mask[(long)r * cols + c] = keep ? 1 : 0;
-    });
-    bins[tid] = mine;
-    __syncthreads();
-    u64 target = 0;
-    select_bin<1>(bins, wred, sel, [&](u64 total) {
-        const unsigned u = desta_rng32(seed_lo, seed_hi, ((unsigned long)(step + (unsigned)g.j) << 32) | (unsigned)g.b);   // uint32 sum: wraps
-        target = (u64)((double)(u >> 8) * (1.0 / 16777216.0) * (double)total);   // < total
-        if (total == 0) sel[0] = 0, sel[1] = 0;                                   // no finite score: token 0 (below)
-        return target;
-    });
-    if (tid == (int)sel[0]) {
-        const u64 rem = target - sel[1];
-        u64 run = 0;
-        int tok = -1;
-        row_chunk(row, c0, c1, vec, [&](int c, bf16_t b) {
-            if (tok >= 0) return;
-            const float t = tval(c, b);
-            if (kept(t)) {
-                run += mass(t);
-                if (run > rem) tok = c;
-            }
-        });
-        out[r] = tok >= 0 ? tok : 0;
-    }
-}
-
-// the checks and the launch of both entry points: `batch` sequences of `width` rows each
+// the checks and the launch of every entry point: `batch` sequences of `width` rows each; tr == nullptr: steps 7-9 do not exist
 int sample_launch(const void* logits, int64_t ld, int batch, int width, int cols, const int64_t* hist, int64_t hist_ld, int hist_len,
                   const int64_t* tail, int64_t tail_ld, float repetition_penalty, int do_sample, float temperature, int top_k, float top_p,
-                  float min_p, uint64_t seed, uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream) {
+                  float min_p, const Truncation* tr, uint64_t seed, uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream) {
     DESTA_CHECK_ARG(logits && out && batch > 0 && cols > 0 && ld >= cols, "sample: bad argument");
     DESTA_CHECK_ARG(width >= 1 && width <= SAMPLE_ROWS_MAX_WIDTH, "sample: width %d out of range (1..%d)", width, SAMPLE_ROWS_MAX_WIDTH);
     DESTA_CHECK_ARG(temperature > 0.f, "sample: need temperature > 0");
@@ -329,14 +201,25 @@ int sample_launch(const void* logits, int64_t ld, int batch, int width, int cols
                     "sample: a repetition penalty over %d rows per sequence needs the tail tokens", width);
     DESTA_CHECK_ARG(repetition_penalty == 1.f || (hist_len == 0 && width == 1) || cols <= PEN_MAX_COLS,
                     "sample: a repetition penalty needs cols <= %d", PEN_MAX_COLS);
+    bool truncated = false;
+    if (tr) {
+        DESTA_CHECK_ARG(tr->typical_p > 0.f && tr->typical_p <= 1.f, "sample: need 0 < typical_p <= 1");
+        DESTA_CHECK_ARG(tr->epsilon_cutoff >= 0.f && tr->epsilon_cutoff < 1.f, "sample: need 0 <= epsilon_cutoff < 1");
+        DESTA_CHECK_ARG(tr->eta_cutoff >= 0.f && tr->eta_cutoff < 1.f, "sample: need 0 <= eta_cutoff < 1");
+        truncated = tr->typical_p < 1.f || tr->epsilon_cutoff > 0.f || tr->eta_cutoff > 0.f;
+    }
     if (!do_sample)
         hipLaunchKernelGGL(sample_greedy_k, dim3(batch, width), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
                            (const long*)hist, (long)hist_ld, hist_len, (const long*)tail, (long)tail_ld, width, repetition_penalty,
                            (long*)out, keep_mask);
-    else
+    else if (!truncated)
         hipLaunchKernelGGL(sample_chain_k, dim3(batch, width), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld, cols,
                            (const long*)hist, (long)hist_ld, hist_len, (const long*)tail, (long)tail_ld, width, repetition_penalty,
                            temperature, top_k, top_p, min_p, (unsigned)seed, (unsigned)(seed >> 32), step0, (long*)out, keep_mask);
+    else
+        hipLaunchKernelGGL(sample_truncated_k, dim3(batch, width), dim3(SNT), 0, (hipStream_t)stream, (const bf16_t*)logits, (long)ld,
+                           cols, (const long*)hist, (long)hist_ld, hist_len, (const long*)tail, (long)tail_ld, width, repetition_penalty,
+                           temperature, top_k, top_p, min_p, *tr, (unsigned)seed, (unsigned)(seed >> 32), step0, (long*)out, keep_mask);
     DESTA_CHECK_LAUNCH("sample");
     return DESTA_OK;
 }
@@ -347,7 +230,7 @@ extern "C" int desta_sample_bf16(const void* logits, int64_t ld, int rows, int c
                                  float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
                                  uint64_t seed, uint32_t step, int64_t* out, uint8_t* keep_mask, void* stream) {
     return sample_launch(logits, ld, rows, 1, cols, hist, hist_ld, hist_len, nullptr, 0, repetition_penalty, do_sample, temperature, top_k,
-                         top_p, min_p, seed, step, out, keep_mask, stream);
+                         top_p, min_p, nullptr, seed, step, out, keep_mask, stream);
 }
 
 extern "C" int desta_sample_rows_bf16(const void* logits, int64_t ld, int batch, int width, int cols, const int64_t* hist, int64_t hist_ld,
@@ -355,5 +238,15 @@ extern "C" int desta_sample_rows_bf16(const void* logits, int64_t ld, int batch,
                                       float temperature, int top_k, float top_p, float min_p, uint64_t seed, uint32_t step0, int64_t* out,
                                       uint8_t* keep_mask, void* stream) {
     return sample_launch(logits, ld, batch, width, cols, hist, hist_ld, hist_len, tail, tail_ld, repetition_penalty, do_sample, temperature,
-                         top_k, top_p, min_p, seed, step0, out, keep_mask, stream);
+                         top_k, top_p, min_p, nullptr, seed, step0, out, keep_mask, stream);
+}
+
+extern "C" int desta_sample_truncated_rows_bf16(const void* logits, int64_t ld, int batch, int width, int cols, const int64_t* hist,
+                                                int64_t hist_ld, int hist_len, const int64_t* tail, int64_t tail_ld,
+                                                float repetition_penalty, int do_sample, float temperature, int top_k, float top_p,
+                                                float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff, uint64_t seed,
+                                                uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream) {
+    const Truncation tr = {typical_p, epsilon_cutoff, eta_cutoff};
+    return sample_launch(logits, ld, batch, width, cols, hist, hist_ld, hist_len, tail, tail_ld, repetition_penalty, do_sample, temperature,
+                         top_k, top_p, min_p, &tr, seed, step0, out, keep_mask, stream);
 }

@@ -899,11 +899,25 @@ _sample_chain = _sig("desta_sample_bf16", vp, i64, i32, i32, vp, i64, i32, f32, 
                      vp, vp, vp)
 
 
+def _truncation_on(typical_p, epsilon_cutoff, eta_cutoff):
+    return typical_p != 1.0 or epsilon_cutoff != 0.0 or eta_cutoff != 0.0
+
+
 def sample(logits, ld, rows, cols, out, *, do_sample=True, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, repetition_penalty=1.0,
-           hist=None, hist_len=0, seed=0, step=0, keep_mask=None):
+           hist=None, hist_len=0, seed=0, step=0, keep_mask=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
     """One step of HF's logits chain per row of bf16 logits: repetition penalty over the int64 token history hist[:, :hist_len],
-    then argmax (do_sample=False) or temperature -> top-k -> top-p -> min-p -> one draw (include/desta_hip.h desta_sample_bf16)."""
+    then argmax (do_sample=False) or temperature -> top-k -> top-p -> min-p -> one draw (include/desta_hip.h desta_sample_bf16).
+    typical_p < 1, epsilon_cutoff > 0 or eta_cutoff > 0 put HF's truncation warpers in front of the draw
+    (desta_sample_truncated_rows_bf16 at width 1); without them the call is desta_sample_bf16's, as it always was."""
     hist_ld = 0 if hist is None else hist.stride(0)
+    if _truncation_on(typical_p, epsilon_cutoff, eta_cutoff):
+        global SAMPLE_TRUNCATED_CALLS
+        check(_sample_truncated_rows(p(logits), ld, rows, 1, cols, p(hist), hist_ld, hist_len, None, 0, repetition_penalty,
+                                     int(bool(do_sample)), temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff,
+                                     seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, p(out), p(keep_mask), stream()),
+              "desta_sample_truncated_rows_bf16")
+        SAMPLE_TRUNCATED_CALLS += 1
+        return
     check(_sample_chain(p(logits), ld, rows, cols, p(hist), hist_ld, hist_len, repetition_penalty, int(bool(do_sample)), temperature,
                         top_k, top_p, min_p, seed & 0xFFFFFFFFFFFFFFFF, step & 0xFFFFFFFF, p(out), p(keep_mask), stream()),
           "desta_sample_bf16")
@@ -912,6 +926,9 @@ def sample(logits, ld, rows, cols, out, *, do_sample=True, temperature=1.0, top_
 _sample_top_p_rows = _sig("desta_sample_top_p_rows_bf16", vp, i64, i32, i32, i32, f32, f32, C.c_uint64, C.c_uint32, vp, vp, vp)
 _sample_rows = _sig("desta_sample_rows_bf16", vp, i64, i32, i32, i32, vp, i64, i32, vp, i64, f32, i32, f32, i32, f32, f32, C.c_uint64,
                     C.c_uint32, vp, vp, vp)
+_sample_truncated_rows = _sig("desta_sample_truncated_rows_bf16", vp, i64, i32, i32, i32, vp, i64, i32, vp, i64, f32, i32, f32, i32, f32,
+                              f32, f32, f32, f32, C.c_uint64, C.c_uint32, vp, vp, vp)
+SAMPLE_TRUNCATED_CALLS = 0         # chain launches with typical-p / epsilon / eta steps (one-row and grouped) issued by this process
 SAMPLE_ROWS_CALLS = 0              # grouped chain / penalty sampler launches issued by this process
 SAMPLE_TOP_P_ROWS_CALLS = 0        # grouped top-p sampler launches issued by this process
 
@@ -926,13 +943,23 @@ def sample_top_p_rows(logits, ld, batch, width, cols, temperature, top_p, seed, 
 
 
 def sample_rows(logits, ld, batch, width, cols, out, *, do_sample=True, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0,
-                repetition_penalty=1.0, hist=None, hist_len=0, tail=None, seed=0, step0=0, keep_mask=None):
+                repetition_penalty=1.0, hist=None, hist_len=0, tail=None, seed=0, step0=0, keep_mask=None, typical_p=1.0,
+                epsilon_cutoff=0.0, eta_cutoff=0.0):
     """`sample` over the batch * width rows (batch-major) of a verify step: row (b, j) is row b of a batch-row call at step
     step0 + j whose history is hist[b, :hist_len] followed by tail[b, 1:1 + j] (tail int64 [batch, >= width]: the verify step's
-    input, last emitted token then the drafts) (desta_sample_rows_bf16)."""
-    global SAMPLE_ROWS_CALLS
+    input, last emitted token then the drafts) (desta_sample_rows_bf16; desta_sample_truncated_rows_bf16 when typical_p,
+    epsilon_cutoff or eta_cutoff is active)."""
+    global SAMPLE_ROWS_CALLS, SAMPLE_TRUNCATED_CALLS
     assert hist is None or (hist.dtype == torch.int64 and hist.stride(1) == 1)
     assert tail is None or (tail.dtype == torch.int64 and tail.stride(1) == 1 and tail.shape[0] >= batch and tail.shape[1] >= width)
+    if _truncation_on(typical_p, epsilon_cutoff, eta_cutoff):
+        check(_sample_truncated_rows(p(logits), ld, batch, width, cols, p(hist), 0 if hist is None else hist.stride(0), hist_len, p(tail),
+                                     0 if tail is None else tail.stride(0), repetition_penalty, int(bool(do_sample)), temperature, top_k,
+                                     top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff, seed & 0xFFFFFFFFFFFFFFFF, step0 & 0xFFFFFFFF,
+                                     p(out), p(keep_mask), stream()), "desta_sample_truncated_rows_bf16")
+        SAMPLE_ROWS_CALLS += 1
+        SAMPLE_TRUNCATED_CALLS += 1
+        return
     check(_sample_rows(p(logits), ld, batch, width, cols, p(hist), 0 if hist is None else hist.stride(0), hist_len, p(tail),
                        0 if tail is None else tail.stride(0), repetition_penalty, int(bool(do_sample)), temperature, top_k, top_p, min_p,
                        seed & 0xFFFFFFFFFFFFFFFF, step0 & 0xFFFFFFFF, p(out), p(keep_mask), stream()), "desta_sample_rows_bf16")

@@ -22,6 +22,7 @@ from __future__ import annotations
 import json
 import logging
 import math
+import numbers
 import os
 from collections import OrderedDict
 from dataclasses import dataclass, field, asdict
@@ -409,9 +410,11 @@ _HF_GEN_UNSUPPORTED = {"num_beams": 1, "typical_p": 1.0, "epsilon_cutoff": 0.0, 
 
 # HF's banning processors, honoured by `desta_logit_constraints_bf16` where a caller opts in (`constraints=True` below)
 _HF_GEN_CONSTRAINTS = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_new_tokens")
+# HF's truncation warpers behind min-p, honoured by `desta_sample_truncated_rows_bf16` where a caller opts in (`truncation=True`)
+_HF_GEN_TRUNCATION = ("typical_p", "epsilon_cutoff", "eta_cutoff")
 
 
-def resolve_generation_kwargs(llm_generation_config: dict, *, constraints: bool = False, **explicit) -> dict:
+def resolve_generation_kwargs(llm_generation_config: dict, *, constraints: bool = False, truncation: bool = False, **explicit) -> dict:
     """The sampling settings HF's `generate` would use (TF:generation/utils.py:1806-1808): an explicit argument, else the
     checkpoint's `generation_config.json`, else HF's global default (so top_k = 50 unless someone says otherwise).  `None`
     counts as unset.  Keys other than the sampling settings (max_new_tokens, seed, ...) pass through.  Raises
@@ -419,11 +422,14 @@ def resolve_generation_kwargs(llm_generation_config: dict, *, constraints: bool 
     epsilon / eta cutoffs, top_h, no_repeat_ngram_size, bad_words_ids, suppress_tokens).
     constraints=True: no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens and min_new_tokens are
     resolved as well (explicit, else the file's, else None = off; 0 and [] count as off) and returned for `generate` instead of
-    raising; the other settings of that list still raise."""
+    raising; the other settings of that list still raise.
+    truncation=True: typical_p, epsilon_cutoff and eta_cutoff are resolved as well (explicit, else the file's, else None = off;
+    typical_p = 1.0 and a cutoff of 0.0 count as off) and returned for `generate` instead of raising.  Beam search and top_h
+    raise under every combination."""
     file_cfg = dict(llm_generation_config or {})
     bad = []
     for k, off in _HF_GEN_UNSUPPORTED.items():
-        if constraints and k in _HF_GEN_CONSTRAINTS:
+        if (constraints and k in _HF_GEN_CONSTRAINTS) or (truncation and k in _HF_GEN_TRUNCATION):
             continue
         v = explicit.get(k) if explicit.get(k) is not None else file_cfg.get(k)
         if v is not None and v != off and v != []:
@@ -438,6 +444,10 @@ def resolve_generation_kwargs(llm_generation_config: dict, *, constraints: bool 
         for k in _HF_GEN_CONSTRAINTS:
             v = explicit.get(k) if explicit.get(k) is not None else file_cfg.get(k)
             out[k] = None if (v is None or v == [] or (v == 0 and not isinstance(v, bool))) else v
+    if truncation:
+        for k in _HF_GEN_TRUNCATION:
+            v = explicit.get(k) if explicit.get(k) is not None else file_cfg.get(k)
+            out[k] = None if (v is None or (not isinstance(v, bool) and v == _HF_GEN_UNSUPPORTED[k])) else v
     return out
 
 
@@ -450,6 +460,29 @@ def check_sampling_args(top_k=None, min_p=None, repetition_penalty=None) -> None
         raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k}")
     if min_p is not None and not (isinstance(min_p, (int, float)) and 0 <= min_p <= 1.0):
         raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+
+
+def check_truncation_args(typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> None:
+    """HF's argument checks for TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper (TF:generation/logits_process.py),
+    with HF's messages; None means off, and so do the values HF's `_get_logits_processor` skips the warper for: typical_p = 1.0,
+    epsilon_cutoff = 0.0, eta_cutoff = 0.0."""
+    for name, v, off in (("typical_p", typical_p, 1.0), ("epsilon_cutoff", epsilon_cutoff, 0.0), ("eta_cutoff", eta_cutoff, 0.0)):
+        real = isinstance(v, numbers.Real) and not isinstance(v, bool)     # HF takes float(v): numpy scalars and ints are fine
+        if v is None or (real and v == off):
+            continue
+        if not real:
+            raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {v}")
+        if not (0 < v < 1):
+            raise ValueError(f"`{name}` has to be a float > 0 and < 1, but is {float(v)}")      # HF converts first: 2 reads "2.0"
+
+
+def truncation_kwargs(do_sample: bool, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> dict:
+    """The keyword arguments `H.sample` / `H.sample_rows` take for steps 7-9 of the chain: empty when every step is off or the
+    call does not sample (HF's warpers run under do_sample=True only), so such a call reaches the kernels it always reached."""
+    check_truncation_args(typical_p, epsilon_cutoff, eta_cutoff)
+    kw = dict(typical_p=1.0 if typical_p is None else float(typical_p), epsilon_cutoff=float(epsilon_cutoff or 0.0),
+              eta_cutoff=float(eta_cutoff or 0.0))
+    return kw if do_sample and kw != dict(typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0) else {}
 
 
 def _is_id(v) -> bool:
@@ -2459,7 +2492,7 @@ class CausalLMHIP:
         run all unfinished rows accept, the correction behind it included) and hands back a through a pinned int32: ONE host wait
         per verify step.
         The pick is the plain loop's for emitted position n + j (`pick`, scope "all"): argmax for plain greedy (pick None);
-        `H.sample_rows` for the chain (repetition penalty, top_k, min_p; both do_sample modes) and `H.sample_top_p_rows` otherwise,
+        `H.sample_rows` for the chain (repetition penalty, top_k, min_p, typical_p / epsilon / eta cut-offs; both do_sample modes) and `H.sample_top_p_rows` otherwise,
         at step0 = n.  Two histories are kept apart.  The penalty's is HF's `input_ids`, `pen_hist` [B, Pp + T]: the prompt ids of a
         text-only chat (left pads included), then the emitted tokens, pad for finished rows; `out` is its tail (a view), so the
         accept kernel's store into `out` is the store into it, and row j adds the chunk's j drafts in front of it.  The lookup
@@ -2491,7 +2524,7 @@ class CausalLMHIP:
             elif pick["chain"]:
                 H.sample(logits, self.Vp, B, self.V, self.g_next, do_sample=pick["do_sample"], temperature=pick["temperature"], top_k=pick["top_k"],
                          top_p=pick["top_p"], min_p=pick["min_p"], repetition_penalty=pick["repetition_penalty"], hist=pen_hist, hist_len=Pp,
-                         seed=pick["seed"], step=0)
+                         seed=pick["seed"], step=0, **pick["truncation"])
             else:
                 H.sample_top_p(logits, self.Vp, B, self.V, pick["temperature"], pick["top_p"], pick["seed"], 0, self.g_next)
 
@@ -2504,7 +2537,7 @@ class CausalLMHIP:
             elif pick["chain"]:
                 H.sample_rows(vl, self.Vp, B, w, self.V, pred, do_sample=pick["do_sample"], temperature=pick["temperature"], top_k=pick["top_k"],
                               top_p=pick["top_p"], min_p=pick["min_p"], repetition_penalty=pick["repetition_penalty"], hist=pen_hist,
-                              hist_len=Pp + n, tail=inp, seed=pick["seed"], step0=n)
+                              hist_len=Pp + n, tail=inp, seed=pick["seed"], step0=n, **pick["truncation"])
             else:
                 H.sample_top_p_rows(vl, self.Vp, B, w, self.V, pick["temperature"], pick["top_p"], pick["seed"], n, pred)
         if logprobs is not None:
@@ -2582,7 +2615,8 @@ class CausalLMHIP:
                         repetition_penalty: Optional[float] = None, prompt_ids: Optional[torch.Tensor] = None, chunk_hook=None,
                         logprobs: Optional[int] = None, speculate: Optional[int] = None, draft_tokens: Optional[torch.Tensor] = None,
                         lookup_ids: Optional[torch.Tensor] = None, guidance_scale: Optional[float] = None,
-                        constraints: Optional["ConstraintPlan"] = None):
+                        constraints: Optional["ConstraintPlan"] = None, typical_p: Optional[float] = None,
+                        epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None):
         """Prompt pass + KV-cached decode (greedy, or temperature / top-p sampling with the library's counter RNG).  Returns new token ids [B, n_new] (int64; finished sequences are
         filled with pad_token_id, generation stops early once every sequence has produced an EOS), and, with
         collect_logits, the per-step logits [n_new, B, V] (bf16).  `forced_tokens` [B, T] teacher-forces the
@@ -2619,7 +2653,12 @@ class CausalLMHIP:
         rules see is the penalty's above, kept with a plan even without a chain.  Without guidance the pass runs in place on the
         step's logits, or into a [Bc, Vp] scratch when `logprobs` or collect_logits read them: those keep reporting the raw model
         output.  A row with every token banned yields token 0.  Under `set_speculative(k, scope="all")` the verify rows go through
-        the same pass (`_speculative_loop`); under scope "greedy" the plain loop runs (`spec_stats["reason"] == "logit_constraints"`)."""
+        the same pass (`_speculative_loop`); under scope "greedy" the plain loop runs (`spec_stats["reason"] == "logit_constraints"`).
+        typical_p / epsilon_cutoff / eta_cutoff (None, 1.0 and 0.0 / 0.0: off; sampling only, ignored with do_sample=False as HF's
+        warpers are): HF's TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper behind min-p, steps 7-9 of
+        `desta_sample_truncated_rows_bf16`.  Any of them selects the chain kernel, which runs them in the same launch; guidance and
+        constraints stay in front of it, `logprobs` and collect_logits keep reporting the raw distribution, and under
+        `set_speculative(k, scope="all")` the verify rows take the same three values through the grouped call."""
         assert max_new_tokens >= 1
         check_guidance_arg(guidance_scale)
         guided = guidance_scale is not None and float(guidance_scale) != 1.0
@@ -2628,7 +2667,8 @@ class CausalLMHIP:
         self.check_rows(B, guided)
         Bc = B // 2 if guided else B                                        # sequences: rows of the result and of every per-call state
         use_pen = repetition_penalty is not None and float(repetition_penalty) != 1.0
-        chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0)))
+        trunc = truncation_kwargs(do_sample, typical_p, epsilon_cutoff, eta_cutoff)
+        chain = use_pen or (do_sample and ((top_k is not None and int(top_k) != 0) or (min_p is not None and float(min_p) > 0.0) or bool(trunc)))
         check_speculative_arg(speculate)
         spec_k = (self.speculative if speculate is None else speculate) or 0
         con = constraints if constraints is not None and constraints.active else None
@@ -2662,7 +2702,8 @@ class CausalLMHIP:
             pick = None
             if chain or do_sample:                                           # scope "all": the plain loop's sampler, one row per emitted position
                 pick = dict(chain=chain, do_sample=do_sample, temperature=float(temperature), top_k=int(top_k or 0), top_p=float(top_p),
-                            min_p=float(min_p or 0.0), repetition_penalty=float(repetition_penalty) if use_pen else 1.0, seed=seed)
+                            min_p=float(min_p or 0.0), repetition_penalty=float(repetition_penalty) if use_pen else 1.0, seed=seed,
+                            truncation=trunc)
             return self._speculative_loop(logits, out, finished, eos, S, spec_k, kv_start, int(pad_token_id), collect_logits, draft_tokens, lookup_ids,
                                           pick=pick, pen_hist=hist if chain or con is not None else None, logprobs=logprobs, constraints=con)
         steps_logits = []
@@ -2694,7 +2735,8 @@ class CausalLMHIP:
             if chain:
                 H.sample(scores, self.Vp, Bc, self.V, g_next, do_sample=do_sample, temperature=float(temperature),
                          top_k=int(top_k or 0), top_p=float(top_p), min_p=float(min_p or 0.0),
-                         repetition_penalty=float(repetition_penalty) if use_pen else 1.0, hist=hist, hist_len=P + t, seed=seed, step=t)
+                         repetition_penalty=float(repetition_penalty) if use_pen else 1.0, hist=hist, hist_len=P + t, seed=seed, step=t,
+                         **trunc)
             elif do_sample:
                 H.sample_top_p(scores, self.Vp, Bc, self.V, float(temperature), float(top_p), seed, t, g_next)
             else:
@@ -3246,7 +3288,8 @@ class DeSTA25AudioModel:
     def _generate_step(self, inputs, pad_token_id, temperature=0.7, top_p=0.9, max_new_tokens=512, do_sample=True,
                        eos_token_id=None, forced_tokens=None, collect_logits=False, seed=0, top_k=None, min_p=None,
                        repetition_penalty=None, prompt_in_history=False, logprobs=None, draft_tokens=None, guidance_scale=None,
-                       no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=None):
+                       no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=None,
+                       typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
         """Reference `_generate_step` (modeling_desta25.py:1358-1431): audio features spliced into the prompt
         embeddings, then `llm_model.generate(inputs_embeds=…)` — here the KV-cached decoder on the HIP path.
         Returns ONLY the new tokens, as HF does for inputs_embeds prompts.  do_sample=False: greedy (temperature / top_p
@@ -3273,8 +3316,12 @@ class DeSTA25AudioModel:
         dropped, min_new_tokens bans every EOS id for the first m emitted tokens, and begin_suppress_tokens act on the first one.
         One launch per step sets the banned scores to -inf in front of the pick and behind the guidance
         (`desta_logit_constraints_bf16`); `logprobs` and collect_logits keep the raw model output.  If every token of a step is
-        banned the step yields token 0."""
+        banned the step yields token 0.
+        typical_p / epsilon_cutoff / eta_cutoff: HF's TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper behind min-p, in
+        the chain kernel's launch (`desta_sample_truncated_rows_bf16`); None, 1.0 and 0.0 / 0.0 = off, and with do_sample=False they
+        are accepted and ignored, as HF's warpers are."""
         check_sampling_args(top_k, min_p, repetition_penalty)
+        check_truncation_args(typical_p, epsilon_cutoff, eta_cutoff)
         check_logprobs_arg(logprobs)
         check_guidance_arg(guidance_scale)
         check_constraint_args(no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens, min_new_tokens,
@@ -3350,17 +3397,19 @@ class DeSTA25AudioModel:
                                                 top_p=1.0 if top_p is None else float(top_p), seed=int(seed), layer_hook=hook, after_prompt=after,
                                                 top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty,
                                                 prompt_ids=(input_ids[:B // 2] if guided else input_ids) if prompt_in_history else None,
-                                                chunk_hook=chunk, logprobs=logprobs, guidance_scale=guidance_scale, **extra)
+                                                chunk_hook=chunk, logprobs=logprobs, guidance_scale=guidance_scale, typical_p=typical_p,
+                                                epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, **extra)
         finally:
             self.training = was_training
 
-    def hf_generation_kwargs(self, *, constraints: bool = False, **explicit) -> dict:
+    def hf_generation_kwargs(self, *, constraints: bool = False, truncation: bool = False, **explicit) -> dict:
         """`resolve_generation_kwargs(self.llm_generation_config, **explicit)`: the settings HF's `generate` would use for this
         checkpoint.  `model.generate(msgs, **model.hf_generation_kwargs(temperature=0.7, top_p=0.9, do_sample=True))` samples
         as the reference does (modeling_desta25.py:1419-1427), top_k from the checkpoint or HF's default 50 included.
         constraints=True: the checkpoint's no_repeat_ngram_size / bad_words_ids / suppress_tokens / begin_suppress_tokens /
-        min_new_tokens come along for `generate` instead of raising."""
-        return resolve_generation_kwargs(self.llm_generation_config, constraints=constraints, **explicit)
+        min_new_tokens come along for `generate` instead of raising.  truncation=True: so do its typical_p / epsilon_cutoff /
+        eta_cutoff."""
+        return resolve_generation_kwargs(self.llm_generation_config, constraints=constraints, truncation=truncation, **explicit)
 
     def _asr_whisper(self, waves) -> List[str]:
         """`perception.whisper.generate(input_features, attention_mask=None, max_new_tokens=128)` + `processor.batch_decode(...,
@@ -3422,7 +3471,8 @@ class DeSTA25AudioModel:
 
     def generate(self, messages, temperature=0.7, top_p=0.9, do_sample=True, max_new_tokens=512, seed=0, top_k=None, min_p=None,
                  repetition_penalty=None, logprobs=None, guidance_scale=None, negative_messages=None, no_repeat_ngram_size=None,
-                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=None):
+                 bad_words_ids=None, suppress_tokens=None, begin_suppress_tokens=None, min_new_tokens=None, typical_p=None,
+                 epsilon_cutoff=None, eta_cutoff=None):
         """The reference's chat-level `generate` (modeling_desta25.py:1491-1721): messages -> audio decode -> log-mel -> placeholder
         expansion of every `<|AUDIO|>` -> left-padded tokenisation, pad-shifted start positions, transcription ids ->
         `_generate_step` -> `GenerationOutput(text, audios, generated_ids)`.  Same messages schema, same errors; the front-end
@@ -3443,8 +3493,12 @@ class DeSTA25AudioModel:
         the same names, None = off (see `_generate_step`): no n-gram of that size twice, the listed token sequences / tokens never
         (the listed begin tokens not as the first token), no EOS before m new tokens.  An audio chat matches them against the
         answer alone, a text-only chat against prompt + answer, as HF does for `inputs_embeds` / `input_ids` prompts.  A
-        checkpoint's own settings: `model.generate(msgs, **model.hf_generation_kwargs(constraints=True))`."""
+        checkpoint's own settings: `model.generate(msgs, **model.hf_generation_kwargs(constraints=True))`.
+        typical_p / epsilon_cutoff / eta_cutoff: HF's truncation warpers of the same names behind min-p (locally typical sampling,
+        epsilon and eta sampling), None = off, sampling only (see `_generate_step`).  A checkpoint's own:
+        `model.hf_generation_kwargs(truncation=True)`."""
         check_sampling_args(top_k, min_p, repetition_penalty)
+        check_truncation_args(typical_p, epsilon_cutoff, eta_cutoff)
         check_logprobs_arg(logprobs)
         check_guidance_arg(guidance_scale)
         cons = dict(no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids, suppress_tokens=suppress_tokens,
@@ -3452,6 +3506,7 @@ class DeSTA25AudioModel:
         check_constraint_args(**cons, vocab=getattr(getattr(self, "llm", None), "V", None))
         extra = dict(top_k=top_k, min_p=min_p, repetition_penalty=repetition_penalty)
         extra.update({k: v for k, v in cons.items() if v is not None})
+        extra.update({k: v for k, v in dict(typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff).items() if v is not None})
         if logprobs is not None:
             extra["logprobs"] = logprobs
         if guidance_scale is not None and float(guidance_scale) != 1.0:

@@ -620,8 +620,10 @@ class DeSTA25Trainer:
         """desta_trainer.py:160-189: generate from the context part of the batch; decode when a tokenizer is attached.
         generation_kwargs `logprobs` = n: every prediction row also carries `token_logprobs` (its tokens up to and including the
         first EOS, under the model's own distribution) and `avg_logprob`, their mean.  no_repeat_ngram_size, bad_words_ids,
-        suppress_tokens, begin_suppress_tokens and min_new_tokens reach `_generate_step` when set (None: not passed)."""
-        cons = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_new_tokens")
+        suppress_tokens, begin_suppress_tokens and min_new_tokens reach `_generate_step` when set (None: not passed), and so do
+        typical_p, epsilon_cutoff and eta_cutoff."""
+        cons = ("no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens", "min_new_tokens",
+                "typical_p", "epsilon_cutoff", "eta_cutoff")
         gk = dict(temperature=0.7, top_p=0.9, max_new_tokens=128, do_sample=False, top_k=None, min_p=None, repetition_penalty=None,
                   logprobs=None, **{k: None for k in cons})
         cfg_gk = getattr(getattr(self.cfg, "model", None), "generation_kwargs", None) if self.cfg is not None else None

@@ -736,6 +736,32 @@ int desta_sample_top_p_rows_bf16(const void* logits, int64_t ld, int batch, int 
                                  float temperature, float top_p, uint64_t seed, uint32_t step0,
                                  int64_t* out, uint8_t* keep_mask, void* stream);
 
+/* desta_sample_rows_bf16 with HF's truncation warpers between its step 6 (min-p) and its draw (additive to ABI 8;
+ * `generate(typical_p=, epsilon_cutoff=, eta_cutoff=)`): TypicalLogitsWarper, EpsilonLogitsWarper, EtaLogitsWarper of
+ * TF:generation/logits_process.py in the order of `_get_logits_processor` (TF:generation/utils.py), min_tokens_to_keep = 1.
+ * Same grid, rows, history, tail, counter and fixed-point masses as desta_sample_rows_bf16; width == 1 is the one-row case.
+ * With S the survivors of steps 4-6, a_i = t_i - t_max, e_i = exp(a_i), and every step renormalising over ITS input set
+ * (p_i = e_i / sum of e over that set, as each HF warper takes a fresh softmax of scores that hold -inf on removed tokens):
+ *   7. typical_p = m < 1: c = sum_S p_i a_i, d_i = |a_i - c| (= HF's |-log p_i - H|, as H = log Z - c and -log p_i = log Z - a_i);
+ *      D = the smallest d with sum over {i in S, d_i <= D} of p_i >= m; keep d_i <= D.  Tokens tied with D all stay, the token
+ *      closest to c always stays, and the row's most probable token can go.  typical_p == 1: off.
+ *   8. epsilon_cutoff = eps > 0: over the survivors of step 7 keep p_i >= eps, and every token tied with the maximum score OF
+ *      THOSE SURVIVORS (after step 7 that need not be t_max).  0: off.
+ *   9. eta_cutoff = eta > 0: over the survivors of step 8, H = -sum p_i log p_i, theta = min(eta, sqrt(eta) * exp(-H)); keep
+ *      p_i >= theta, and every token tied with the survivors' maximum.  0: off.
+ *  10. the draw of desta_sample_bf16 (step 7 there) on what is left.
+ * The sums that decide a kept set (Z, sum e a, the mass bins of the radix select over d) are integer sums of 2^-40 fixed point
+ * values, so their order cannot change the result.  keep_mask, -inf scores (never kept), rows without a finite score (nothing
+ * kept, token 0) and greedy mode (do_sample == 0: steps 3-10 do not apply) are as in desta_sample_bf16.  With all three off the
+ * launch IS desta_sample_rows_bf16's: the same kernel, bit-identical picks and keep masks.  DESTA_EINVAL, nothing launched: what
+ * desta_sample_rows_bf16 rejects, and unless 0 < typical_p <= 1, 0 <= epsilon_cutoff < 1, 0 <= eta_cutoff < 1. */
+int desta_sample_truncated_rows_bf16(const void* logits, int64_t ld, int batch, int width, int cols,
+                                     const int64_t* hist, int64_t hist_ld, int hist_len,
+                                     const int64_t* tail, int64_t tail_ld,
+                                     float repetition_penalty, int do_sample, float temperature, int top_k, float top_p, float min_p,
+                                     float typical_p, float epsilon_cutoff, float eta_cutoff,
+                                     uint64_t seed, uint32_t step0, int64_t* out, uint8_t* keep_mask, void* stream);
+
 /* The hard constraints of HF's logits chain on the scores of one decode step (additive to ABI 8; `generate(no_repeat_ngram_size=,
  * bad_words_ids=, suppress_tokens=, begin_suppress_tokens=, min_new_tokens=)`, the loop of `llm_model.generate`
  * modeling_desta25.py:1419 / :1703): NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, SuppressTokensLogitsProcessor,
